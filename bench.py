@@ -13,11 +13,16 @@ What the p2plane line quotes: `value` with the library's defaults -- exact NN re
 query whose neighbour provably cannot have changed skips its search) and frozen pairs on (once a scan's pairs are certified to
 stay, their sums are evaluated from moments instead of streaming the scan; same pairs, float64 sums equal to rounding), and with the
 steps of the timed loop -- enqueued back to back without a host synchronisation, as the contract's loop does -- overlapping on the library's
-two internal lanes (sf_icp_set_pipeline: a step's last, nearly idle launches run under the next step's first).  Measured
-beside it in the same run: `value_no_pipeline` (one lane), `value_no_freeze` (frozen pairs off), `value_no_reuse` (every query searches in every iteration),
-`value_32_in_flight`, `value_upload_inclusive`, `single_scan_latency_ms`, `value_stream_config4`.
+two internal lanes (sf_icp_set_pipeline: a step's last, nearly idle launches run under the next step's first).  A plain run
+sets up, warms up, times `--steps` steps and prints the line; its parity gate checks the timed results against the generating
+transform.  With `--full` the same run goes on to measure beside it: `value_no_pipeline` (one lane), `value_no_freeze` (frozen pairs
+off), `value_no_reuse` (every query searches in every iteration), `value_32_in_flight`, `value_upload_inclusive`, `single_scan_latency_ms`,
+`value_stream_config4`, `value_city`, the per-launch profile and roofline of the dominant kernel, and the single-threaded CPU baseline
+whose pose must match the GPU's (parity gate); with N > 1 the per-rank phase timings, `value_strong` and `value_replicas`.
+`--dump-outputs DIR` writes the last timed step's results (one .npy per field of sf_icp_result, scans in id order) to DIR.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full --dump-outputs bench_outputs
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -87,8 +92,13 @@ def parse():
     ap.add_argument("--tile", action="store_true", help="sf_icp_set_tile_search(always): the searching launches served out of LDS tile by tile (sf_tile.hpp; measured "
                                                         "slower than the walk through the global grid index, which stays the default)")
     ap.add_argument("--no-pipeline", action="store_true", help="sf_icp_set_pipeline(0): consecutive steps do not overlap (every alignment on the context's stream)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extra legs (no-reuse throughput, upload-inclusive rate, single-scan latency)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the extra legs, the per-launch profile and roofline, the CPU baseline and its parity check (N > 1: per-rank "
+                         "phase timings, strong scaling, replicas); off: only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<field>.npy (float32 / float64, scans in id order)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extra legs (no-reuse throughput, upload-inclusive rate, single-scan latency)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, default); gloo to rehearse the N>1 path with several ranks on ONE GPU (rendezvous and barriers only: the data "
@@ -102,6 +112,22 @@ def local_scan(synth, map_sorted_x, center, n_points, scan_id):
     near = map_sorted_x[lo:hi]
     near = near[((near[:, :2] - center[:2]) ** 2).sum(1) < 100.0]
     return synth.make_scan(near, n_points, scan_id=scan_id)[0]
+
+
+def dump_outputs(path, results):
+    """{scan id: result dict} -> path/<field>.npy, one array per field of sf_icp_result over the scans in id order
+    (T: float32 4x4, T64: float64 4x4, error: float32, the integer fields as float64), and scan_ids.npy."""
+    os.makedirs(path, exist_ok=True)
+    ids = sorted(results)
+    rs = [results[b] for b in ids]
+    arrays = {"scan_ids": np.array(ids, dtype=np.float64),
+              "T": np.array([r["T"] for r in rs], dtype=np.float32).reshape(-1, 4, 4),
+              "T64": np.array([r["T64"] for r in rs], dtype=np.float64).reshape(-1, 4, 4),
+              "error": np.array([r["error"] for r in rs], dtype=np.float32)}
+    for k in ("iterations", "converged", "n_corr", "n_research", "flags", "fitness", "rmse"):
+        arrays[k] = np.array([r[k] for r in rs], dtype=np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def main():
@@ -492,6 +518,17 @@ def main():
     else:
         results = results_box["r"]
         delivery = {"mode": "all", "how": "sf_icp_align_sharded fetches every step (blocking)"}
+    if args.dump_outputs:
+        everything = {}
+        for part in gather_stats(results):          # N > 1: every rank holds the results of the scans it took part in
+            everything.update(part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, everything)
+    # frozen pairs in the timed run (config.frozen_pairs): the library's counts of the last alignment, no further step
+    if routed is None:
+        froze_timed = icp.freeze_stats()["froze"] > 0
+    else:
+        froze_timed = not agree(not any(getattr(v[0], "icp", v[0]).freeze_stats()["frozen_at_end"] > 0 for v in routed.mine.values()))
 
     # ---------------- correctness of what was timed: the registrations against the generating transform
     terr = max(synth.pose_error(r["T64"], synth.t_true())[0] for r in results.values()) if results else 0.0
@@ -503,7 +540,7 @@ def main():
 
     # ---------------- the dominant kernel (fused transform + NN + accumulate; ref_cpp: the search kernel), HIP events per launch
     prof = None
-    if routed is None:
+    if routed is None and args.full:
         icp.use_graph(False)
         icp.profile_enable(True)
         prof_steps = max(2, min(4, args.steps))
@@ -534,7 +571,7 @@ def main():
 
     # ---------------- N > 1: what every rank spent where (HIP events around every phase of the sharded loop, on the stream)
     rank_stats, roof_dist = None, None
-    if routed is not None:
+    if routed is not None and args.full:
         cache_b = 32 if args.mode == "p2plane" else 20
         mine_stat = {"rank": rank, "step_ms": elapsed_local / args.steps * 1e3, "map_points": len(mp), "scans": len(my_scans), "resumes": int(routed.resumes)}
         grp = max(routed.mine.items(), key=lambda kv: len(kv[1][2])) if routed.mine else None
@@ -603,7 +640,7 @@ def main():
 
     # ---------------- N > 1, weak scaling: the same machine on `--batch` scans in ALL (strong scaling) for the record
     strong = None
-    if routed is not None and world > 1 and args.scaling == "weak" and not args.no_extras:
+    if routed is not None and world > 1 and args.scaling == "weak" and args.full and not args.no_extras:
         keep_routed = routed
         routed = make_routed(scans[:args.batch])
         step()
@@ -622,7 +659,7 @@ def main():
     # its own scans unsharded, no collective at all.  Reported beside the sharded metric, never as it: it says what the node does when
     # the map fits one GPU, and bounds from above what sharding can reach.
     replicas = None
-    if routed is not None and world > 1 and args.scan_kind == "whole" and not args.no_extras:
+    if routed is not None and world > 1 and args.scan_kind == "whole" and args.full and not args.no_extras:
         full_cloud = api.Cloud(ctx, map_ds)
         full_map = api.Map(ctx, full_cloud, args.cell)
         if args.mode == "p2plane":
@@ -654,7 +691,7 @@ def main():
 
     # ---------------- untimed extra legs: no-reuse throughput, upload-inclusive rate, single-scan latency
     extras = {}
-    if routed is None and not args.no_extras:
+    if routed is None and args.full and not args.no_extras:
         k = max(3, min(10, args.steps))
         if args.mode != "ref_cpp" and not args.no_nn_reuse:
             icp.set_nn_reuse(False)
@@ -787,7 +824,7 @@ def main():
     # (sf_ekf_*), per-scan registration (O3D_P2P to convergence, single launch), every registered scan appended on the
     # device and the map re-voxelised + re-indexed every 10 scans -- tests/test_gpu_config4_stream.py is the same
     # run with its oracle checks.  Wall clock around every callback incl. the Python -> C calls; scans pre-generated.
-    if routed is None and not args.no_extras and args.mode == "p2plane":
+    if routed is None and args.full and not args.no_extras and args.mode == "p2plane":
         from scipy.spatial.transform import Rotation
         from slam_sensor_fusion_amd.localization_flow import ImuEkfMappingFlow
         n_stream, pts_stream = 1000, 20_000
@@ -1032,7 +1069,7 @@ def main():
                                                                                      ("" if (args.no_freeze or args.mode != "p2plane") else
                                                                                       "; once a scan's pairs are certified to stay, their sums come from 96 moments (float64, equal to rounding)")))),
                    "mode": args.mode, "scans_in_flight": B, "scans_in_flight_per_gpu": B // world if args.scaling == "weak" else B, "cell_m": args.cell,
-                   "max_corr_dist_m": max_dist, "nn_reuse": not args.no_nn_reuse, "frozen_pairs": bool((prof is not None and prof["fz"]["froze"] > 0) or (rank_stats is not None and (rank_stats.get("frozen_scans") or {}).get("max", 0) > 0)),
+                   "max_corr_dist_m": max_dist, "nn_reuse": not args.no_nn_reuse, "frozen_pairs": bool(froze_timed or (prof is not None and prof["fz"]["froze"] > 0) or (rank_stats is not None and (rank_stats.get("frozen_scans") or {}).get("max", 0) > 0)),
                    "scan_kind": args.scan_kind,
                    "parallelism": ("map sharded into %d x-slabs (+halo); %s; collective: %s"
                                    % (world, "every scan spans every slab: each rank owns 1/%d of every scan's queries, all-reduce of the normal-equation records once per ICP iteration" % world
@@ -1046,6 +1083,7 @@ def main():
         "parity": {"max_translation_err_vs_truth_m": terr, "max_rotation_err_vs_truth_rad": rerr, "ok": bool(ok_truth)},
         "roofline": roof if roof is not None else roof_dist,
         "setup_s": setup_s,
+        "full": bool(args.full),
     }
     if sharded_run:
         out["ranks"] = rank_stats
@@ -1054,7 +1092,7 @@ def main():
         out["value_replicas"] = replicas
 
     # ---------------- CPU baseline: the oracle (port of the reference path), 1 thread, rank 0, N=1 -- and the parity gate
-    if rank == 0 and world == 1 and not sharded_run and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not sharded_run and args.full and not args.no_cpu_baseline:
         from oracle import oracle as orc
         tb = time.perf_counter()
         tree = orc.KdTreeD(map_ds.astype(np.float64))

@@ -11,7 +11,8 @@ The UTM block is produced by oracle/_ref itself, i.e. by reference code.
 They freeze the oracle (CPU tests) and are what the HIP path is compared with on the GPU
 box, where /root/reference and the oracle's _ref build recipe do not exist.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py          (all of them)
+    python tests/golden/make_golden.py utm      (utm_reference_build.npz alone; needs oracle/_ref)
 """
 import os
 import sys
@@ -99,8 +100,25 @@ def main():
                         map_T_global=mtg, gps_pose=gps, quat=q, quat_pose=orc.quat_to_pose(q, [1.0, 2.0, 3.0]),
                         gains=np.array(orc.pose_gains(np.diag([0.25, 0.25, 0.25]), np.diag([1e-4] * 6))),
                         bf_x=orc.bf_sequence(1.5, 0.1), bf_z=orc.bf_sequence(0.1, 0.05), bf_yaw=orc.bf_sequence(np.pi / 6.0, np.pi / 18.0))
+    utm_reference_build()
     print("golden vectors written to", HERE)
 
 
+def utm_reference_build():
+    """utm_reference_build.npz: UTM of 305 points computed by oracle/_ref (the reference's own geo_lib.hpp), what
+    tests/test_oracle_fusion.py pins the oracle's restatement against, bit for bit, where the reference is not present."""
+    if orc.ref_lib() is None:
+        print("oracle/_ref not built: utm_reference_build.npz left as it is")
+        return
+    rng = np.random.default_rng(0)
+    ll = np.r_[np.c_[rng.uniform(-80, 84, 300), rng.uniform(-180, 180, 300)],
+               [[60.0, 5.0], [0.0, 0.0], [-22.9068, -43.1729], [45.0, 179.99], [10.0, -180.0]]]
+    utm_ref = np.array([orc.ref_ll_to_utm(a, b) for a, b in ll])
+    np.savez_compressed(os.path.join(HERE, "utm_reference_build.npz"), latlon=ll, utm_ref=utm_ref)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["utm"]:
+        utm_reference_build()
+    else:
+        main()

@@ -28,7 +28,7 @@ def test_bench_two_ranks_on_one_gpu(scan_kind):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "4", "--map-points", "2000000", "--scan-points", "140000",
-           "--dist-backend", "gloo", "--scan-kind", scan_kind]
+           "--dist-backend", "gloo", "--scan-kind", scan_kind, "--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=420)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{") and '"metric"' in l][-1]

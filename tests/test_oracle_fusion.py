@@ -1,22 +1,23 @@
-"""Pins the oracle's pose-fusion restatement: UTM against oracle/_ref (the reference's own
-geo_lib.hpp compiled from /root/reference), quaternions against scipy Rotation (which the
+"""Pins the oracle's pose-fusion restatement: UTM against the reference's own geo_lib.hpp (its
+build's output stored in tests/golden, and oracle/_ref itself where it is built), quaternions against scipy Rotation (which the
 reference's Python twin itself uses), StochasticFilter against its documented weights and
 a scripted gate trip, BruteForceAlignment candidate order."""
 import numpy as np
-import pytest
 from scipy.spatial.transform import Rotation
 
 from conftest import load_golden
 
 
 def test_utm_matches_reference_build(orc):
-    if orc.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (reference absent on this machine); golden test covers it")
-    rng = np.random.default_rng(0)
-    for lat, lon in np.c_[rng.uniform(-80, 84, 300), rng.uniform(-180, 180, 300)]:
-        assert orc.ll_to_utm(lat, lon) == orc.ref_ll_to_utm(lat, lon)          # bit-identical doubles
-    for lat, lon in [(60.0, 5.0), (0.0, 0.0), (-22.9068, -43.1729), (45.0, 179.99), (10.0, -180.0)]:
-        assert orc.ll_to_utm(lat, lon) == orc.ref_ll_to_utm(lat, lon)
+    """305 points (300 uniform + 5 edge cases): bit-identical doubles to the reference build's output stored by
+    tests/golden/make_golden.py, and to oracle/_ref itself when it is built."""
+    g = load_golden("utm_reference_build.npz")
+    assert len(g["latlon"]) == 305
+    for (lat, lon), (n, e) in zip(g["latlon"], g["utm_ref"]):
+        assert orc.ll_to_utm(lat, lon) == (n, e)                               # bit-identical doubles
+    if orc.ref_lib() is not None:
+        for lat, lon in g["latlon"]:
+            assert orc.ll_to_utm(lat, lon) == orc.ref_ll_to_utm(lat, lon)
 
 
 def test_utm_golden_from_reference(orc):

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 V=$1; shift
 for t in 0 1 0 1; do
   echo -n "$V=$t: "
-  env $V=$t timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-extras "$@" 2>/dev/null | python3 -c '
+  env $V=$t timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-extras "$@" 2>/dev/null | python3 -c '
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1])
 r=d.get("roofline") or {}

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 for rep in 1 2; do
 for p in "$@"; do
   echo -n "[$p] "
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-extras ${p:+--freeze-params "$p"} $BENCH_EXTRA 2>/dev/null | python3 -c '
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-extras ${p:+--freeze-params "$p"} $BENCH_EXTRA 2>/dev/null | python3 -c '
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1])
 r=d.get("roofline") or {}

@@ -6,7 +6,7 @@ cp $L /tmp/orig.so
 for rep in 1 2; do
 for lib in "$@"; do
   cp $lib $L
-  python bench.py $BENCH_EXTRA --steps 8 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  python bench.py --full $BENCH_EXTRA --steps 8 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print(sys.argv[1], 'scans/s', round(d['value'],1), 'ms/step', round(d['ms_per_step'],3), 'parity', d['parity']['ok'])
