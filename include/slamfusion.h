@@ -359,7 +359,8 @@ int sf_icp_tile_info(sf_icp *icp, int64_t out[12]);
  * Same pairs, same float64 sums up to summation rounding (~1e-13 of a pose).  on: 0 never, 1 (default) when the batch holds
  * at least 0.7 M queries -- a frozen launch costs a fixed latency whatever the batch, a small batch is faster
  * without --, 2 always.  No reference counterpart (the reference searches every point in every iteration,
- * icp_point_to_point.cpp:64-69). */
+ * icp_point_to_point.cpp:64-69).  While a robust kernel is set (sf_icp_set_robust_kernel) P2PLANE never freezes, whatever
+ * `on` says: the moment polynomial assumes unit weights. */
 int sf_icp_set_freeze(sf_icp *icp, int on);
 /* guard = max(guard_scale x motion of the last pose update, guard_min) [m]; a freeze launch is asked for once that is at most
  * guard_max (a larger guard means long active lists), at most max_tries times per alignment, from launch index
@@ -368,6 +369,29 @@ int sf_icp_set_freeze_params(sf_icp *icp, float guard_scale, float guard_min, fl
 /* of the last batched alignment, summed over its scans: {freeze launches that held, thaws (moved beyond the guard),
  * freeze launches that did not hold, active queries of the last freeze launch, scans frozen at the end} */
 int sf_icp_freeze_stats(sf_icp *icp, int64_t out[5]);
+/* Robust M-estimator kernel of SF_ICP_P2PLANE (REF_CPP and O3D_P2P ignore it, as Open3D's point-to-point estimator takes no
+ * kernel).  With r = (y - p) . n the float64 point-to-plane residual of a pair (y the transformed source point, p / n the
+ * neighbour and its normal) and the scale k > 0 in metres, every pair enters the normal equations with the weight w(r):
+ *   SF_ROBUST_NONE    1 (default: the unweighted path, unchanged)
+ *   SF_ROBUST_HUBER   1 if |r| <= k, else k / |r|
+ *   SF_ROBUST_CAUCHY  1 / (1 + (r/k)^2)
+ *   SF_ROBUST_TUKEY   (1 - (r/k)^2)^2 if |r| <= k, else 0
+ *   SF_ROBUST_GM      (k^2 / (k^2 + r^2))^2   (Geman-McClure with k in metres; Open3D's GMLoss takes k in m^2: not equal)
+ * The Huber, Cauchy and Tukey forms are meant to be those of Open3D's TransformationEstimationPointToPlane(kernel); that
+ * parity has not been checked against Open3D itself.  The JtJ and Jtr sums are weighted (sum w J J^T, sum w J r, w formed
+ * in float64); the correspondence count, sum r^2 and sum d^2 are not, so fitness, rmse and n_corr keep their meaning.  A
+ * weighted system that is not positive definite (Tukey zeroing too many pairs) sets SF_ICP_FLAG_SINGULAR and stops that
+ * scan.  Correspondences do not depend on the kernel (the neighbour reuse is unaffected).  The setting is read when an
+ * alignment is enqueued and travels with it (two unfetched alignments keep their own; a captured graph is re-captured when
+ * it changes).  While a kind other than NONE is set, P2PLANE does not freeze (sf_icp_set_freeze) and does not take the tile
+ * search (sf_icp_set_tile_search); the single-launch form and the sharded paths carry the weights.
+ * SF_ERR_INVALID (setting unchanged) for an unknown kind, or for a k that is not finite or <= 0 while kind != NONE. */
+#define SF_ROBUST_NONE 0
+#define SF_ROBUST_HUBER 1
+#define SF_ROBUST_CAUCHY 2
+#define SF_ROBUST_TUKEY 3
+#define SF_ROBUST_GM 4
+int sf_icp_set_robust_kernel(sf_icp *icp, int kind, double k);
 
 /* multi-GPU (map tile-sharded along x with halo): this rank only
  * accumulates queries whose TRANSFORMED x lies in [x_lo, x_hi); per iteration

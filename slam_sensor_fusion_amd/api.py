@@ -20,6 +20,7 @@ SF_ICP_FLAG_FEW_CORR, SF_ICP_FLAG_SINGULAR, SF_ICP_FLAG_SHARD_STALE, SF_ICP_FLAG
 PROF_NN, PROF_REDUCE, PROF_COLLECTIVE, PROF_SOLVE, PROF_SHARD_BUILD = 0, 1, 2, 3, 4
 SF_ERR_COMM = -6
 MODES = {"ref_cpp": SF_ICP_REF_CPP, "o3d_p2p": SF_ICP_O3D_P2P, "p2plane": SF_ICP_P2PLANE}
+ROBUST_KINDS = {"none": 0, "huber": 1, "cauchy": 2, "tukey": 3, "gm": 4}  # SF_ROBUST_*
 
 
 class SlamFusionError(RuntimeError):
@@ -88,6 +89,7 @@ def load_library():
     lib.sf_fusion_compass_to_yaw.restype = C.c_float
     lib.sf_fusion_closest_altitude.restype = C.c_float
     lib.sf_sfilter_pose_zscore.restype = C.c_float
+    lib.sf_icp_set_robust_kernel.argtypes = [C.c_void_p, C.c_int, C.c_double]
     _lib = lib
     return lib
 
@@ -102,7 +104,7 @@ def kernel_source_hash():
     carry the hash of the build their counters were taken on; bench.py only quotes them while it still matches."""
     import hashlib
     h = hashlib.sha256()
-    for name in ("sf_icp.hip", "sf_nn.hpp", "sf_tile.hpp", "sf_order.hpp", "sf_common.hpp"):
+    for name in ("sf_icp.hip", "sf_nn_red_body.inc", "sf_nn.hpp", "sf_tile.hpp", "sf_order.hpp", "sf_common.hpp"):
         with open(os.path.join(_HERE, "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -565,6 +567,14 @@ class Icp:
         False / "off", "auto" (default: batches of at least 0.7 M queries), True / "always"."""
         code = {False: 0, "off": 0, "auto": 1, True: 2, "always": 2}[on]
         _check(self.lib.sf_icp_set_freeze(self.h, C.c_int(code)))
+
+    def set_robust_kernel(self, kind="none", k=None):
+        """Robust M-estimator kernel of point-to-plane ICP (sf_icp_set_robust_kernel; REF_CPP and O3D_P2P ignore it), see
+        include/slamfusion.h.  "none" (default), "huber", "cauchy", "tukey" or "gm" (Geman-McClure), scale k in metres
+        (finite, > 0; ignored for "none").  Each pair's JtJ / Jtr terms are weighted by w(r) of its plane residual; fitness,
+        rmse and n_corr stay unweighted.  P2PLANE does not freeze or take the tile search while a kind is set."""
+        code = ROBUST_KINDS[kind]
+        _check(self.lib.sf_icp_set_robust_kernel(self.h, code, float("nan") if k is None and code != 0 else float(k or 0.0)))
 
     def set_wide_scan_points(self, points):
         """Scans above this many points take the launch list with two queries per lane and may freeze (sf_icp_set_wide_scan_points;

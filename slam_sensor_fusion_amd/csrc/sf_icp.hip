@@ -720,6 +720,23 @@ __device__ __forceinline__ PairTerms pair_terms(const LanePair &P)
     return t;
 }
 
+// Robust kernel of P2PLANE (sf_icp_set_robust_kernel), passed by value to the ROBUST instantiations: every enqueued
+// alignment (and every captured graph) carries its own.  The weight of a pair is w(r) of its float64 point-to-plane
+// residual, by the SF_ROBUST_* formulas of include/slamfusion.h.  Every kernel that sums robust pairs calls this one
+// function, so all of them form the same bits.
+struct RobustArg { int kind; double k; };
+__device__ __forceinline__ double robust_weight(const RobustArg &rk, double r)
+{
+    const double a = fabs(r), k = rk.k;
+    switch (rk.kind) {
+    case SF_ROBUST_HUBER: return a <= k ? 1.0 : k / a;
+    case SF_ROBUST_CAUCHY: { const double q = r / k; return 1.0 / (1.0 + q * q); }
+    case SF_ROBUST_TUKEY: { const double q = r / k, s = 1.0 - q * q; return a <= k ? s * s : 0.0; }
+    case SF_ROBUST_GM: { const double k2 = k * k, s = k2 / (k2 + r * r); return s * s; }
+    default: return 1.0;
+    }
+}
+
 // the 32 record slots of one pair, half h (0: slots 0..15, 1: slots 16..31), added to v.  The products go in as fused
 // multiply-adds (float64 accumulation of this library's own sums -- no reference arithmetic to mirror here, and the vector
 // issue slots are what the kernel runs out of: one instruction per term instead of two)
@@ -759,6 +776,31 @@ __device__ __forceinline__ void add_half(const PairTerms &t, int h, double (&v)[
     }
 }
 
+// add_half<2> of a pair with weight w (robust kernel): the JtJ and Jtr slots take Jw_a = w * J_a; the count, sum r^2 and
+// sum d2 stay unweighted (fitness, rmse and n_corr keep their meaning)
+__device__ __forceinline__ void add_half_robust(const PairTerms &t, int h, double (&v)[16], double w)
+{
+    double Jw[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) Jw[a] = w * t.J[a];
+    if (h == 0) { v[0] += t.wgt; v[1] = fma(t.r, t.r, v[1]); }
+    int k = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int c = a; c < 6; ++c) {
+            if (h == 0 && k < 16) v[k] = fma(Jw[a], t.J[c], v[k]);
+            if (h == 1 && k >= 16) v[k - 16] = fma(Jw[a], t.J[c], v[k - 16]);
+            ++k;
+        }
+    }
+    if (h == 1) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v[7 + a] = fma(Jw[a], t.r, v[7 + a]);
+        v[13] += t.d2;
+    }
+}
+
 #ifdef SF_PHASE_TRACE
 __device__ unsigned long long g_phase_trace[sf::PH_SHARDS * sf::PH_SLOTS];
 #endif
@@ -767,99 +809,20 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red(SfGrid g, SfWindow
                                                 int n, const IcpState *__restrict__ st, float thr, float xlo, float xhi, double *__restrict__ partials, int nblocks,
                                                 const uint32_t *__restrict__ own_off, float4 *__restrict__ qcache, int64_t cache_n, uint32_t *__restrict__ stats)
 {
-    constexpr int NREC = MODE == 2 ? NREC_PLANE : NREC_P2P;
-    // XCD-aware placement: workgroups are dealt round-robin to the 8 XCDs in launch order, so
-    // linear id L runs on XCD L % 8.  Each XCD sweeps its own CONTIGUOUS eighth of the chunks
-    // (chunk = 256 * Q consecutive queries of a scan), all scans of the batch adjacent in time:
-    // with cell-ordered queries, chunk c of every scan covers about the same stretch of the map (to
-    // within a chunk or so), so neighbouring chunks must meet in the same L2.  grid.x is padded
-    // to a multiple of 8.
-    const int L = blockIdx.y * gridDim.x + blockIdx.x;
-    const int kk = L >> 3;
-    const int b = kk % (int)gridDim.y;
-    const int bx = (L & 7) * ((int)gridDim.x >> 3) + kk / (int)gridDim.y;
-    if (bx >= nblocks) return;
-    const IcpState *S = st + b;
-    if (S->done) return;
-    // sharded: X0x/y/z are this rank's compact arrays of owned-query candidates (slab widened by
-    // the margin at the pose the arrays were built at, cell-ordered, scan b at [own_off[b], own_off[b+1]));
-    // the exact slab predicate is still applied per lane
-    const int n_live = SHARD ? (int)(own_off[b + 1] - own_off[b]) : n;
-    if (SHARD && bx * (BLK * Q) >= n_live) return; // k_reduce_only reads only the rows that exist
-    __shared__ sf::WaveNN nn_ws[BLK / 64];
-    __shared__ double stage[BLK / 64][32];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // the pairs are kept, not their terms (13 against 36 registers per query across the next search); the terms are
-    // formed once per half below
-#ifdef SF_PHASE_TRACE
-    sf::PhaseClock pclk, *pc = &pclk;
-    pclk.start();
-#else
-    sf::PhaseClock *pc = nullptr;
-#endif
-    LanePair P[Q];
-    // Q > 1, from the launch on in which most waves only verify: the loads of ALL the lane's queries go out together (one
-    // round trip per wave, Q times the bytes in flight) and, if every lane of the wave certifies every one of its
-    // queries, the pairs come straight from them.  A wave with anything left to search drops what it loaded and takes the
-    // queries one after the other as always -- the same pairs either way, so which path a wave takes changes no bit.
-    bool fast = false;
-    if (Q > 1 && qcache != nullptr && S->cache_live != 0 && S->n_research >= VERIFY_FROM_SEARCH) {
-        const float m_now = (float)S->motion;
-        bool any_need = false;
-#pragma unroll
-        for (int u = 0; u < Q; ++u) {
-            const int slot = bx * (BLK * Q) + u * BLK + (int)threadIdx.x;
-            const QueryIn q = query_in<MODE, SHARD>(X0x, X0y, X0z, n, b, S, xlo, xhi, own_off, qcache, cache_n, true, slot, n_live);
-            sf::NNHit hit, seed;
-            float4 tn;
-            any_need = reuse_certificate(q.valid, q.qx, q.qy, q.qz, thr, m_now, q.e, q.c1, q.c2, hit, tn, seed) || any_need;
-            P[u] = make_pair(q, hit, tn);
-        }
-        fast = __ballot(any_need) == 0ull;
-    }
-    if (!fast) {
-        asm volatile("" ::: "memory"); // nothing loaded above stays live across the searches below
-#pragma unroll
-        for (int u = 0; u < Q; ++u) {
-            const int slot = bx * (BLK * Q) + u * BLK + (int)threadIdx.x;
-            P[u] = nn_pair<MODE, WINDOW, SHARD>(g, w, X0x, X0y, X0z, n, b, S, thr, xlo, xhi, own_off, qcache, cache_n, slot, n_live, &nn_ws[wv], stats, pc);
-        }
-    }
-    // the lane's pairs added, reduced over the wave in two halves of 16 values (keeps the live
-    // registers low enough for 4+ waves per SIMD), staged per wave in LDS
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        double v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v[k] = 0.0;
-#pragma unroll
-        for (int u = 0; u < Q; ++u) {
-            const PairTerms t = pair_terms<MODE>(P[u]);
-            add_half<MODE>(t, h, v);
-        }
-        if (MODE == 1 && h == 1) {
-            const double t1 = wave_reduce_1(v[0]);
-            if (lane == 0) stage[wv][16] = t1;
-        } else {
-            const double t0 = wave_reduce_16(v);
-            if ((lane & 3) == 0) stage[wv][16 * h + (lane >> 2)] = t0;
-        }
-    }
-    SF_PH(pc, 7);
-    __syncthreads();
-    if (threadIdx.x < NREC) {
-        const int c = threadIdx.x;
-        double *dst = partials + ((size_t)b * nblocks + bx) * REC_STRIDE;
-        dst[c] = ((stage[0][c] + stage[1][c]) + stage[2][c]) + stage[3][c];
-    }
-#ifdef SF_PHASE_TRACE
-    SF_PH(pc, 8);
-    pclk.count(14, 1u);
-    if (lane == 0) {
-        unsigned long long *dstp = g_phase_trace + (size_t)(L & (sf::PH_SHARDS - 1)) * sf::PH_SLOTS;
-        for (int i = 0; i < sf::PH_SLOTS; ++i) atomicAdd(&dstp[i], (unsigned long long)pclk.acc[i]);
-    }
-#endif
+    constexpr bool ROBUST = false;
+    [[maybe_unused]] constexpr RobustArg rk{0, 0.0}; // (named by the robust branches only, which this kernel discards)
+#include "sf_nn_red_body.inc"
+}
+
+// P2PLANE under a robust kernel: the pairs, rows and summation order of k_nn_red<2, ...>, the JtJ / Jtr slots weighted
+template <bool WINDOW, bool SHARD, int Q>
+__global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_rob(SfGrid g, SfWindow w, const float *__restrict__ X0x, const float *__restrict__ X0y, const float *__restrict__ X0z,
+                                                    int n, const IcpState *__restrict__ st, float thr, float xlo, float xhi, double *__restrict__ partials, int nblocks,
+                                                    const uint32_t *__restrict__ own_off, float4 *__restrict__ qcache, int64_t cache_n, uint32_t *__restrict__ stats, RobustArg rk)
+{
+    constexpr int MODE = 2;
+    constexpr bool ROBUST = true;
+#include "sf_nn_red_body.inc"
 }
 
 // ------------------------------------------------------------------ query order
@@ -2788,114 +2751,20 @@ __global__ __launch_bounds__(BLK) void k_icp_fused(SfGrid g, SfWindow w, const f
                                                    IcpState *__restrict__ st, float thr, int K, double *__restrict__ partials, int nblocks, uint32_t *__restrict__ bar,
                                                    IcpState *__restrict__ host_out)
 {
-    constexpr int NREC = MODE == 2 ? NREC_PLANE : NREC_P2P;
-    const int b = blockIdx.y, bx = blockIdx.x;
-    __shared__ IcpState S;
-    __shared__ double rec[REC_STRIDE];
-    __shared__ sf::WaveNN nn_ws[BLK / 64];
-    __shared__ double stage[BLK / 64][32];
-    __shared__ int bar_ok;
-    for (int k = threadIdx.x; k < (int)(sizeof(IcpState) / 4); k += BLK) reinterpret_cast<uint32_t *>(&S)[k] = reinterpret_cast<const uint32_t *>(st + b)[k];
-    __syncthreads();
-    uint32_t *ctr = bar + 2 * b, *fin = bar + 2 * b + 1;
-    double *const slab_even = partials + (size_t)b * nblocks * REC_STRIDE, *const slab_odd = partials + ((size_t)gridDim.y + b) * nblocks * REC_STRIDE; // used in turn: see k_ref_fused
-    const int slot = bx * BLK + (int)threadIdx.x;
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool have = slot < n;
-    double x0 = 0.0, y0 = 0.0, z0 = 0.0;
-    if (have) {
-        const size_t o = (size_t)b * n + (size_t)slot;
-        x0 = X0x[o]; y0 = X0y[o]; z0 = X0z[o];
-    }
-    float4 c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0, c2 = c0; // the lane's neighbour cache (k_nn_red keeps it in memory)
-    uint32_t passed = 0;
-    bool alive = true;
-    const int launches = MODE == 1 ? K + 1 : K; // what the launch list enqueues
-    for (int it = 0; it < launches && !S.done; ++it) {
-        double sx = 0, sy = 0, sz = 0;
-        float qx = 0.f, qy = 0.f, qz = 0.f;
-        if (have) {
-            sx = S.T[0] * x0 + S.T[1] * y0 + S.T[2] * z0 + S.T[3];
-            sy = S.T[4] * x0 + S.T[5] * y0 + S.T[6] * z0 + S.T[7];
-            sz = S.T[8] * x0 + S.T[9] * y0 + S.T[10] * z0 + S.T[11];
-            qx = (float)sx; qy = (float)sy; qz = (float)sz;
-        }
-        sf::NNHit hit;
-        float4 tn;
-        sf::NNHit seed;
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        const bool live = REUSE && S.n_research > 0;
-        const bool need = reuse_certificate_pos(have, qx, qy, qz, thr, live ? c0 : z4, live ? c1 : z4, live ? c2 : z4, hit, tn, seed);
-        if (__ballot(need) != 0ull) {
-            const sf::NNHit h = sf::nn_search_wave<WINDOW>(g, w, need, qx, qy, qz, thr, &nn_ws[wv], seed);
-            if (need) {
-                hit = h;
-                if (MODE == 2 && h.j >= 0) tn = g.nrm[h.j];
-                if (REUSE) {
-                    c0 = make_float4(qx, qy, qz, sqrtf(h.lb2));
-                    c1 = make_float4(h.px, h.py, h.pz, __int_as_float(h.j));
-                    c2 = tn;
-                }
-            }
-        }
-        LanePair P;
-        P.sx = sx; P.sy = sy; P.sz = sz;
-        P.px = hit.px; P.py = hit.py; P.pz = hit.pz;
-        P.tn = tn;
-        P.ok = hit.j >= 0;
-        const PairTerms T = pair_terms<MODE>(P);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            double v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = 0.0;
-            add_half<MODE>(T, h, v);
-            if (MODE == 1 && h == 1) {
-                const double t1 = wave_reduce_1(v[0]);
-                if (lane == 0) stage[wv][16] = t1;
-            } else {
-                const double t0 = wave_reduce_16(v);
-                if ((lane & 3) == 0) stage[wv][16 * h + (lane >> 2)] = t0;
-            }
-        }
-        __syncthreads();
-        double *slab = (passed & 1u) ? slab_odd : slab_even;
-        if (threadIdx.x < NREC) {
-            const int c = threadIdx.x;
-            slab[(size_t)bx * REC_STRIDE + c] = ((stage[0][c] + stage[1][c]) + stage[2][c]) + stage[3][c];
-        }
-        ++passed;
-        alive = ref_grid_barrier(ctr, passed * (uint32_t)nblocks, &bar_ok);
-        if (!alive) break;
-        reduce_partials<NREC, BLK>(slab, nblocks, rec);
-        if (threadIdx.x == 0) {
-            for (int c = 0; c < NREC; ++c) S.rec[c] = rec[c];
-            if (MODE == 1) solve_o3d(&S, rec, n, 0, K);
-            else solve_plane(&S, rec, n, K);
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    if (!alive) {
-        if (threadIdx.x == 0) {
-            atomicOr(&st[b].flags, SF_ICP_FLAG_BARRIER_TIMEOUT);
-            if (host_out) host_out[b].flags = SF_ICP_FLAG_BARRIER_TIMEOUT;
-        }
-        return;
-    }
-    if (bx == 0)
-        for (int k = threadIdx.x; k < (int)(sizeof(IcpState) / 4); k += BLK) {
-            const uint32_t v = reinterpret_cast<const uint32_t *>(&S)[k];
-            reinterpret_cast<uint32_t *>(st + b)[k] = v;
-            if (host_out) reinterpret_cast<uint32_t *>(host_out + b)[k] = v;
-        }
-    if (threadIdx.x == 0) {
-        const uint32_t left = __hip_atomic_fetch_add(fin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (left == (uint32_t)nblocks - 1u) {
-            __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(fin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    constexpr bool ROBUST = false;
+    [[maybe_unused]] constexpr RobustArg rk{0, 0.0}; // (named by the robust branches only, which this kernel discards)
+#include "sf_icp_fused_body.inc"
+}
+
+// P2PLANE under a robust kernel in one launch (its own occupancy: fused_capacity asks for it separately)
+template <bool WINDOW, bool REUSE>
+__global__ __launch_bounds__(BLK) void k_icp_fused_rob(SfGrid g, SfWindow w, const float *__restrict__ X0x, const float *__restrict__ X0y, const float *__restrict__ X0z, int n,
+                                                       IcpState *__restrict__ st, float thr, int K, double *__restrict__ partials, int nblocks, uint32_t *__restrict__ bar,
+                                                       IcpState *__restrict__ host_out, RobustArg rk)
+{
+    constexpr int MODE = 2;
+    constexpr bool ROBUST = true;
+#include "sf_icp_fused_body.inc"
 }
 
 } // namespace
@@ -2959,7 +2828,7 @@ struct sf_icp {
     bool fused = true;       // sf_icp_set_fused
     bool last_fused = false; // the last alignment ran as the single launch
     sf::DevBuf bar;          // per scan: {arrival counter, departure counter} of the grid barrier
-    int fused_limit[3] = {-1, -1, -1}; // per mode: workgroups that are certainly resident together (-1: not asked yet)
+    int fused_limit[4] = {-1, -1, -1, -1}; // per mode, [3] P2PLANE under a robust kernel: workgroups that are certainly resident together (-1: not asked yet)
     double fused_share = 0.0; // share of the device the single-launch grid in flight holds in the ledger (0: none)
     int64_t fused_redone = 0; // alignments redone through the launch list after a barrier gave up
     bool inject_timeout = false; // test hook (sf_icp_test_inject_barrier_timeout): treat the next single-launch alignment as timed out
@@ -2975,15 +2844,17 @@ struct sf_icp {
     // it is unchanged; sf_map stamps every build / normals pass with a process-unique generation, DevBuf counts its
     // reallocations (epoch).
     struct GraphKey {
-        int mode = -1, iters = -1, batch = -1, window = -1, ordered = -1, reuse = -1;
+        int mode = -1, iters = -1, batch = -1, window = -1, ordered = -1, reuse = -1, robust_kind = -1;
         int64_t n = -1;
         const void *map = nullptr;
         uint64_t map_generation = 0, epochs = 0;
         float max_corr = 0, accept = 0, eps = 0;
+        double robust_k = 0;
         bool operator==(const GraphKey &o) const
         {
             return mode == o.mode && iters == o.iters && batch == o.batch && window == o.window && ordered == o.ordered && reuse == o.reuse && n == o.n && map == o.map &&
-                   map_generation == o.map_generation && epochs == o.epochs && max_corr == o.max_corr && accept == o.accept && eps == o.eps;
+                   map_generation == o.map_generation && epochs == o.epochs && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
+                   robust_kind == o.robust_kind && robust_k == o.robust_k;
         }
     } graph_key;
     // Consecutive asynchronous alignments of the launch list overlap: an alignment's last launches (frozen pairs: fourteen 16 us
@@ -3063,6 +2934,9 @@ struct sf_icp {
     sf::DevBuf fz_state, fz_part, fz_cnt, fz_ids, fz_all;
     int64_t nn_stats_used = 0;
     static constexpr int64_t NN_STATS_CAP = 1024;
+    // robust kernel of P2PLANE (sf_icp_set_robust_kernel): read at enqueue, passed to the kernels by value
+    int robust_kind = SF_ROBUST_NONE;
+    double robust_k = 0.0;
     // tile search (sf_tile.hpp): the searching launches of large batches
     int tile_mode = 0;              // sf_icp_set_tile_search: 0 off, 1 when the batch is large enough to gain (TILE_AUTO_MIN_QUERIES), 2 whenever possible
     bool tile_on = false;           // this alignment's queries are sorted by tile and its searching launches run k_tile_search
@@ -3080,7 +2954,11 @@ const float *src(sf_icp *icp, int axis)
     return soa(icp->ordered ? icp->Xq : icp->X0, icp->plane, axis);
 }
 
-int fused_capacity(sf_icp *icp, int mode); // (workgroups the single-launch kernels keep resident; defined with them)
+int fused_capacity(sf_icp *icp, int mode, bool robust = false); // (workgroups the single-launch kernels keep resident; defined with them)
+
+// this alignment's pairs are weighted (P2PLANE only; the other modes ignore the setting)
+bool robust_on(const sf_icp *icp, int mode) { return mode == SF_ICP_P2PLANE && icp->robust_kind != SF_ROBUST_NONE; }
+RobustArg robust_arg(const sf_icp *icp) { return RobustArg{icp->robust_kind, icp->robust_k}; }
 
 // AUTO orders when there is enough work for the order to pay for the sort.  Measured, 200 k-point
 // scans, 20 iterations: 1 scan in flight +1.5 % (break-even), 2: +8 %, 4: +32 %, 32: +65 %
@@ -3152,7 +3030,8 @@ bool tile_plan(const SfGrid &g, sf::SfTiles *out)
 
 bool tile_wanted(const sf_icp *icp, int mode)
 {
-    if (icp->tile_mode == 0 || icp->shard || icp->map->window.kind != 0 || (mode != SF_ICP_P2PLANE && mode != SF_ICP_O3D_P2P)) return false;
+    // (k_red_cached sums unit weights: under a robust kernel the searching launches stay with k_nn_red_rob)
+    if (icp->tile_mode == 0 || robust_on(icp, mode) || icp->shard || icp->map->window.kind != 0 || (mode != SF_ICP_P2PLANE && mode != SF_ICP_O3D_P2P)) return false;
     if (icp->qpl == 1) return false; // scans the single-launch kernels can take keep their summation order (and their launch list)
     return icp->tile_mode == 2 || icp->n * icp->batch >= TILE_AUTO_MIN_QUERIES;
 }
@@ -3483,6 +3362,7 @@ sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
     k.n = (mode == SF_ICP_REF_CPP && icp->batch == 1) ? -icp->n_cap : icp->n; // REF_CPP, one scan: any count of the same capacity replays
     k.map = (const void *)icp->map;
     k.map_generation = icp->map->generation;
+    k.robust_kind = robust_on(icp, mode) ? icp->robust_kind : SF_ROBUST_NONE; k.robust_k = robust_on(icp, mode) ? icp->robust_k : 0.0; // (passed by value to the robust kernels)
     k.max_corr = icp->prm.max_corr; k.accept = icp->prm.accept; k.eps = icp->prm.eps + icp->fz_prm.guard_scale * 1.0e-3f + icp->fz_prm.guard_min + icp->fz_prm.guard_max + (float)icp->fz_prm.max_tries; // (the freeze parameters travel by value too)
     const sf::DevBuf *bufs[] = {&icp->X0, &icp->X0r, &icp->X, &icp->Xq, &icp->qcache, &icp->corr, &icp->state, &icp->partials, &icp->d_box, &icp->d_boxes, &icp->n_dev,
                                 &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &icp->fz_state, &icp->fz_part, &icp->fz_cnt, &icp->fz_ids, &icp->fz_all, &icp->tseg, &icp->tile_stats};
@@ -3510,6 +3390,19 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
     uint32_t *stats = nullptr;
     if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + 2 * NN_STATS_SHARDS * icp->nn_stats_used++;
     const bool win = m->window.kind != 0;
+    if (MODE == 2 && robust_on(icp, MODE)) {
+        const RobustArg rk = robust_arg(icp);
+#define SF_LAUNCH_NNRED_ROB(W, S, QQ)                                                                                                                         \
+    hipLaunchKernelGGL((k_nn_red_rob<W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)icp->n, st, thr, icp->xlo, icp->xhi, part, nb, \
+                       icp->own_off.as<uint32_t>(), icp->reuse ? icp->qcache.as<float4>() : nullptr, icp->cache_n, stats, rk)
+        const bool q1 = icp->qpl == 1 || one_per_lane;
+        if (win && sharded) { if (q1) SF_LAUNCH_NNRED_ROB(true, true, 1); else SF_LAUNCH_NNRED_ROB(true, true, SF_WIDE_QPL); }
+        else if (win) { if (q1) SF_LAUNCH_NNRED_ROB(true, false, 1); else SF_LAUNCH_NNRED_ROB(true, false, SF_WIDE_QPL); }
+        else if (sharded) { if (q1) SF_LAUNCH_NNRED_ROB(false, true, 1); else SF_LAUNCH_NNRED_ROB(false, true, SF_WIDE_QPL); }
+        else { if (q1) SF_LAUNCH_NNRED_ROB(false, false, 1); else SF_LAUNCH_NNRED_ROB(false, false, SF_WIDE_QPL); }
+#undef SF_LAUNCH_NNRED_ROB
+        return;
+    }
 #define SF_LAUNCH_NNRED_Q(W, S, QQ)                                                                                                                              \
     hipLaunchKernelGGL((k_nn_red<MODE, W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)icp->n, st, thr, icp->xlo, icp->xhi, part, nb, \
                        icp->own_off.as<uint32_t>(), icp->reuse ? icp->qcache.as<float4>() : nullptr, icp->cache_n, stats)
@@ -3559,7 +3452,7 @@ bool freeze_on(const sf_icp *icp, int mode)
     // eight 1.07 / 0.97, sixteen 1.68 / 1.42)
     const int64_t queries = icp->shard ? icp->own_total : icp->n * icp->batch;
     const bool wanted = icp->freeze == 2 || (icp->freeze == 1 && queries >= FREEZE_AUTO_MIN_QUERIES);
-    return mode == SF_ICP_P2PLANE && wanted && icp->reuse && icp->qpl == SF_WIDE_QPL && icp->map->window.kind == 0 && icp->prm.num_iters > icp->fz_from + 1 &&
+    return mode == SF_ICP_P2PLANE && wanted && !robust_on(icp, mode) && icp->reuse && icp->qpl == SF_WIDE_QPL && icp->map->window.kind == 0 && icp->prm.num_iters > icp->fz_from + 1 &&
            icp->fz_from >= VERIFY_FROM_SEARCH;
 }
 
@@ -3756,11 +3649,14 @@ int resident_workgroups(sf_icp *icp, KERNELS... kernels)
     return std::max(std::min(per_cu - 1, 4), 0) * prop.multiProcessorCount;
 }
 
-int fused_capacity(sf_icp *icp, int mode)
+// robust (P2PLANE): the robust twin of k_icp_fused keeps its own register count, so its residency is asked for separately
+int fused_capacity(sf_icp *icp, int mode, bool robust)
 {
-    int &slot = icp->fused_limit[mode];
+    robust = robust && mode == SF_ICP_P2PLANE;
+    int &slot = icp->fused_limit[robust ? 3 : mode];
     if (slot >= 0) return slot;
-    if (mode == SF_ICP_REF_CPP) slot = resident_workgroups(icp, k_ref_fused<true>, k_ref_fused<false>);
+    if (robust) slot = resident_workgroups(icp, k_icp_fused_rob<true, true>, k_icp_fused_rob<false, true>, k_icp_fused_rob<true, false>, k_icp_fused_rob<false, false>);
+    else if (mode == SF_ICP_REF_CPP) slot = resident_workgroups(icp, k_ref_fused<true>, k_ref_fused<false>);
     else if (mode == SF_ICP_O3D_P2P)
         slot = resident_workgroups(icp, k_icp_fused<1, true, true>, k_icp_fused<1, false, true>, k_icp_fused<1, true, false>, k_icp_fused<1, false, false>);
     else
@@ -3797,7 +3693,7 @@ bool fused_eligible(sf_icp *icp, int mode)
 {
     const int64_t rows = mode == SF_ICP_REF_CPP ? icp->nblocks : icp->nblocks_nn;
     // the single-launch kernels keep one point per lane (rows of 256): wide scans (qpl > 1) are not theirs
-    const int64_t cap = fused_capacity(icp, mode);
+    const int64_t cap = fused_capacity(icp, mode, robust_on(icp, mode));
     if (!(icp->fused && !icp->profiling && !icp->shard && (mode == SF_ICP_REF_CPP || icp->qpl == 1) && cap > 0 && rows * icp->batch <= cap)) return false;
     fused_release(icp); // the previous alignment of this object has been fetched or superseded
     return fused_reserve(icp, (double)(rows * icp->batch) / (double)cap);
@@ -3810,6 +3706,18 @@ void launch_icp_fused(sf_icp *icp, dim3 grid)
     hipStream_t s = icp->ctx->stream;
     const float thr = o3d_thr(icp);
     const bool win = m->window.kind != 0;
+    if (MODE == 2 && robust_on(icp, MODE)) {
+        const RobustArg rk = robust_arg(icp);
+#define SF_LAUNCH_ICPF_ROB(W, R)                                                                                                                                        \
+    hipLaunchKernelGGL((k_icp_fused_rob<W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, icp->state.as<IcpState>(), thr, \
+                       icp->prm.num_iters, icp->partials.as<double>(), icp->nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin, rk)
+        if (win && icp->reuse) SF_LAUNCH_ICPF_ROB(true, true);
+        else if (win) SF_LAUNCH_ICPF_ROB(true, false);
+        else if (icp->reuse) SF_LAUNCH_ICPF_ROB(false, true);
+        else SF_LAUNCH_ICPF_ROB(false, false);
+#undef SF_LAUNCH_ICPF_ROB
+        return;
+    }
 #define SF_LAUNCH_ICPF(W, R)                                                                                                                                               \
     hipLaunchKernelGGL((k_icp_fused<MODE, W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, icp->state.as<IcpState>(), thr, \
                        icp->prm.num_iters, icp->partials.as<double>(), icp->nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin)
@@ -4209,6 +4117,16 @@ void freeze_learn_schedule(sf_icp *icp)
     else if (never * 4 <= icp->batch) icp->fz_from = std::min(std::max(FZ_FROM_DEFAULT, latest), std::max(FZ_FROM_DEFAULT, K - 2));
 }
 } // namespace
+
+extern "C" int sf_icp_set_robust_kernel(sf_icp *icp, int kind, double k)
+{
+    SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
+    SF_CHECK(kind >= SF_ROBUST_NONE && kind <= SF_ROBUST_GM, SF_ERR_INVALID, "unknown robust kernel %d", kind);
+    SF_CHECK(kind == SF_ROBUST_NONE || (std::isfinite(k) && k > 0.0), SF_ERR_INVALID, "the robust kernel's scale must be finite and > 0 (got %g)", k);
+    icp->robust_kind = kind;
+    icp->robust_k = kind == SF_ROBUST_NONE ? 0.0 : k;
+    return SF_OK;
+}
 
 extern "C" int sf_icp_set_freeze_params(sf_icp *icp, float guard_scale, float guard_min, float guard_max, int max_tries, int from_launch)
 {

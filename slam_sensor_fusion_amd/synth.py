@@ -197,3 +197,22 @@ def raycast_scan(boxes, T_sensor, rings=64, azimuths=2032, elev_deg=(-24.8, 2.0)
     ok = t_hit < max_range
     p = d_s[ok] * t_hit[ok, None] + rng.normal(0.0, sigma, (ok.sum(), 3))
     return p.astype(np.float32)
+
+
+def make_cars(boxes, centers, n_cars, radius=(4.0, 15.0), seed=CITY_SEED + 3):
+    """Seeded car-sized boxes (4.5 x 1.8 x 1.5 m, axis-aligned either way, on the ground) within `radius` (min, max) metres
+    of the given sensor positions (centers[k, 2], x / y), clear of the buildings: objects a ray-cast scan sees but a map of
+    the buildings does not hold (parked cars, dynamic objects).  Returns boxes[n_cars, 6] in make_city's layout."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    centers = np.asarray(centers, dtype=np.float64).reshape(-1, 2)
+    out = []
+    while len(out) < n_cars:
+        c = centers[rng.integers(len(centers))]
+        r, a = rng.uniform(*radius), rng.uniform(0.0, 2.0 * np.pi)
+        xy = c + r * np.array([np.cos(a), np.sin(a)])
+        half = np.array([2.25, 0.9]) if rng.uniform() < 0.5 else np.array([0.9, 2.25])
+        car = np.r_[xy - half, 0.0, xy + half, 1.5]
+        clear = lambda b: (car[3] < b[0] - 0.5) | (car[0] > b[3] + 0.5) | (car[4] < b[1] - 0.5) | (car[1] > b[4] + 0.5)
+        if all(clear(b) for b in boxes) and all(clear(b) for b in out):
+            out.append(car)
+    return np.array(out).reshape(-1, 6)

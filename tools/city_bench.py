@@ -10,7 +10,12 @@ One JSON line per (rings, prior error) case: scans/s with the library's defaults
 reuse off; per-launch times, the share of queries that search per launch, and sf_icp_freeze_stats (froze / thawed / voided /
 active share).  Frozen pairs need wide scans (include/slamfusion.h, sf_icp_set_wide_scan_points): above 131 072 points, or above
 65 536 in a batch that no single launch could take -- a 64-ring scan (<= 130 048 returns) in a batch of 64 qualifies.
-   python tools/city_bench.py [--map-points 10000000] [--batch 64] [--rings 64 128] [--prior 0.06:0.3 0.3:1.5]"""
+--dynamic-boxes N adds N seeded car-sized boxes (4.5 x 1.8 x 1.5 m, on the ground around the sensor positions) to the world the
+scans are ray cast in but not to the map (parked cars, dynamic objects); --robust KIND:K adds a run under that robust kernel
+(sf_icp_set_robust_kernel, e.g. tukey:0.1) to every case.  The pose errors against the ray-casting truth (median / p95 /
+max, translation and rotation) are reported for the plain run and, under "robust", for the robust one; a robust kernel
+keeps P2PLANE from freezing, so its fair throughput baseline is scans_per_s_no_freeze.
+   python tools/city_bench.py [--map-points 10000000] [--batch 64] [--rings 64 128] [--prior 0.06:0.3 0.3:1.5] [--dynamic-boxes 40] [--robust tukey:0.1]"""
 import argparse
 import json
 import os
@@ -33,6 +38,13 @@ def timed(icp, ctx, mode, steps, batch):
     return batch * steps / (time.perf_counter() - t0)
 
 
+def pose_errors(res, truths):
+    errs = np.array([synth.pose_error(r["T64"], T) for r, T in zip(res, truths)])
+    return {"max_translation_err_m": float(errs[:, 0].max()), "max_rotation_err_rad": float(errs[:, 1].max()),
+            "median_translation_err_m": float(np.median(errs[:, 0])), "p95_translation_err_m": float(np.percentile(errs[:, 0], 95)),
+            "median_rotation_err_deg": float(np.degrees(np.median(errs[:, 1]))), "p95_rotation_err_deg": float(np.degrees(np.percentile(errs[:, 1], 95)))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--map-points", type=int, default=10_000_000)
@@ -43,6 +55,8 @@ def main():
     ap.add_argument("--rings", type=int, nargs="+", default=[64, 128])
     ap.add_argument("--prior", nargs="+", default=["0.06:0.3", "0.3:1.5"], help="1-sigma prior error per axis, metres:degrees")
     ap.add_argument("--wide-from", type=int, default=0, help="sf_icp_set_wide_scan_points (0: the library's own rule -- above 131 072 points, or above 65 536 in a batch no single launch could take)")
+    ap.add_argument("--dynamic-boxes", type=int, default=0, help="car-sized boxes in the ray-cast world that the map does not hold")
+    ap.add_argument("--robust", default=None, help="KIND:K -- also register under this robust kernel (huber, cauchy, tukey, gm; K in metres)")
     args = ap.parse_args()
     mode = "p2plane"
     ctx = api.Context(0)
@@ -55,13 +69,15 @@ def main():
     mp = api.Map(ctx, cloud, 0.25)
     mp.estimate_normals(0.25)
     cell, dims = mp.cell_size()
+    cars = synth.make_cars(boxes, [(0.0, 0.0)], args.dynamic_boxes, radius=(3.0, 20.0)) if args.dynamic_boxes > 0 else np.zeros((0, 6))
+    world = np.r_[boxes, cars]
     for rings in args.rings:
         rng = np.random.default_rng(77)
         truths, scans = [], []
         while len(scans) < args.batch:
             xy = rng.uniform(-12.0, 12.0, 2)
             T = synth.make_T((xy[0], xy[1], 1.8), (0.0, 0.0, rng.uniform(0, 360)))
-            s = synth.raycast_scan(boxes, T, rings=rings, seed=synth.CITY_SEED + 10 + len(scans))
+            s = synth.raycast_scan(world, T, rings=rings, seed=synth.CITY_SEED + 10 + len(scans))
             if len(s) < 0.45 * rings * 2032:
                 continue
             truths.append(T)
@@ -81,9 +97,7 @@ def main():
             icp.set_initial_batch(inits)
             out = {}
             res = icp.align_batch(mode)
-            errs = [synth.pose_error(r["T64"], T) for r, T in zip(res, truths)]
-            out["max_translation_err_m"], out["max_rotation_err_rad"] = max(e[0] for e in errs), max(e[1] for e in errs)
-            out["median_translation_err_m"] = float(np.median([e[0] for e in errs]))
+            out.update(pose_errors(res, truths))
             out["scans_per_s"] = timed(icp, ctx, mode, args.steps, args.batch)
             fs = icp.freeze_stats()
             out["freeze_stats"] = dict(fs, active_share=fs["active_queries"] / float(n * args.batch), scans=args.batch, wide_from=args.wide_from or "library rule")
@@ -103,11 +117,19 @@ def main():
             icp.set_freeze("auto")
             icp.set_nn_reuse(False)
             out["scans_per_s_no_reuse"] = timed(icp, ctx, mode, max(2, args.steps // 2), args.batch)
+            icp.set_nn_reuse(True)
+            if args.robust:
+                kind, k = args.robust.split(":")
+                icp.set_robust_kernel(kind, float(k))
+                rob = pose_errors(icp.align_batch(mode), truths)
+                rob["scans_per_s"] = timed(icp, ctx, mode, args.steps, args.batch)
+                out["robust"] = dict(kernel=args.robust, **rob)
+                icp.set_robust_kernel("none")
             icp.close()
             print(json.dumps(dict(workload="ring scans (%d x 2032 rays) vs a %.0f m synthetic city, %d samples -> %d map points (voxel 0.1 m), %d scans in flight x %d points, "
                                            "%d %s iterations, prior error %.2f m / %.1f deg (1 sigma per axis)" % (rings, args.extent, args.map_points, n_map, args.batch, n, args.iters,
                                                                                                                   mode, sig_t, sig_r),
-                                  rings=rings, prior_sigma_m=sig_t, prior_sigma_deg=sig_r, points_per_scan=int(n), cell_m=cell, grid=list(dims), **out)), flush=True)
+                                  rings=rings, dynamic_boxes=len(cars), prior_sigma_m=sig_t, prior_sigma_deg=sig_r, points_per_scan=int(n), cell_m=cell, grid=list(dims), **out)), flush=True)
 
 
 if __name__ == "__main__":
