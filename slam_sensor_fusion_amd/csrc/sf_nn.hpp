@@ -362,14 +362,25 @@ __device__ __forceinline__ NNHit nn_search(const SfGrid &g, const SfWindow &w, f
 // minimum of (d2, j) over everything visited; pruning only ever skips ranges that cannot hold a
 // candidate as good as the current best (0.2 % margin), and a task reports ties with the best it
 // started from, so the result does not depend on the order in which lanes finish.
+// Flat rounds (WINDOW = false): a lane does not scan its task's range itself.  The 64 ranges of a round, pruned as above,
+// are laid end to end and their candidates dealt out over the wave, NN_DEAL_K per lane per trip, so a round costs
+// ceil(sum of lengths / (64 NN_DEAL_K)) trips -- about one -- instead of the longest range's ceil(length / 4).  Same
+// visited set, same result, same runner-up bound (the second smallest (d2, j) over what was visited, with the gaps of
+// what was pruned -- which does not depend on the order of the comparisons).  A windowed search keeps one range per
+// lane: there a candidate the window rejects enters the runner-up bound through the lane's running best.
+#ifndef SF_NN_DEAL_K
+#define SF_NN_DEAL_K 2
+#endif
+constexpr int NN_DEAL_K = SF_NN_DEAL_K; // candidate slots per lane in one trip of a flat round
 struct WaveNN {
     unsigned long long best[64]; // (float bits of d2) << 32 | j; j = 0xffffffff: none
     uint32_t lb2[64];            // float bits: lower bound of the squared distance to every point but the best
-    float4 q[64];
+    float4 q[64];                // the query and, in .w, its gxm2
     RowBounds rb0[64];           // bounds of the own cell and its x neighbours (tasks 0, 1, 10)
-    float gap[6][64];            // the owner's gaps (gxm2, gxp2, gym, gyp, gzm, gzp) and ...
+    float gap[5][64];            // the owner's other gaps (gxp2, gym, gyp, gzm, gzp) and ...
     unsigned long long cell0[64]; // ... the linear index of its cell: a task gets its geometry from here instead of recomputing it (~45 instructions per task)
     uint16_t task[64 * 11];      // owner lane << 4 | t, grouped by t
+    alignas(4) uint8_t mark[64 * NN_DEAL_K]; // flat rounds: lane + 1 of the task whose range starts at this slot of the trip, 0 elsewhere
 };
 
 __device__ __forceinline__ unsigned long long pack_hit(float d2, int j) { return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)(uint32_t)j; }
@@ -412,6 +423,76 @@ __device__ __forceinline__ float row_gap2(const QueryGeo &G, int k)
     const float ry = dy < 0 ? G.gym : (dy > 0 ? G.gyp : 0.0f);
     const float rz = dz < 0 ? G.gzm : (dz > 0 ? G.gzp : 0.0f);
     return ry * ry + rz * rz;
+}
+
+// inclusive scan (sum or max) of a 32-bit value over the 64 lanes: shifts of 1, 2, 4, 8 inside each row of 16, then
+// row 0's last lane into row 1 and row 2's into row 3, then lane 31 into rows 2 and 3 -- DPP only, no LDS round trip
+template <bool MAX>
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
+{
+    auto op = [](uint32_t a, uint32_t b) { return MAX ? max(a, b) : a + b; };
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false)); // row_shr:1
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false)); // row_shr:2
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false)); // row_shr:4
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false)); // row_shr:8
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false)); // row_bcast:15 into rows 1, 3
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false)); // row_bcast:31 into rows 2, 3
+    return v;
+}
+
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// one ring-1 task of a round up to its candidate range: the owner's query, the owner's best at the start of the round,
+// the range [a, b) after the x neighbours are pruned (live = false: the whole task is pruned) and the bound that what it
+// prunes contributes to the owner's runner-up bound
+struct RoundTask {
+    int owner;
+    bool live;
+    uint32_t a, b;
+    float bound;
+    float4 Q;
+    unsigned long long start;
+};
+
+__device__ __forceinline__ RoundTask round_task(const SfGrid &g, WaveNN *ws, uint32_t e)
+{
+    const int nx = g.dim[0], ny = g.dim[1];
+    RoundTask T;
+    T.owner = (int)(e >> 4);
+    const int owner = T.owner, t = (int)(e & 15u);
+    T.Q = ws->q[owner];
+    QueryGeo G; // from the owner's entry (cx, cy, cz are not needed: the row is addressed relative to the owner's cell)
+    G.cx = G.cy = G.cz = 0;
+    G.gxm2 = T.Q.w; G.gxp2 = ws->gap[0][owner];
+    G.gym = ws->gap[1][owner]; G.gyp = ws->gap[2][owner]; G.gzm = ws->gap[3][owner]; G.gzp = ws->gap[4][owner];
+    T.start = __atomic_load_n(&ws->best[owner], __ATOMIC_RELAXED);
+    const float cur = __uint_as_float((uint32_t)(T.start >> 32));
+    const bool own_row = t < 2 || t == 10;
+    const float g2 = own_row ? (t == 0 ? G.gxm2 : (t == 1 ? G.gxp2 : 0.0f)) : row_gap2(G, t - 2);
+    T.bound = g2;
+    T.a = T.b = 0;
+    T.live = g2 * 0.998f < cur;
+    if (T.live) {
+        T.bound = 3.0e38f;
+        if (own_row) {
+            const RowBounds rb = ws->rb0[owner];
+            T.a = t == 0 ? rb.s0 : (t == 1 ? rb.s2 : rb.s1 + 4);
+            T.b = t == 0 ? rb.s1 : (t == 1 ? rb.s3 : rb.s2);
+        } else {
+            const long long step = ((long long)row_dz(t - 2) * ny + row_dy(t - 2)) * nx; // the row's cell relative to the owner's (inside the grid: checked when queued)
+            const RowBounds rb = load_row_bounds(g, (size_t)((long long)ws->cell0[owner] + step));
+            const bool xm = (g2 + G.gxm2) * 0.998f < cur, xp = (g2 + G.gxp2) * 0.998f < cur;
+            T.a = xm ? rb.s0 : rb.s1;
+            T.b = xp ? rb.s3 : rb.s2;
+            if (!xm && rb.s0 < rb.s1) T.bound = g2 + G.gxm2;
+            if (!xp && rb.s2 < rb.s3) T.bound = fminf(T.bound, g2 + G.gxp2);
+        }
+    }
+    return T;
 }
 
 // every lane of the wave must call this (lanes without a query pass valid = false: they still work).
@@ -458,6 +539,7 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
     }
     if (valid && seed.j >= 0 && seed.d2 < thr) { hit.d2 = seed.d2; hit.j = seed.j; hit.px = seed.px; hit.py = seed.py; hit.pz = seed.pz; }
     uint32_t mask = 0;
+    float q_gxm2 = 0.0f;
 #ifdef SF_PHASE_TRACE
     QueryGeo G{};
     RowBounds rb0{0, 0, 0, 0};
@@ -499,15 +581,16 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
                 else hit.lb2 = fminf(hit.lb2, gap2);
             }
         }
-        if (mask) { // what the tasks of this query need of its geometry
-            ws->gap[0][lane] = G.gxm2; ws->gap[1][lane] = G.gxp2;
-            ws->gap[2][lane] = G.gym; ws->gap[3][lane] = G.gyp; ws->gap[4][lane] = G.gzm; ws->gap[5][lane] = G.gzp;
+        if (mask) { // what the tasks of this query need of its geometry (gxm2 goes with the query)
+            q_gxm2 = G.gxm2;
+            ws->gap[0][lane] = G.gxp2;
+            ws->gap[1][lane] = G.gym; ws->gap[2][lane] = G.gyp; ws->gap[3][lane] = G.gzm; ws->gap[4][lane] = G.gzp;
             ws->cell0[lane] = ((unsigned long long)G.cz * (unsigned long long)ny + (unsigned long long)G.cy) * (unsigned long long)nx + (unsigned long long)G.cx;
         }
     }
     ws->best[lane] = pack_hit(hit.d2, hit.j);
     ws->lb2[lane] = __float_as_uint(hit.lb2);
-    ws->q[lane] = make_float4(qx, qy, qz, 0.0f);
+    ws->q[lane] = make_float4(qx, qy, qz, q_gxm2);
     int total = 0;
 #pragma unroll
     for (int t = 0; t < 11; ++t) {
@@ -527,61 +610,112 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
     for (int i0 = 0; i0 < total; i0 += 64) {
         SF_PHC(pc, 9, 1u);
         const int idx = i0 + lane;
+        if constexpr (WINDOW) { // one task per lane, its range scanned by the lane itself
 #ifdef SF_PHASE_TRACE
-        unsigned my_trips = 0;
+            unsigned my_trips = 0;
 #endif
-        if (idx < total) {
-            const uint32_t e = ws->task[idx];
-            const int owner = (int)(e >> 4), t = (int)(e & 15u);
-            const float4 Q = ws->q[owner];
-            QueryGeo G; // from the owner's entry (cx, cy, cz are not needed: the row is addressed relative to the owner's cell)
-            G.cx = G.cy = G.cz = 0;
-            G.gxm2 = ws->gap[0][owner]; G.gxp2 = ws->gap[1][owner];
-            G.gym = ws->gap[2][owner]; G.gyp = ws->gap[3][owner]; G.gzm = ws->gap[4][owner]; G.gzp = ws->gap[5][owner];
-            const unsigned long long start = __atomic_load_n(&ws->best[owner], __ATOMIC_RELAXED);
-            const float cur = __uint_as_float((uint32_t)(start >> 32));
-            const bool own_row = t < 2 || t == 10;
-            const float g2 = own_row ? (t == 0 ? G.gxm2 : (t == 1 ? G.gxp2 : 0.0f)) : row_gap2(G, t - 2);
-            float bound = g2; // what this task contributes to the owner's runner-up bound
-            if (g2 * 0.998f < cur) {
-                uint32_t a, b;
-                bound = 3.0e38f;
-                if (own_row) {
-                    const RowBounds rb = ws->rb0[owner];
-                    a = t == 0 ? rb.s0 : (t == 1 ? rb.s2 : rb.s1 + 4);
-                    b = t == 0 ? rb.s1 : (t == 1 ? rb.s3 : rb.s2);
-                } else {
-                    const long long step = ((long long)row_dz(t - 2) * ny + row_dy(t - 2)) * nx; // the row's cell relative to the owner's (inside the grid: checked when queued)
-                    const RowBounds rb = load_row_bounds(g, (size_t)((long long)ws->cell0[owner] + step));
-                    const bool xm = (g2 + G.gxm2) * 0.998f < cur, xp = (g2 + G.gxp2) * 0.998f < cur;
-                    a = xm ? rb.s0 : rb.s1;
-                    b = xp ? rb.s3 : rb.s2;
-                    if (!xm && rb.s0 < rb.s1) bound = g2 + G.gxm2;
-                    if (!xp && rb.s2 < rb.s3) bound = fminf(bound, g2 + G.gxp2);
+            if (idx < total) {
+                const RoundTask T = round_task(g, ws, ws->task[idx]);
+                float bound = T.bound; // what this task contributes to the owner's runner-up bound
+                if (T.live) {
+                    // the task starts from the owner's best as it stands: ties are settled by the index rule of consider(),
+                    // the best itself -- met again in its own range -- is neither taken nor counted as a runner-up
+                    NNHit h;
+                    h.d2 = __uint_as_float((uint32_t)(T.start >> 32));
+                    h.j = (int)(uint32_t)T.start;
+                    h.px = h.py = h.pz = 0.0f;
+                    h.lb2 = 3.0e38f;
+                    scan_range<WINDOW, true>(g, w, T.a, T.b, T.Q.x, T.Q.y, T.Q.z, h);
+#ifdef SF_PHASE_TRACE
+                    my_trips = (T.b - T.a + 3u) / 4u; lane_cands += T.b - T.a; lane_trips += my_trips;
+#endif
+                    bound = fminf(bound, h.lb2);
+                    const unsigned long long mine = pack_hit(h.d2, h.j);
+                    if (mine != T.start) { // something lexicographically smaller: whichever of (the best by now, this candidate) loses is a runner-up
+                        const unsigned long long old = atomicMin(&ws->best[T.owner], mine);
+                        bound = fminf(bound, __uint_as_float((uint32_t)((old > mine ? old : mine) >> 32)));
+                    }
                 }
-                // the task starts from the owner's best as it stands: ties are settled by the index rule of consider(),
-                // the best itself -- met again in its own range -- is neither taken nor counted as a runner-up
-                NNHit h;
-                h.d2 = cur;
-                h.j = (int)(uint32_t)start;
-                h.px = h.py = h.pz = 0.0f;
-                h.lb2 = 3.0e38f;
-                scan_range<WINDOW, true>(g, w, a, b, Q.x, Q.y, Q.z, h);
+                atomicMin(&ws->lb2[T.owner], __float_as_uint(bound));
+            }
 #ifdef SF_PHASE_TRACE
-                my_trips = (b - a + 3u) / 4u; lane_cands += b - a; lane_trips += my_trips;
+            { unsigned m = my_trips; for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o)); SF_PHC(pc, 10, m); }
 #endif
-                bound = fminf(bound, h.lb2);
-                const unsigned long long mine = pack_hit(h.d2, h.j);
-                if (mine != start) { // something lexicographically smaller: whichever of (the best by now, this candidate) loses is a runner-up
-                    const unsigned long long old = atomicMin(&ws->best[owner], mine);
-                    bound = fminf(bound, __uint_as_float((uint32_t)((old > mine ? old : mine) >> 32)));
+        } else {
+            // Flat round.  Each lane prunes its task exactly as above (against the owner's best at the start of the
+            // round) and ends with a range [a, a + len); the ranges are laid end to end by an exclusive scan of len, and
+            // slot s of trip c (s = c * 64 K + k * 64 + lane, k < K) takes the candidate at offset s of that list.
+            uint32_t a = 0, len = 0;
+            int owner = 0;
+            if (idx < total) {
+                const RoundTask T = round_task(g, ws, ws->task[idx]);
+                owner = T.owner;
+                if (T.live) { a = T.a; len = T.b - T.a; }
+                atomicMin(&ws->lb2[owner], __float_as_uint(T.bound));
+            }
+            const uint32_t incl = wave_incl_scan<false>(len);
+            const uint32_t off = incl - len;
+            const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            const uint32_t base = a - off; // the candidate of slot s of this lane's task is base + s (mod 2^32)
+            SF_PHC(pc, 13, tot);
+            uint32_t carry = 0; // lane + 1 of the task that holds the last slot of the previous trip
+            for (uint32_t c0 = 0; c0 < tot; c0 += 64u * NN_DEAL_K) {
+                SF_PHC(pc, 10, 1u);
+                // which task holds each slot: its lane + 1 marked at the slot where its range starts (ranges that are not
+                // empty start at distinct slots), then a running max over the slots
+                for (int i = lane; i < 16 * NN_DEAL_K; i += 64) reinterpret_cast<uint32_t *>(ws->mark)[i] = 0u;
+                __builtin_amdgcn_wave_barrier();
+                if (len != 0u && off - c0 < 64u * NN_DEAL_K && off >= c0) ws->mark[off - c0] = (uint8_t)(lane + 1);
+                wave_sync();
+                uint32_t src[NN_DEAL_K];
+#pragma unroll
+                for (int k = 0; k < NN_DEAL_K; ++k) src[k] = wave_incl_scan<true>((uint32_t)ws->mark[64 * k + lane]);
+#pragma unroll
+                for (int k = 0; k < NN_DEAL_K; ++k) {
+                    src[k] = max(src[k], carry);
+                    carry = (uint32_t)__builtin_amdgcn_readlane((int)src[k], 63);
+                }
+                wave_sync(); // the marks are read before the next trip clears them
+                SF_PHC(pc, 12, (unsigned)__popcll(__ballot(c0 + (uint32_t)lane < tot)));
+                // every slot's load goes out before any is folded in (the folds are LDS atomics: the compiler does not move
+                // a load across them)
+                uint32_t j[NN_DEAL_K];
+                int ow[NN_DEAL_K];
+                float4 p[NN_DEAL_K], Q[NN_DEAL_K];
+                unsigned long long cur[NN_DEAL_K];
+#pragma unroll
+                for (int k = 0; k < NN_DEAL_K; ++k) {
+                    const uint32_t s = c0 + 64u * (uint32_t)k + (uint32_t)lane;
+                    const int from = (int)((src[k] - 1u) & 63u) << 2; // slots past the end read some task: nothing is done with it
+                    j[k] = (uint32_t)__builtin_amdgcn_ds_bpermute(from, (int)base) + s;
+                    ow[k] = __builtin_amdgcn_ds_bpermute(from, owner);
+                    p[k] = load_point(g, j[k], s < tot);
+                }
+#pragma unroll
+                for (int k = 0; k < NN_DEAL_K; ++k) {
+                    Q[k] = ws->q[ow[k]];
+                    cur[k] = __atomic_load_n(&ws->best[ow[k]], __ATOMIC_RELAXED);
+                }
+                // fold each candidate into its owner: whichever of (the owner's best, the candidate) loses is a runner-up,
+                // the best itself met again is neither taken nor counted -- the rule of consider(), so the runner-up bound
+                // comes out the same whatever order the candidates are met in
+#pragma unroll
+                for (int k = 0; k < NN_DEAL_K; ++k) {
+                    const bool live = c0 + 64u * (uint32_t)k + (uint32_t)lane < tot;
+                    const float d2 = l2_simple(Q[k].x, Q[k].y, Q[k].z, p[k].x, p[k].y, p[k].z);
+                    const unsigned long long mine = pack_hit(d2, (int)j[k]);
+                    if (live && mine != cur[k]) {
+                        uint32_t lose = __float_as_uint(d2);
+                        if (mine < cur[k]) {
+                            const unsigned long long old = atomicMin(&ws->best[ow[k]], mine);
+                            lose = (uint32_t)((old > mine ? old : mine) >> 32);
+                        }
+                        atomicMin(&ws->lb2[ow[k]], lose);
+                    }
                 }
             }
-            atomicMin(&ws->lb2[owner], __float_as_uint(bound));
+            wave_sync();
         }
-#ifdef SF_PHASE_TRACE
-        { unsigned m = my_trips; for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o)); SF_PHC(pc, 10, m); }
-#endif
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
