@@ -147,6 +147,21 @@ public:
         return ICPResult(slamfusion::Matrix4f::fromRowMajor(r.T), r.error, r.iterations, r.converged != 0);
     }
 
+    // Extension (no counterpart in the reference): pose covariance and degeneracy of every alignment from now on
+    // (sf_icp_set_covariance, include/slamfusion.h); getAlignmentCovariance() after calculateAlignment() returns the
+    // 6x6 information matrix, covariance (order wx wy wz tx ty tz, T' = Exp(w, t) T), marginal eigenvalues and SF_COV_* flags.
+    void setCovarianceEstimation(bool on, double sensor_sigma = 0.0) { check(sf_icp_set_covariance(icp_, on ? 1 : 0, sensor_sigma)); }
+    void setDegeneracyThresholds(double trans, double rot, double inflate_trans_var = 0.0, double inflate_rot_var = 0.0)
+    {
+        check(sf_icp_set_degeneracy_thresholds(icp_, trans, rot, inflate_trans_var, inflate_rot_var));
+    }
+    sf_icp_covariance getAlignmentCovariance()
+    {
+        sf_icp_covariance c;
+        check(sf_icp_fetch_covariance(icp_, &c));
+        return c;
+    }
+
 private:
     static void check(int rc)
     {

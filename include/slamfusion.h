@@ -393,6 +393,60 @@ int sf_icp_freeze_stats(sf_icp *icp, int64_t out[5]);
 #define SF_ROBUST_GM 4
 int sf_icp_set_robust_kernel(sf_icp *icp, int kind, double k);
 
+/* Pose covariance and degeneracy of an alignment.  With the switch on (sf_icp_set_covariance; default off) every alignment
+ * enqueues, behind its last iteration and on the same stream / lane, ONE more evaluation of the objective it minimised, at
+ * the pose it ended at (the T64 of its result), with its own source, target, max_correspondence_dist, mode and robust
+ * kernel.  No solve changes; an object that never touches the switch computes what it always did.
+ *   Pairs: for every source point s_i = T x_i (float64) its exact nearest map point q_i (normal n_i) -- a fresh search at
+ *     the FINAL pose, on the float32 rounding of s_i like every search of this library, whole map or the attached window
+ *     -- accepted by the mode's own predicate (REF_CPP: d2 < max_correspondence_dist un-squared, as the reference compares;
+ *     O3D_P2P / P2PLANE: d2 < max_correspondence_dist^2).
+ *   Perturbation: T' = Exp(w, t) T, vector order (wx wy wz tx ty tz), map frame -- the convention of the Gauss-Newton step.
+ *   P2PLANE: r_i = n_i . (s_i - q_i), J_i = [s_i x n_i, n_i], w_i = the robust weight of r_i (1 without a kernel);
+ *     H = sum w_i J_i^T J_i, chi2 = sum w_i r_i^2, W = sum w_i, dof = W - 6.
+ *   REF_CPP / O3D_P2P: r_i = s_i - q_i, J_i = [-[s_i]x, I], unit weights; H = sum J_i^T J_i (formed in closed form from n,
+ *     sum s, sum s s^T), chi2 = sum |r_i|^2, W = n_corr, dof = 3 n_corr - 6.
+ *   sigma2_hat = chi2 / dof (0 when dof <= 0); sigma2 = sensor_sigma^2 when a sensor sigma > 0 was set, else sigma2_hat.
+ *   H = V diag(lambda) V^T (cyclic Jacobi, float64); cov = sigma2 V diag(1 / max(lambda_k, SF_COV_EIG_EPS lambda_max)) V^T:
+ *     always finite, symmetric, positive semi-definite.  Any lambda_k <= SF_COV_EIG_EPS lambda_max sets SF_COV_SINGULAR.
+ *     Fewer than 10 pairs (the reference's own floor) set SF_COV_FEW_CORR; info, cov and the degeneracy fields are zero then.
+ *   Degeneracy: the marginal information of the translation, S_t = H_tt - H_tr H_rr^-1 H_rt, and of the rotation,
+ *     S_r = H_rr - H_rt H_tt^-1 H_tr (formed as the inverses of the diagonal blocks of cov / sigma2, so they stay finite
+ *     when H is singular): eigenvalues ascending, DIVIDED BY W, with their eigenvectors as rows.  For P2PLANE
+ *     trace(H_tt) = W, so the smallest normalised translation eigenvalue lies in [0, 1/3] whatever the scan size.
+ *     sf_icp_set_degeneracy_thresholds(trans, rot, inflate_trans_var, inflate_rot_var) (defaults 0 = never) sets
+ *     SF_COV_DEGENERATE_TRANS / _ROT when a normalised eigenvalue is below its threshold and adds, for EVERY flagged
+ *     eigenvector v, inflate * u u^T to cov (u = v embedded in the 6-vector); info stays the pure H.
+ * This is the Hessian (Gauss-Newton / Cramer-Rao style) covariance: it models sensor noise on CORRECT pairs.  It knows
+ * nothing of wrong data association nor of the bias of a sampled map, and where the geometry barely constrains a direction
+ * (a tunnel's axis) the noise of the map normals still leaves a little information per pair, which over thousands of pairs
+ * claims millimetres where the pose is decimetres off.  That is the known weakness of Hessian covariances, and why
+ * LOAM-style stacks threshold eigenvalues instead: let the FLAG (and the inflation), not the magnitude of cov, decide.
+ * The settings are read when an alignment is enqueued and travel with it (part of a captured graph's key).
+ * sf_icp_fetch_covariance: the covariances of the alignment sf_icp_fetch_results last returned (call it first; batch
+ * entries); sf_icp_fetch_covariance_previous: of the alignment sf_icp_fetch_previous returns (callable before or after it,
+ * once).  SF_ERR_STATE when that alignment ran with the switch off, or there is none.  Sharded / stepping alignments
+ * (sf_icp_set_shard, sf_icp_step_*, sf_icp_align_sharded*, sf_icp_align_group) decline: SF_ERR_STATE while the switch is on.
+ * SF_ERR_INVALID: NULL arguments, a negative or non-finite sigma, threshold or inflation. */
+#define SF_COV_EIG_EPS 1e-12
+#define SF_COV_FEW_CORR 1
+#define SF_COV_SINGULAR 2
+#define SF_COV_DEGENERATE_TRANS 4
+#define SF_COV_DEGENERATE_ROT 8
+typedef struct {
+    double info[36];        /* H, row-major, order (wx wy wz tx ty tz) */
+    double cov[36];
+    double sigma2, sigma2_hat, weight_sum;
+    double trans_info[3], trans_dir[9];   /* ascending, / weight_sum; eigenvectors as rows */
+    double rot_info[3], rot_dir[9];
+    int64_t n_corr;
+    int32_t flags;          /* SF_COV_* */
+} sf_icp_covariance;
+int sf_icp_set_covariance(sf_icp *icp, int on, double sensor_sigma);
+int sf_icp_set_degeneracy_thresholds(sf_icp *icp, double trans, double rot, double inflate_trans_var, double inflate_rot_var);
+int sf_icp_fetch_covariance(sf_icp *icp, sf_icp_covariance *out);
+int sf_icp_fetch_covariance_previous(sf_icp *icp, sf_icp_covariance *out);
+
 /* multi-GPU (map tile-sharded along x with halo): this rank only
  * accumulates queries whose TRANSFORMED x lies in [x_lo, x_hi); per iteration
  *   sf_icp_step_begin  -> NN + partial normal equations into the exchange buffer
@@ -646,6 +700,11 @@ int sf_ekf_predict_odometry(sf_ekf *e, const double odom_T_prev[16], const doubl
 int sf_ekf_update_position(sf_ekf *e, const double p_map[3], const double cov[9]);   /* GPS, already in the map frame (sf_fusion_gps_pose) */
 int sf_ekf_update_yaw(sf_ekf *e, double yaw, double var);                            /* compass (sf_fusion_compass_to_yaw) */
 int sf_ekf_update_pose(sf_ekf *e, const double T[16], const double cov_pos[3], const double cov_rot[3]);  /* ICP result */
+/* The same update with the ICP's own 6x6 covariance (sf_icp_covariance::cov, order (wx wy wz tx ty tz), left perturbation
+ * T' = Exp(w, t) T of the measured pose).  Innovation as above: y = (p_meas - p, Log(R^T R_meas)).  To first order the
+ * perturbed measurement is p' = p_meas + w x p_meas + t and R' = (I + [w]x) R_meas = R_meas Exp(R_meas^T w), so the filter's
+ * measurement error is (dp, dtheta) = A (w, t) with A = [[-[p_meas]x, I], [R_meas^T, 0]] and the measurement noise A cov A^T. */
+int sf_ekf_update_pose_cov(sf_ekf *e, const double T[16], const double cov[36]);
 int sf_ekf_get(const sf_ekf *e, double T[16], double v[3], double P[81]);            /* any output may be NULL; P = the (dp, dv, dtheta) block */
 int sf_ekf_get_full(const sf_ekf *e, double gyro_bias[3], double accel_bias[3], double P[225]); /* biases and the whole 15x15 covariance */
 

@@ -43,6 +43,22 @@ class IcpResult(C.Structure):
                     fitness=float(self.fitness), rmse=float(self.rmse))
 
 
+COV_FLAGS = {"few_corr": 1, "singular": 2, "degenerate_trans": 4, "degenerate_rot": 8}  # SF_COV_*
+
+
+class IcpCovariance(C.Structure):
+    """sf_icp_covariance: pose covariance and degeneracy of one alignment, order (wx wy wz tx ty tz), T' = Exp(w, t) T."""
+    _fields_ = [("info", C.c_double * 36), ("cov", C.c_double * 36), ("sigma2", C.c_double), ("sigma2_hat", C.c_double),
+                ("weight_sum", C.c_double), ("trans_info", C.c_double * 3), ("trans_dir", C.c_double * 9),
+                ("rot_info", C.c_double * 3), ("rot_dir", C.c_double * 9), ("n_corr", C.c_int64), ("flags", C.c_int32)]
+
+    def as_dict(self):
+        a = lambda f, *shape: np.array(f, dtype=np.float64).reshape(shape)
+        return dict(info=a(self.info, 6, 6), cov=a(self.cov, 6, 6), sigma2=float(self.sigma2), sigma2_hat=float(self.sigma2_hat),
+                    weight_sum=float(self.weight_sum), trans_info=a(self.trans_info, 3), trans_dir=a(self.trans_dir, 3, 3),
+                    rot_info=a(self.rot_info, 3), rot_dir=a(self.rot_dir, 3, 3), n_corr=int(self.n_corr), flags=int(self.flags))
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
@@ -90,6 +106,10 @@ def load_library():
     lib.sf_fusion_closest_altitude.restype = C.c_float
     lib.sf_sfilter_pose_zscore.restype = C.c_float
     lib.sf_icp_set_robust_kernel.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    lib.sf_icp_set_covariance.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    lib.sf_icp_set_degeneracy_thresholds.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]
+    lib.sf_icp_fetch_covariance.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_icp_fetch_covariance_previous.argtypes = [C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -575,6 +595,28 @@ class Icp:
         rmse and n_corr stay unweighted.  P2PLANE does not freeze or take the tile search while a kind is set."""
         code = ROBUST_KINDS[kind]
         _check(self.lib.sf_icp_set_robust_kernel(self.h, code, float("nan") if k is None and code != 0 else float(k or 0.0)))
+
+    def set_covariance(self, on=True, sensor_sigma=0.0):
+        """Pose covariance and degeneracy of every alignment from now on (sf_icp_set_covariance, include/slamfusion.h): one more
+        evaluation of the mode's objective at the final pose, enqueued behind the last iteration.  sensor_sigma (metres) > 0
+        scales the covariance; 0 uses the residual variance the pairs themselves show.  Default off."""
+        _check(self.lib.sf_icp_set_covariance(self.h, int(bool(on)), float(sensor_sigma)))
+
+    def set_degeneracy_thresholds(self, trans=0.0, rot=0.0, inflate_trans_var=0.0, inflate_rot_var=0.0):
+        """Eigenvalues of the marginal translation / rotation information divided by the weight sum below these thresholds
+        flag the alignment (COV_FLAGS) and add inflate_* (m^2, rad^2) to cov along every flagged eigenvector.  0 = never."""
+        _check(self.lib.sf_icp_set_degeneracy_thresholds(self.h, float(trans), float(rot), float(inflate_trans_var), float(inflate_rot_var)))
+
+    def fetch_covariance(self, previous=False, batch=None):
+        """One dict per scan (6x6 numpy info / cov, sigma2, sigma2_hat, weight_sum, trans_info, trans_dir, rot_info, rot_dir,
+        n_corr, flags) of the alignment fetch_results last returned, or with previous=True of the one fetch_previous returns."""
+        if previous:
+            arr = (IcpCovariance * int(batch or getattr(self, "_prev_batch", None) or self.batch))()
+            _check(self.lib.sf_icp_fetch_covariance_previous(self.h, arr))
+        else:
+            arr = (IcpCovariance * int(batch or getattr(self, "_last_batch", None) or self.batch))()
+            _check(self.lib.sf_icp_fetch_covariance(self.h, arr))
+        return [c.as_dict() for c in arr]
 
     def set_wide_scan_points(self, points):
         """Scans above this many points take the launch list with two queries per lane and may freeze (sf_icp_set_wide_scan_points;
@@ -1242,6 +1284,11 @@ class Ekf:
     def update_pose(self, T, cov_pos, cov_rot):
         T, cp, cr = _f64(T).reshape(16), _f64(cov_pos).reshape(3), _f64(cov_rot).reshape(3)
         _check(self.lib.sf_ekf_update_pose(self.h, _p(T), _p(cp), _p(cr)))
+
+    def update_pose_cov(self, T, cov):
+        """Pose update with the ICP's 6x6 covariance (Icp.fetch_covariance()[i]["cov"], order (w, t), left perturbation)."""
+        T, cov = _f64(T).reshape(16), _f64(cov).reshape(36)
+        _check(self.lib.sf_ekf_update_pose_cov(self.h, _p(T), _p(cov)))
 
     def state(self):
         T, v, P = np.empty(16), np.empty(3), np.empty(81)

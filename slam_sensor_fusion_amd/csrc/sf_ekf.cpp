@@ -388,6 +388,47 @@ extern "C" int sf_ekf_update_pose(sf_ekf *e, const double T[16], const double co
     return update(e, y, H, Rm, 6);
 }
 
+// the pose update with the ICP's own 6x6 covariance over its left perturbation (w, t): measurement noise A cov A^T with
+// A = [[-[p_meas]x, I], [R_meas^T, 0]] (derivation: include/slamfusion.h)
+extern "C" int sf_ekf_update_pose_cov(sf_ekf *e, const double T[16], const double cov[36])
+{
+    if (!e || !T || !cov) return SF_ERR_INVALID;
+    for (int i = 0; i < 36; ++i)
+        if (!std::isfinite(cov[i])) return SF_ERR_INVALID;
+    double H[6 * NS] = {0}, y[6], Rm[36], Rmeas[9], Rt[9], dR[9], A[36] = {0}, AC[36];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Rmeas[3 * r + c] = T[4 * r + c];
+    transpose(e->R, Rt, 3, 3);
+    mul33(Rt, Rmeas, dR);
+    so3_log(dR, y + 3);
+    const double px = T[3], py = T[7], pz = T[11];
+    A[0 * 6 + 1] = pz; A[0 * 6 + 2] = -py; // -[p]x
+    A[1 * 6 + 0] = -pz; A[1 * 6 + 2] = px;
+    A[2 * 6 + 0] = py; A[2 * 6 + 1] = -px;
+    for (int i = 0; i < 3; ++i) {
+        A[6 * i + 3 + i] = 1.0;
+        for (int j = 0; j < 3; ++j) A[6 * (3 + i) + j] = Rmeas[3 * j + i]; // R_meas^T
+        y[i] = T[4 * i + 3] - e->p[i];
+        H[NS * i + i] = 1.0;
+        H[NS * (3 + i) + 6 + i] = 1.0;
+    }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double a = 0;
+            for (int k = 0; k < 6; ++k) a += A[6 * i + k] * cov[6 * k + j];
+            AC[6 * i + j] = a;
+        }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double a = 0;
+            for (int k = 0; k < 6; ++k) a += AC[6 * i + k] * A[6 * j + k];
+            Rm[6 * i + j] = a;
+        }
+    for (int i = 0; i < 6; ++i) // (exactly symmetric, whatever the rounding of the two products)
+        for (int j = i + 1; j < 6; ++j) Rm[6 * i + j] = Rm[6 * j + i] = 0.5 * (Rm[6 * i + j] + Rm[6 * j + i]);
+    return update(e, y, H, Rm, 6);
+}
+
 extern "C" int sf_ekf_get(const sf_ekf *e, double T[16], double v[3], double P[81])
 {
     if (!e) return SF_ERR_INVALID;

@@ -2767,6 +2767,8 @@ __global__ __launch_bounds__(BLK) void k_icp_fused_rob(SfGrid g, SfWindow w, con
 #include "sf_icp_fused_body.inc"
 }
 
+#include "sf_cov.hpp"
+
 } // namespace
 
 // ==================================================================== host side
@@ -2844,17 +2846,18 @@ struct sf_icp {
     // it is unchanged; sf_map stamps every build / normals pass with a process-unique generation, DevBuf counts its
     // reallocations (epoch).
     struct GraphKey {
-        int mode = -1, iters = -1, batch = -1, window = -1, ordered = -1, reuse = -1, robust_kind = -1;
+        int mode = -1, iters = -1, batch = -1, window = -1, ordered = -1, reuse = -1, robust_kind = -1, cov_on = -1;
         int64_t n = -1;
         const void *map = nullptr;
         uint64_t map_generation = 0, epochs = 0;
         float max_corr = 0, accept = 0, eps = 0;
         double robust_k = 0;
+        double cov_prm[5] = {0, 0, 0, 0, 0};
         bool operator==(const GraphKey &o) const
         {
             return mode == o.mode && iters == o.iters && batch == o.batch && window == o.window && ordered == o.ordered && reuse == o.reuse && n == o.n && map == o.map &&
                    map_generation == o.map_generation && epochs == o.epochs && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
-                   robust_kind == o.robust_kind && robust_k == o.robust_k;
+                   robust_kind == o.robust_kind && robust_k == o.robust_k && cov_on == o.cov_on && std::memcmp(cov_prm, o.cov_prm, sizeof(cov_prm)) == 0;
         }
     } graph_key;
     // Consecutive asynchronous alignments of the launch list overlap: an alignment's last launches (frozen pairs: fourteen 16 us
@@ -2865,7 +2868,7 @@ struct sf_icp {
     // enqueues next (a fetch, an upload, a map rebuild) is ordered behind it as before; only back-to-back alignments of unchanged
     // inputs run side by side.  Same kernels, same data, same results (tests/test_gpu_pipeline.py).
     struct Lane {
-        sf::DevBuf X, qcache, Xq, qkeys, qkeys2, qidx, qidx2, corr, state, d_inits, partials, fz_state, fz_part, fz_cnt, fz_ids, fz_all, qtkey, tseg, tile_stats;
+        sf::DevBuf X, qcache, Xq, qkeys, qkeys2, qidx, qidx2, corr, state, d_inits, partials, fz_state, fz_part, fz_cnt, fz_ids, fz_all, qtkey, tseg, tile_stats, cov_part, cov_out;
         hipGraphExec_t graph_exec = nullptr;
         GraphKey graph_key;
         std::vector<double> inits_uploaded;
@@ -2896,6 +2899,7 @@ struct sf_icp {
     // what the lane's last alignment was (sf_icp_fetch_previous reads the OTHER lane's states with the other lane's description)
     struct LaneMeta {
         bool valid = false;
+        bool cov = false; // it ran with the covariance switch on: cov_out of its lane holds its sf_icp_covariance entries
         int batch = 0, mode = 0;
         std::vector<double> inits;
     } meta, other_meta;
@@ -2937,6 +2941,11 @@ struct sf_icp {
     // robust kernel of P2PLANE (sf_icp_set_robust_kernel): read at enqueue, passed to the kernels by value
     int robust_kind = SF_ROBUST_NONE;
     double robust_k = 0.0;
+    // pose covariance (sf_cov.hpp): read at enqueue, passed to the kernels by value; the rows and the result live per lane
+    int cov_on = 0;
+    CovArg cov_arg{0.0, 0.0, 0.0, 0.0, 0.0};
+    sf::DevBuf cov_part, cov_out;
+    bool prev_cov_ok = false; // sf_icp_fetch_covariance_previous has something to read (set with prev_ok, cleared by its own fetch)
     // tile search (sf_tile.hpp): the searching launches of large batches
     int tile_mode = 0;              // sf_icp_set_tile_search: 0 off, 1 when the batch is large enough to gain (TILE_AUTO_MIN_QUERIES), 2 whenever possible
     bool tile_on = false;           // this alignment's queries are sorted by tile and its searching launches run k_tile_search
@@ -3363,9 +3372,11 @@ sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
     k.map = (const void *)icp->map;
     k.map_generation = icp->map->generation;
     k.robust_kind = robust_on(icp, mode) ? icp->robust_kind : SF_ROBUST_NONE; k.robust_k = robust_on(icp, mode) ? icp->robust_k : 0.0; // (passed by value to the robust kernels)
+    k.cov_on = icp->cov_on;
+    if (icp->cov_on) { const double cp[5] = {icp->cov_arg.sensor_sigma, icp->cov_arg.thr_t, icp->cov_arg.thr_r, icp->cov_arg.infl_t, icp->cov_arg.infl_r}; std::memcpy(k.cov_prm, cp, sizeof(cp)); }
     k.max_corr = icp->prm.max_corr; k.accept = icp->prm.accept; k.eps = icp->prm.eps + icp->fz_prm.guard_scale * 1.0e-3f + icp->fz_prm.guard_min + icp->fz_prm.guard_max + (float)icp->fz_prm.max_tries; // (the freeze parameters travel by value too)
     const sf::DevBuf *bufs[] = {&icp->X0, &icp->X0r, &icp->X, &icp->Xq, &icp->qcache, &icp->corr, &icp->state, &icp->partials, &icp->d_box, &icp->d_boxes, &icp->n_dev,
-                                &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &icp->fz_state, &icp->fz_part, &icp->fz_cnt, &icp->fz_ids, &icp->fz_all, &icp->tseg, &icp->tile_stats};
+                                &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &icp->fz_state, &icp->fz_part, &icp->fz_cnt, &icp->fz_ids, &icp->fz_all, &icp->tseg, &icp->tile_stats, &icp->cov_part, &icp->cov_out};
     k.epochs = (uint64_t)icp->plane;
     for (const sf::DevBuf *b : bufs) k.epochs = (k.epochs * 1000003ull + b->epoch) * 1000003ull + (uint64_t)(uintptr_t)b->p; // (the address too: the two source sets take turns under one lane's graph)
     return k;
@@ -3558,6 +3569,45 @@ int launch_state_init(sf_icp *icp)
     return SF_OK;
 }
 
+#define COV_DECLINE_MSG "the pose covariance (sf_icp_set_covariance) serves unsharded alignments enqueued whole: switch it off for sharded / stepping alignments"
+// Pose covariance of the alignment just enqueued (sf_cov.hpp): one search of every query at the final pose and the per-scan
+// solve, behind the last iteration on the same stream.  in_list: part of the launch list (REF_CPP reads the map crop and a
+// single scan's count from device memory there, as its own kernels do -- a captured graph bakes neither in).
+int cov_alloc(sf_icp *icp)
+{
+    const size_t B = (size_t)std::max(icp->batch, 1);
+    SF_TRY(icp->cov_part.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(icp->nblocks, 1) * B));
+    SF_TRY(icp->cov_out.reserve(sizeof(sf_icp_covariance) * B));
+    return SF_OK;
+}
+
+template <int MODE>
+void launch_cov(sf_icp *icp, bool in_list)
+{
+    sf_map *m = icp->map;
+    hipStream_t s = icp->ctx->stream;
+    const int nb = icp->nblocks, B = icp->batch;
+    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)B), blk(BLK);
+    const bool win = m->window.kind != 0;
+    const float thr = MODE == 0 ? icp->prm.max_corr : o3d_thr(icp); // REF_CPP: the squared-vs-unsquared quirk, icp_point_to_point.cpp:70
+    const SfWindow *wdev = (MODE == 0 && win && in_list) ? m->d_window.as<SfWindow>() : nullptr;
+    const int *nl = (MODE == 0 && B == 1) ? icp->n_dev.as<int>() : nullptr;
+    const RobustArg rk = robust_on(icp, MODE) ? robust_arg(icp) : RobustArg{SF_ROBUST_NONE, 0.0};
+    double *part = icp->cov_part.as<double>();
+    if (win)
+        hipLaunchKernelGGL((k_nn_cov<MODE, true>), grid, blk, 0, s, m->grid, m->window, wdev, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, nl, icp->state.as<IcpState>(), thr, part, nb, rk);
+    else
+        hipLaunchKernelGGL((k_nn_cov<MODE, false>), grid, blk, 0, s, m->grid, m->window, wdev, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, nl, icp->state.as<IcpState>(), thr, part, nb, rk);
+    hipLaunchKernelGGL(k_cov_solve<MODE>, dim3((unsigned)B), dim3(COV_SBLK), 0, s, part, nb, icp->cov_arg, icp->cov_out.as<sf_icp_covariance>());
+}
+
+void enqueue_cov(sf_icp *icp, int mode, bool in_list)
+{
+    if (mode == SF_ICP_REF_CPP) launch_cov<0>(icp, in_list);
+    else if (mode == SF_ICP_O3D_P2P) launch_cov<1>(icp, in_list);
+    else launch_cov<2>(icp, in_list);
+}
+
 // enqueue the whole alignment (no host synchronisation)
 int enqueue_align(sf_icp *icp, int mode)
 {
@@ -3626,6 +3676,7 @@ int enqueue_align(sf_icp *icp, int mode)
             if (i + 1 < K) red(1, 0);
         }
     }
+    if (icp->cov_on) enqueue_cov(icp, mode, true);
     SF_HIP(hipGetLastError());
     return SF_OK;
 }
@@ -4235,6 +4286,7 @@ void lane_flip(sf_icp *icp)
     raw_swap(icp->qidx, o.qidx); raw_swap(icp->qidx2, o.qidx2); raw_swap(icp->corr, o.corr); raw_swap(icp->state, o.state); raw_swap(icp->d_inits, o.d_inits);
     raw_swap(icp->partials, o.partials); raw_swap(icp->fz_state, o.fz_state); raw_swap(icp->fz_part, o.fz_part); raw_swap(icp->fz_cnt, o.fz_cnt);
     raw_swap(icp->fz_ids, o.fz_ids); raw_swap(icp->fz_all, o.fz_all); raw_swap(icp->qtkey, o.qtkey); raw_swap(icp->tseg, o.tseg); raw_swap(icp->tile_stats, o.tile_stats);
+    raw_swap(icp->cov_part, o.cov_part); raw_swap(icp->cov_out, o.cov_out);
     std::swap(icp->graph_exec, o.graph_exec);
     std::swap(icp->graph_key, o.graph_key);
     std::swap(icp->inits_uploaded, o.inits_uploaded);
@@ -4340,15 +4392,23 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     if (!lanes.piped) SF_TRY(lane_reserve(icp)); // (a source written ahead of an alignment in flight left the output buffers alone: icp_alloc)
     icp->unfetched = true;
     icp->prev_ok = lanes.piped && beside && icp->other_meta.valid; // (not piped: this alignment runs in the buffers of the one before it)
+    icp->prev_cov_ok = icp->prev_ok && icp->other_meta.cov;
     icp->meta.valid = true;
+    icp->meta.cov = icp->cov_on != 0;
     icp->meta.batch = icp->batch;
     icp->meta.mode = mode;
     icp->meta.inits = icp->inits;
     hipStream_t s = icp->ctx->stream;
+    if (icp->cov_on) SF_TRY(cov_alloc(icp)); // (before any capture, and before the graph key is formed)
     SF_TRY(launch_state_init(icp));
     if (icp->last_fused) { // everything resident at once: the whole alignment is one launch (window and count by value)
         SF_TRY(order_queries(icp, mode));
-        return launch_fused(icp, mode);
+        SF_TRY(launch_fused(icp, mode));
+        if (icp->cov_on) { // a follow-up launch: the single-launch kernels leave the final state in device memory too
+            enqueue_cov(icp, mode, false);
+            SF_HIP(hipGetLastError());
+        }
+        return SF_OK;
     }
     if (mode == SF_ICP_REF_CPP && icp->map->window.kind != 0) { // the map crop as it stands now, for the kernels that read it from the device
         SF_TRY(icp->map->d_window.reserve(sizeof(SfWindow)));
@@ -4436,6 +4496,57 @@ extern "C" int sf_icp_fetch_previous(sf_icp *icp, sf_icp_result *out)
     SF_HIP(hipStreamSynchronize(icp->lane_stream[ol]));
     for (int b = 0; b < M.batch; ++b) fill_result(icp, M.mode, icp->h_prev[(size_t)b], &M.inits[(size_t)b * 16], out + b);
     icp->prev_ok = false;
+    return SF_OK;
+}
+
+// ------------------------------------------------------------------ pose covariance (sf_cov.hpp)
+extern "C" int sf_icp_set_covariance(sf_icp *icp, int on, double sensor_sigma)
+{
+    SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
+    SF_CHECK(std::isfinite(sensor_sigma) && sensor_sigma >= 0.0, SF_ERR_INVALID, "sensor_sigma must be finite and >= 0 (0: the estimated residual variance)");
+    icp->cov_on = on != 0;
+    icp->cov_arg.sensor_sigma = sensor_sigma;
+    return SF_OK;
+}
+
+extern "C" int sf_icp_set_degeneracy_thresholds(sf_icp *icp, double trans, double rot, double inflate_trans_var, double inflate_rot_var)
+{
+    SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
+    const double v[4] = {trans, rot, inflate_trans_var, inflate_rot_var};
+    for (double x : v) SF_CHECK(std::isfinite(x) && x >= 0.0, SF_ERR_INVALID, "thresholds and inflations must be finite and >= 0");
+    icp->cov_arg.thr_t = trans; icp->cov_arg.thr_r = rot;
+    icp->cov_arg.infl_t = inflate_trans_var; icp->cov_arg.infl_r = inflate_rot_var;
+    return SF_OK;
+}
+
+extern "C" int sf_icp_fetch_covariance(sf_icp *icp, sf_icp_covariance *out)
+{
+    SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(icp->meta.valid && icp->meta.batch > 0 && !icp->shard, SF_ERR_STATE, "no alignment to fetch a covariance of");
+    SF_CHECK(icp->meta.cov, SF_ERR_STATE, "the latest alignment ran with the covariance switch off (sf_icp_set_covariance)");
+    SF_CHECK(!icp->unfetched, SF_ERR_STATE, "fetch the alignment's results first (sf_icp_fetch_results)");
+    SF_CHECK(icp->cov_out.p, SF_ERR_STATE, "no covariance has been computed");
+    SF_HIP(hipSetDevice(icp->ctx->device));
+    hipStream_t s = icp->ctx->stream; // (ordered behind the alignment, whichever lane it took)
+    SF_HIP(hipMemcpyAsync(out, icp->cov_out.p, sizeof(sf_icp_covariance) * (size_t)icp->meta.batch, hipMemcpyDeviceToHost, s));
+    SF_HIP(hipStreamSynchronize(s));
+    return SF_OK;
+}
+
+// twin of sf_icp_fetch_previous: the other lane's buffers, the other lane's stream, the latest alignment goes on running
+extern "C" int sf_icp_fetch_covariance_previous(sf_icp *icp, sf_icp_covariance *out)
+{
+    SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(icp->other_meta.valid && icp->other_meta.batch > 0 && (icp->prev_ok || icp->prev_cov_ok), SF_ERR_STATE,
+             "no earlier alignment to fetch a covariance of: the latest alignment did not run beside the one before it, or it was fetched already");
+    SF_CHECK(icp->other_meta.cov && icp->prev_cov_ok, SF_ERR_STATE, "the earlier alignment ran with the covariance switch off, or its covariance was fetched already");
+    const int ol = icp->lane ^ 1;
+    SF_CHECK(icp->lane_used[ol] && icp->lane_done[ol] && icp->lane_stream[ol] && icp->other.cov_out.p, SF_ERR_STATE, "the other lane holds no covariance");
+    SF_HIP(hipSetDevice(icp->ctx->device));
+    SF_HIP(hipEventSynchronize(icp->lane_done[ol]));
+    SF_HIP(hipMemcpyAsync(out, icp->other.cov_out.p, sizeof(sf_icp_covariance) * (size_t)icp->other_meta.batch, hipMemcpyDeviceToHost, icp->lane_stream[ol]));
+    SF_HIP(hipStreamSynchronize(icp->lane_stream[ol]));
+    icp->prev_cov_ok = false;
     return SF_OK;
 }
 
@@ -4551,6 +4662,7 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     SF_TRY(check_ready(icp, mode));
     SF_CHECK(mode != SF_ICP_REF_CPP, SF_ERR_INVALID, "stepping supports O3D_P2P and P2PLANE");
     SF_CHECK(first >= 0 && first <= 2, SF_ERR_INVALID, "first must be 0, 1 or 2");
+    SF_CHECK(!icp->cov_on, SF_ERR_STATE, COV_DECLINE_MSG);
     SF_CHECK(first != 2 || icp->shard, SF_ERR_STATE, "resume (first = 2) is a sharded-path operation");
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
@@ -4705,6 +4817,7 @@ extern "C" int sf_icp_align_sharded_async(sf_icp *icp, int mode, sf_comm *comm, 
     SF_CHECK(comm && sf::comm_ctx(comm) == icp->ctx, SF_ERR_INVALID, "the communicator must live on the icp's context (same stream)");
     SF_CHECK(icp->shard, SF_ERR_STATE, "sf_icp_set_shard first");
     SF_CHECK(first == 1 || first == 2, SF_ERR_INVALID, "first must be 1 (start) or 2 (resume)");
+    SF_CHECK(!icp->cov_on, SF_ERR_STATE, COV_DECLINE_MSG);
     const int steps = sharded_steps(icp, mode);
     int rc = SF_OK;
     for (int k = 0; k < steps && rc == SF_OK; ++k) {
@@ -4767,6 +4880,7 @@ extern "C" int sf_icp_align_group(sf_icp **members, int n, int mode, sf_icp_resu
     for (int m = 0; m < n; ++m) {
         SF_TRY(check_ready(members[m], mode));
         SF_CHECK(members[m]->shard, SF_ERR_STATE, "member %d: sf_icp_set_shard first", m);
+        SF_CHECK(!members[m]->cov_on, SF_ERR_STATE, COV_DECLINE_MSG);
         SF_CHECK(members[m]->ctx == members[0]->ctx && members[m]->batch == members[0]->batch && members[m]->n == members[0]->n &&
                      members[m]->prm.num_iters == members[0]->prm.num_iters,
                  SF_ERR_INVALID, "member %d does not match member 0 (context, batch, points per scan, iterations)", m);

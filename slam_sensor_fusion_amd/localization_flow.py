@@ -229,6 +229,18 @@ class _LazyLast(dict):
         return v
 
 
+def pose_cov_floor(T, pos_var, rot_var):
+    """diag(pos_var x3, rot_var x3) of the filter's (dp, dtheta) expressed in the ICP's (w, t) left-perturbation order:
+    A^-1 D A^-T with A = [[-[p]x, I], [R^T, 0]] of sf_ekf_update_pose_cov, A^-1 = [[0, R], [I, [p]x R]]."""
+    R, p = T[:3, :3], T[:3, 3]
+    px = np.array([[0.0, -p[2], p[1]], [p[2], 0.0, -p[0]], [-p[1], p[0], 0.0]])
+    Ainv = np.zeros((6, 6))
+    Ainv[:3, 3:] = R
+    Ainv[3:, :3] = np.eye(3)
+    Ainv[3:, 3:] = px @ R
+    return Ainv @ np.diag([pos_var] * 3 + [rot_var] * 3) @ Ainv.T
+
+
 class EkfLocalizationFlow(LocalizationFlow):
     """The same per-scan orchestration with the pose prior from the error-state EKF (extension f-4, sf_ekf_*)
     instead of blend + StochasticFilter: odometry-delta prediction, GPS position and compass yaw updates before
@@ -239,11 +251,33 @@ class EkfLocalizationFlow(LocalizationFlow):
     compass_var_ = np.radians(2.0) ** 2
     start_sigma_m_ = 0.05
     start_sigma_rad_ = np.radians(0.5)
+    # icp_covariance="estimated": the alignment reports its own 6x6 covariance and degeneracy (sf_icp_set_covariance) and the
+    # filter takes it (sf_ekf_update_pose_cov) with the constants above added as a floor in the filter's own (dp, dtheta)
+    # coordinates -- a perfect synthetic fit does not make the filter overconfident, and on a well-constrained scan only the
+    # shape of the noise changes, never to a smaller variance.  A direction whose normalised marginal information
+    # (eigenvalue / weight sum) is below the threshold is flagged and its variance inflated, which is what keeps a tunnel's
+    # axis out of the filter: the Hessian alone claims millimetres there (include/slamfusion.h).  The translation threshold is
+    # sized for P2PLANE, whose smallest normalised eigenvalue lies in [0, 1/3] (measured: open city block 0.09, tunnel 0.01);
+    # the point-to-point objectives pin every pair in all three directions and never flag a translation.
+    icp_covariance_ = "fixed"
+    cov_trans_threshold_ = 0.03
+    cov_rot_threshold_ = 1.0           # m^2 (rotation information per pair: squared lever arms)
+    cov_inflate_trans_var_ = 1.0 ** 2
+    cov_inflate_rot_var_ = np.radians(10.0) ** 2
 
-    def __init__(self, *args, **kw):
+    def __init__(self, *args, icp_covariance=None, **kw):
         super().__init__(*args, **kw)
         self.ekf_ = api.Ekf()
         self.ekf_started_ = False
+        self.set_icp_covariance(self.icp_covariance_ if icp_covariance is None else icp_covariance)
+
+    def set_icp_covariance(self, how):
+        if how not in ("fixed", "estimated"):
+            raise ValueError("icp_covariance must be 'fixed' or 'estimated'")
+        self.icp_covariance_ = how
+        if how == "estimated":
+            self.icp_.set_degeneracy_thresholds(self.cov_trans_threshold_, self.cov_rot_threshold_, self.cov_inflate_trans_var_, self.cov_inflate_rot_var_)
+        self.icp_.set_covariance(how == "estimated")
 
     def pose_prior(self, gps, odom, odom_T_sensor_current):
         if not self.ekf_started_:
@@ -265,8 +299,14 @@ class EkfLocalizationFlow(LocalizationFlow):
         return prior.astype(np.float32)
 
     def after_alignment(self, result, scan):
-        self.ekf_.update_pose(np.asarray(result["T"], dtype=np.float64), [self.icp_pos_var_] * 3, [self.icp_rot_var_] * 3)
+        T = np.asarray(result["T"], dtype=np.float64)
+        cov = self.icp_.fetch_covariance()[0] if self.icp_covariance_ == "estimated" else None
+        if cov is not None and not cov["flags"] & api.COV_FLAGS["few_corr"]:
+            self.ekf_.update_pose_cov(T, cov["cov"] + pose_cov_floor(T, self.icp_pos_var_, self.icp_rot_var_))
+        else:
+            self.ekf_.update_pose(T, [self.icp_pos_var_] * 3, [self.icp_rot_var_] * 3)
         self.map_T_sensor_ = self.ekf_.state()[0].astype(np.float32)
+        self.last_covariance = cov
 
 
 class ImuEkfMappingFlow(EkfLocalizationFlow):
@@ -301,8 +341,8 @@ class ImuEkfMappingFlow(EkfLocalizationFlow):
     gyro_bias_walk_, accel_bias_walk_ = 1e-5, 1e-4
     start_velocity_var_ = 1.0
 
-    def __init__(self, ctx, map_points, map_T_global, altitude_table=None, grow_every=None, voxel_flavour="pcl"):
-        super().__init__(ctx, map_points, map_T_global, altitude_table)
+    def __init__(self, ctx, map_points, map_T_global, altitude_table=None, grow_every=None, voxel_flavour="pcl", icp_covariance=None):
+        super().__init__(ctx, map_points, map_T_global, altitude_table, icp_covariance=icp_covariance)
         if grow_every is not None:
             self.grow_every_ = int(grow_every)
         self.icp_.set_num_iterations(self.mapping_icp_iterations_)

@@ -216,3 +216,20 @@ def make_cars(boxes, centers, n_cars, radius=(4.0, 15.0), seed=CITY_SEED + 3):
         if all(clear(b) for b in boxes) and all(clear(b) for b in out):
             out.append(car)
     return np.array(out).reshape(-1, 6)
+
+
+TUNNEL_SENSOR_XYZ, TUNNEL_SENSOR_RPY_DEG = (1.0, -0.5, 1.8), (0.4, -0.3, 5.0)
+
+
+def make_tunnel(length_m=200.0, half_width_m=4.0, wall_m=2.0, height_m=30.0, m_points=1_500_000, keep_x=60.0, sigma=0.005, seed=CITY_SEED + 1):
+    """A straight tunnel along x: two walls at y = +-half_width (boxes in make_city's layout) plus the ground, whose ends lie
+    beyond a scan's range, so that nothing constrains the pose along x -- the degenerate case of scan-to-map registration.
+    Returns (boxes[2, 6], map points): sample_city's points on those surfaces, kept where |y| < half_width + 0.5 (the
+    inner wall faces and the floor between them) and |x| < keep_x.  TUNNEL_SENSOR_* is the pose the figures of DESIGN.md
+    section 11 were measured at (raycast_scan(boxes, T, rings=16, azimuths=360, max_range=40))."""
+    h = 0.5 * length_m
+    boxes = np.array([[-h, half_width_m, 0.0, h, half_width_m + wall_m, height_m],
+                      [-h, -half_width_m - wall_m, 0.0, h, -half_width_m, height_m]])
+    pts = sample_city(boxes, length_m, m_points, sigma=sigma, seed=seed)
+    keep = (np.abs(pts[:, 1]) < half_width_m + 0.5) & (np.abs(pts[:, 0]) < keep_x)
+    return boxes, pts[keep]

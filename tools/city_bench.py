@@ -15,7 +15,11 @@ scans are ray cast in but not to the map (parked cars, dynamic objects); --robus
 (sf_icp_set_robust_kernel, e.g. tukey:0.1) to every case.  The pose errors against the ray-casting truth (median / p95 /
 max, translation and rotation) are reported for the plain run and, under "robust", for the robust one; a robust kernel
 keeps P2PLANE from freezing, so its fair throughput baseline is scans_per_s_no_freeze.
-   python tools/city_bench.py [--map-points 10000000] [--batch 64] [--rings 64 128] [--prior 0.06:0.3 0.3:1.5] [--dynamic-boxes 40] [--robust tukey:0.1]"""
+--covariance adds a run with the pose covariance on (sf_icp_set_covariance, degeneracy thresholds 0.03 / 1.0 m^2): per scan the
+smallest normalised eigenvalue of the marginal translation / rotation information and the flags, and scans/s with the switch
+off and on (same object, same settings).  --tunnel replaces the city by synth.make_tunnel (walls along x, ends out of range,
+40 m rays): the degenerate scene, where the translation flag is expected on every scan.
+   python tools/city_bench.py [--map-points 10000000] [--batch 64] [--rings 64 128] [--prior 0.06:0.3 0.3:1.5] [--dynamic-boxes 40] [--robust tukey:0.1] [--covariance [--tunnel]]"""
 import argparse
 import json
 import os
@@ -57,11 +61,16 @@ def main():
     ap.add_argument("--wide-from", type=int, default=0, help="sf_icp_set_wide_scan_points (0: the library's own rule -- above 131 072 points, or above 65 536 in a batch no single launch could take)")
     ap.add_argument("--dynamic-boxes", type=int, default=0, help="car-sized boxes in the ray-cast world that the map does not hold")
     ap.add_argument("--robust", default=None, help="KIND:K -- also register under this robust kernel (huber, cauchy, tukey, gm; K in metres)")
+    ap.add_argument("--covariance", action="store_true", help="also register with sf_icp_set_covariance on: eigenvalues, flags, scans/s off vs on")
+    ap.add_argument("--tunnel", action="store_true", help="the degenerate scene (synth.make_tunnel) instead of the city")
     args = ap.parse_args()
     mode = "p2plane"
     ctx = api.Context(0)
-    boxes = synth.make_city(args.extent, int(120 * (args.extent / 240.0) ** 2))
-    raw = synth.sample_city(boxes, args.extent, args.map_points)
+    if args.tunnel:
+        boxes, raw = synth.make_tunnel(m_points=args.map_points)
+    else:
+        boxes = synth.make_city(args.extent, int(120 * (args.extent / 240.0) ** 2))
+        raw = synth.sample_city(boxes, args.extent, args.map_points)
     cloud = api.Cloud(ctx, raw)
     del raw
     cloud.voxel_downsample(0.1, "pcl")
@@ -76,8 +85,12 @@ def main():
         truths, scans = [], []
         while len(scans) < args.batch:
             xy = rng.uniform(-12.0, 12.0, 2)
-            T = synth.make_T((xy[0], xy[1], 1.8), (0.0, 0.0, rng.uniform(0, 360)))
-            s = synth.raycast_scan(world, T, rings=rings, seed=synth.CITY_SEED + 10 + len(scans))
+            if args.tunnel: # along the axis, between the walls, heading within 10 degrees of it either way
+                T = synth.make_T((xy[0], xy[1] / 6.0, 1.8), (0.0, 0.0, rng.uniform(-10, 10) + 180.0 * rng.integers(2)))
+                s = synth.raycast_scan(world, T, rings=rings, max_range=40.0, seed=synth.CITY_SEED + 10 + len(scans))
+            else:
+                T = synth.make_T((xy[0], xy[1], 1.8), (0.0, 0.0, rng.uniform(0, 360)))
+                s = synth.raycast_scan(world, T, rings=rings, seed=synth.CITY_SEED + 10 + len(scans))
             if len(s) < 0.45 * rings * 2032:
                 continue
             truths.append(T)
@@ -125,9 +138,20 @@ def main():
                 rob["scans_per_s"] = timed(icp, ctx, mode, args.steps, args.batch)
                 out["robust"] = dict(kernel=args.robust, **rob)
                 icp.set_robust_kernel("none")
+            if args.covariance:
+                out["scans_per_s_covariance_off"] = timed(icp, ctx, mode, args.steps, args.batch)
+                icp.set_degeneracy_thresholds(0.03, 1.0)
+                icp.set_covariance(True)
+                icp.align_batch(mode)
+                covs = icp.fetch_covariance()
+                out["scans_per_s_covariance_on"] = timed(icp, ctx, mode, args.steps, args.batch)
+                out["covariance"] = dict(min_trans_info=[round(float(c["trans_info"][0]), 5) for c in covs], min_rot_info_m2=[round(float(c["rot_info"][0]), 3) for c in covs],
+                                         flags=[int(c["flags"]) for c in covs], sigma_hat_m=[round(float(np.sqrt(c["sigma2_hat"])), 4) for c in covs],
+                                         weakest_trans_dir_of_scan_0=[round(float(v), 4) for v in covs[0]["trans_dir"][0]])
+                icp.set_covariance(False)
             icp.close()
-            print(json.dumps(dict(workload="ring scans (%d x 2032 rays) vs a %.0f m synthetic city, %d samples -> %d map points (voxel 0.1 m), %d scans in flight x %d points, "
-                                           "%d %s iterations, prior error %.2f m / %.1f deg (1 sigma per axis)" % (rings, args.extent, args.map_points, n_map, args.batch, n, args.iters,
+            print(json.dumps(dict(workload="ring scans (%d x 2032 rays) vs a %.0f m synthetic %s, %d samples -> %d map points (voxel 0.1 m), %d scans in flight x %d points, "
+                                           "%d %s iterations, prior error %.2f m / %.1f deg (1 sigma per axis)" % (rings, args.extent, "tunnel" if args.tunnel else "city", args.map_points, n_map, args.batch, n, args.iters,
                                                                                                                   mode, sig_t, sig_r),
                                   rings=rings, dynamic_boxes=len(cars), prior_sigma_m=sig_t, prior_sigma_deg=sig_r, points_per_scan=int(n), cell_m=cell, grid=list(dims), **out)), flush=True)
 
