@@ -369,6 +369,16 @@ int sf_icp_set_freeze_params(sf_icp *icp, float guard_scale, float guard_min, fl
 /* of the last batched alignment, summed over its scans: {freeze launches that held, thaws (moved beyond the guard),
  * freeze launches that did not hold, active queries of the last freeze launch, scans frozen at the end} */
 int sf_icp_freeze_stats(sf_icp *icp, int64_t out[5]);
+/* Deferred search (frozen-pairs schedule only, unsharded): in the last verifying launch before the first chance to freeze
+ * (from_launch >= 5) a wave in which up to 8 queries fail their certificate lists them instead of searching in place, and a
+ * dense pass behind the launch searches the listed queries 64 per wave.  Same pairs; their terms enter the sums at another
+ * place (the schedule's results agree with the switch off to summation rounding, as frozen pairs on / off do).  on: 0 / 1
+ * (default 1), an A/B switch like sf_icp_set_freeze. */
+int sf_icp_set_defer_search(sf_icp *icp, int on);
+/* of the last batched alignment: {queries that went to the dense pass, waves with more failing queries than the cap, which
+ * searched in place} -- zeros when the schedule did not run or the switch is off.  Whether it ran is recorded when the
+ * alignment is enqueued: a later sf_icp_fetch_results that re-learns the freeze schedule does not change the answer. */
+int sf_icp_defer_stats(sf_icp *icp, int64_t out[2]);
 /* Robust M-estimator kernel of SF_ICP_P2PLANE (REF_CPP and O3D_P2P ignore it, as Open3D's point-to-point estimator takes no
  * kernel).  With r = (y - p) . n the float64 point-to-plane residual of a pair (y the transformed source point, p / n the
  * neighbour and its normal) and the scale k > 0 in metres, every pair enters the normal equations with the weight w(r):

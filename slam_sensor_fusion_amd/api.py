@@ -649,6 +649,17 @@ class Icp:
         _check(self.lib.sf_icp_freeze_stats(self.h, a))
         return {"froze": a[0], "thawed": a[1], "failed": a[2], "active_queries": a[3], "frozen_at_end": a[4]}
 
+    def set_defer_search(self, on=True):
+        """Deferred search of the frozen-pairs schedule (sf_icp_set_defer_search, default on): the stragglers of the last verifying
+        launch before the first chance to freeze go to a dense pass instead of being searched in place."""
+        _check(self.lib.sf_icp_set_defer_search(self.h, C.c_int(int(bool(on)))))
+
+    def defer_stats(self):
+        """Of the last batched alignment (sf_icp_defer_stats): queries that went to the dense pass, waves that hit the cap."""
+        a = (C.c_int64 * 2)()
+        _check(self.lib.sf_icp_defer_stats(self.h, a))
+        return {"deferred_queries": a[0], "capped_waves": a[1]}
+
     def set_query_order(self, order="auto"):
         """'auto' | 'as_given' | 'cell' (SF_ORDER_*): the order a scan's points are walked in."""
         _check(self.lib.sf_icp_set_query_order(self.h, C.c_int({"auto": 0, "as_given": 1, "cell": 2}[order])))

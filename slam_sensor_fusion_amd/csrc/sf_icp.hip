@@ -1905,6 +1905,211 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_fz_few(SfGrid g, S
     }
 }
 
+// ------------------------------------------------------------------ deferred search (the last verifying launch before the freeze)
+// In the launch before the first chance to freeze ~0.4 % of the queries still fail their certificate, but a wave that holds
+// ONE of them drops what it loaded and walks the search's chain of dependent round trips with one or two lanes busy: 42 % of
+// the waves.  Here such a wave lists its failing queries instead (up to DF_WCAP; a segment of its own per wave, filled in
+// (u, lane) order by ballot + prefix -- no atomic appends: the list order is a summation order), gives them a zero
+// contribution and goes on with the pairs it has loaded; k_nn_deferred then searches the listed queries densely, 64 per wave,
+// and writes their records to FZ_FEW rows of their own per scan, which the reduce adds after the ordinary rows.  Same pairs,
+// another place in the sum -- frozen-pairs schedule only, which sums in an order of its own anyway.  A wave with more than
+// DF_WCAP failing queries searches in place as k_nn_red does (count 255: "capped").
+
+#ifndef SF_DF_WCAP
+#define SF_DF_WCAP 8
+#endif
+constexpr int DF_WCAP = SF_DF_WCAP; // measured: 4, 8 and 16 (profiles/LADDER.md round 6)
+constexpr int DF_CAPPED = 255;
+static_assert((BLK / 64) * DF_WCAP <= FZ_CAP && DF_WCAP < DF_CAPPED, "a row defers fewer queries than it could list as active");
+struct DeferBufs {
+    uint8_t *cnt;   // [scan][row][wave]: queries the wave deferred, DF_CAPPED: it searched in place
+    uint16_t *ids;  // [scan][row][wave][DF_WCAP]: their places in the row (u * BLK + thread)
+    double *part;   // [scan][FZ_FEW][REC_STRIDE]: the records of the deferred queries
+    uint32_t *stat; // {deferred queries, capped waves} of the alignment
+};
+
+// k_nn_red<2, false, false, Q> from VERIFY_FROM_SEARCH on, with the deferral above.  The count and the list are written BEFORE
+// the branch that searches: with anything of the bookkeeping live across the search the kernel took 121 VGPRs (4 waves per
+// SIMD) instead of the 92 (5) of the kernel it replaces.
+template <int Q>
+__global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_df(SfGrid g, SfWindow w, const float *__restrict__ X0x, const float *__restrict__ X0y, const float *__restrict__ X0z,
+                                                                 int n, const IcpState *__restrict__ st, float thr, double *__restrict__ partials, int nblocks,
+                                                                 float4 *__restrict__ qcache, int64_t cache_n, uint32_t *__restrict__ stats, DeferBufs df)
+{
+    constexpr int MODE = 2;
+    constexpr int NREC = NREC_PLANE;
+    const int L = blockIdx.y * gridDim.x + blockIdx.x; // placement as k_nn_red
+    const int kk = L >> 3;
+    const int b = kk % (int)gridDim.y;
+    const int bx = (L & 7) * ((int)gridDim.x >> 3) + kk / (int)gridDim.y;
+    if (bx >= nblocks) return;
+    const IcpState *S = st + b;
+    if (S->done) return;
+    __shared__ sf::WaveNN nn_ws[BLK / 64];
+    __shared__ double stage[BLK / 64][32];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t seg = ((size_t)b * nblocks + bx) * (BLK / 64) + wv;
+    LanePair P[Q];
+    bool need[Q];
+#pragma unroll
+    for (int u = 0; u < Q; ++u) need[u] = false;
+    const bool attempted = qcache != nullptr && S->cache_live != 0 && S->n_research >= VERIFY_FROM_SEARCH;
+    bool fast = false;   // the wave goes on with the pairs of the all-at-once attempt
+    uint32_t listed = 0; // what the wave leaves in df.cnt
+    if (attempted) {
+        const float m_now = (float)S->motion;
+#pragma unroll
+        for (int u = 0; u < Q; ++u) {
+            const int slot = bx * (BLK * Q) + u * BLK + (int)threadIdx.x;
+            const QueryIn q = query_in<MODE, false>(X0x, X0y, X0z, n, b, S, 0.0f, 0.0f, nullptr, qcache, cache_n, true, slot, n);
+            sf::NNHit hit, seed;
+            float4 tn;
+            need[u] = reuse_certificate(q.valid, q.qx, q.qy, q.qz, thr, m_now, q.e, q.c1, q.c2, hit, tn, seed);
+            P[u] = make_pair(q, hit, tn); // (a failing query: no pair, a zero contribution)
+        }
+        uint32_t failing = 0;
+#pragma unroll
+        for (int u = 0; u < Q; ++u) failing += (uint32_t)__popcll(__ballot(need[u]));
+        fast = failing <= (uint32_t)DF_WCAP;
+        listed = fast ? failing : (uint32_t)DF_CAPPED;
+    }
+    if (lane == 0) df.cnt[seg] = (uint8_t)listed;
+    if (fast && listed != 0u) {
+        uint32_t before = 0;
+#pragma unroll
+        for (int u = 0; u < Q; ++u) {
+            const unsigned long long bal = __ballot(need[u]);
+            const uint32_t rank = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+            if (need[u]) df.ids[seg * DF_WCAP + before + rank] = (uint16_t)(u * BLK + (int)threadIdx.x); // before + rank < listed <= DF_WCAP
+            before += (uint32_t)__popcll(bal);
+        }
+    }
+    if (!fast) {
+        asm volatile("" ::: "memory"); // nothing loaded above stays live across the searches below
+#pragma unroll
+        for (int u = 0; u < Q; ++u) {
+            const int slot = bx * (BLK * Q) + u * BLK + (int)threadIdx.x;
+            P[u] = nn_pair<MODE, false, false>(g, w, X0x, X0y, X0z, n, b, S, thr, 0.0f, 0.0f, nullptr, qcache, cache_n, slot, n, &nn_ws[wv], stats);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        double v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = 0.0;
+#pragma unroll
+        for (int u = 0; u < Q; ++u) {
+            const PairTerms t = pair_terms<MODE>(P[u]);
+            add_half<MODE>(t, h, v);
+        }
+        const double t0 = wave_reduce_16(v);
+        if ((lane & 3) == 0) stage[wv][16 * h + (lane >> 2)] = t0;
+    }
+    __syncthreads();
+    if (threadIdx.x < NREC) {
+        const int c = threadIdx.x;
+        double *dst = partials + ((size_t)b * nblocks + bx) * REC_STRIDE;
+        dst[c] = ((stage[0][c] + stage[1][c]) + stage[2][c]) + stage[3][c];
+    }
+}
+
+// The dense pass behind k_nn_red_df, grid (FZ_FEW, batch): workgroup r of scan b gathers the lists of the rows = r (mod FZ_FEW)
+// in row, wave and list order (a prefix sum over the segments, BLK segments at a time), then its waves take 64 listed
+// queries each, side by side, through nn_pair (certificate fails -> seeded search -> cache entry written, as always); the
+// waves' records are added in wave order, the rounds in round order, into row r of the scan's deferred rows.  (A small grid:
+// two waves per SIMD are asked for, so that the search inside two loops needs no scratch.)
+template <int Q>
+__global__ __launch_bounds__(BLK, 2) void k_nn_deferred(SfGrid g, SfWindow w, const float *__restrict__ X0x, const float *__restrict__ X0y, const float *__restrict__ X0z,
+                                                                   int n, const IcpState *__restrict__ st, float thr, int nblocks, float4 *__restrict__ qcache, int64_t cache_n,
+                                                                   uint32_t *__restrict__ stats, DeferBufs df)
+{
+    constexpr int MODE = 2;
+    constexpr int NW = BLK / 64;
+    const int r = (int)blockIdx.x, b = (int)blockIdx.y;
+    const IcpState *S = st + b;
+    if (S->done) return;
+    __shared__ sf::WaveNN nn_ws[NW];
+    __shared__ double fstage[NW][32];
+    __shared__ uint32_t list[BLK * DF_WCAP];
+    __shared__ uint32_t wsum[NW];
+    __shared__ uint32_t capped;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (threadIdx.x == 0) capped = 0u;
+    __syncthreads();
+    const int my_rows = r < nblocks ? (nblocks - r + FZ_FEW - 1) / FZ_FEW : 0;
+    const int nseg = my_rows * NW;
+    double acc = 0.0; // thread c < NREC: column c of the workgroup's record
+    uint32_t n_listed = 0;
+    for (int s0 = 0; s0 < nseg; s0 += BLK) {
+        const int sg = s0 + (int)threadIdx.x;
+        const int bx = r + (sg / NW) * FZ_FEW;
+        const size_t seg = ((size_t)b * nblocks + bx) * NW + (sg % NW);
+        uint32_t c = sg < nseg ? (uint32_t)df.cnt[seg] : 0u;
+        if (c > (uint32_t)DF_WCAP) { // (a capped wave: counted, nothing listed)
+            atomicAdd(&capped, 1u);
+            c = 0u;
+        }
+        uint32_t incl = c; // inclusive prefix over the wave, then over the waves
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t t = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += t;
+        }
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        uint32_t base = 0, total = 0;
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) {
+            if (ww < wv) base += wsum[ww];
+            total += wsum[ww];
+        }
+        const uint32_t start = base + incl - c;
+        for (uint32_t i = 0; i < c; ++i) list[start + i] = (uint32_t)bx * (uint32_t)(BLK * Q) + (uint32_t)df.ids[seg * DF_WCAP + i]; // start + c <= BLK * DF_WCAP
+        __syncthreads();
+        n_listed += total;
+        for (uint32_t q0 = 0; q0 < total; q0 += BLK) {
+            const uint32_t i = q0 + (uint32_t)threadIdx.x;
+            if (q0 + (uint32_t)(wv * 64) < total) { // (whole waves; dealing a round out in equal shares to the four waves measured the same, 172 against 173 us)
+                const int slot = i < total ? (int)list[i] : n; // n: no query
+                const LanePair A1 = nn_pair<MODE, false, false>(g, w, X0x, X0y, X0z, n, b, S, thr, 0.0f, 0.0f, nullptr, qcache, cache_n, slot, n, &nn_ws[wv], stats);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    double v[16];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) v[k] = 0.0;
+                    const PairTerms t = pair_terms<MODE>(A1);
+                    add_half<MODE>(t, h, v);
+                    const double t0 = wave_reduce_16(v);
+                    if ((lane & 3) == 0) fstage[wv][16 * h + (lane >> 2)] = t0;
+                }
+            } else if (lane < 32) {
+                fstage[wv][lane] = 0.0;
+            }
+            __syncthreads();
+            if (threadIdx.x < 32) acc += ((fstage[0][threadIdx.x] + fstage[1][threadIdx.x]) + fstage[2][threadIdx.x]) + fstage[3][threadIdx.x];
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x < REC_STRIDE) df.part[((size_t)b * FZ_FEW + r) * REC_STRIDE + threadIdx.x] = threadIdx.x < NREC_PLANE ? acc : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) { // (integers: order independent)
+        if (n_listed) atomicAdd(&df.stat[0], n_listed);
+        if (capped) atomicAdd(&df.stat[1], capped);
+    }
+}
+
+// the records of a scan's deferred queries (k_nn_deferred) added to rec[] behind everything else, row by row
+__device__ __forceinline__ void add_deferred_rows(const double *__restrict__ df_part, int b, double *rec)
+{
+    if (threadIdx.x < NREC_PLANE) {
+        double v = 0.0;
+#pragma unroll
+        for (int r = 0; r < FZ_FEW; ++r) v += df_part[((size_t)b * FZ_FEW + r) * REC_STRIDE + threadIdx.x];
+        rec[threadIdx.x] += v;
+    }
+    __syncthreads();
+}
+
 // fixed-order column sums of a slab with rows of STRIDE doubles, NCOL columns (NCOL <= 128), by NT threads (a multiple of
 // 128): thread (slice s of NT / 128, column c of 128) adds rows s, s + NT / 128, ...; the slices are then added in order
 // (NS = 8 slices whatever NT: a workgroup of fewer than 1024 threads takes several slices per thread, one after the other --
@@ -2027,6 +2232,7 @@ struct FreezeBufs {
     const uint32_t *act_cnt;  // [scan][row]
     const uint16_t *act_ids;  // [scan][row][FZ_CAP]
     uint32_t *act_all;        // [scan][rows x FZ_CAP]: the scan's list
+    const double *df_part;    // [scan][FZ_FEW][REC_STRIDE]: the records of this launch's deferred queries (k_nn_deferred); nullptr: none
 };
 
 // The reduce half of a launch that may freeze, by the scan's workgroup of RBLK threads: the record of the scan's pairs at
@@ -2153,6 +2359,7 @@ __global__ __launch_bounds__(RBLK) void k_reduce_solve_fz(IcpState *__restrict__
     FreezeState *F = fb.fz + b;
     __shared__ double rec[REC_STRIDE];
     freeze_fold<RBLK>(S, F, b, partials, nblocks, nblocks, fb, rec);
+    if (fb.df_part) add_deferred_rows(fb.df_part, b, rec);
     if (threadIdx.x == 0) {
         for (int c = 0; c < NREC_PLANE; ++c) S->rec[c] = rec[c];
         double To[12];
@@ -2166,9 +2373,10 @@ __global__ __launch_bounds__(RBLK) void k_reduce_solve_fz(IcpState *__restrict__
     }
 }
 
-__global__ void k_fz_init(FreezeState *__restrict__ fz, int batch)
+__global__ void k_fz_init(FreezeState *__restrict__ fz, int batch, uint32_t *__restrict__ df_stat)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b == 0) df_stat[0] = df_stat[1] = 0u;
     if (b >= batch) return;
     FreezeState *F = fz + b;
     F->mode = 0; F->tries = 0; F->froze = 0; F->thawed = 0; F->n_active = 0; F->guard = 0.0f; F->launch_mode = 0; F->motion0 = 0.0;
@@ -2194,6 +2402,7 @@ __global__ __launch_bounds__(SBLK) void k_reduce_only(IcpState *__restrict__ st,
     const int rows = own_off ? (int)((own_off[b + 1] - own_off[b] + BLK * qpl - 1) / (BLK * qpl)) : nblocks; // sharded: workgroups beyond the owned queries wrote nothing
     if (MODE == 2 && fb.fz) freeze_fold<SBLK>(st + b, fb.fz + b, b, partials, nblocks, rows, fb, rec);
     else reduce_partials<NREC, SBLK>(partials + (size_t)b * nblocks * REC_STRIDE, rows, rec);
+    if (MODE == 2 && fb.df_part) add_deferred_rows(fb.df_part, b, rec);
     if (threadIdx.x < REC_STRIDE) xchg[(size_t)b * REC_STRIDE + threadIdx.x] = rec[threadIdx.x];
 }
 
@@ -2868,7 +3077,7 @@ struct sf_icp {
     // enqueues next (a fetch, an upload, a map rebuild) is ordered behind it as before; only back-to-back alignments of unchanged
     // inputs run side by side.  Same kernels, same data, same results (tests/test_gpu_pipeline.py).
     struct Lane {
-        sf::DevBuf X, qcache, Xq, qkeys, qkeys2, qidx, qidx2, corr, state, d_inits, partials, fz_state, fz_part, fz_cnt, fz_ids, fz_all, qtkey, tseg, tile_stats, cov_part, cov_out;
+        sf::DevBuf X, qcache, Xq, qkeys, qkeys2, qidx, qidx2, corr, state, d_inits, partials, fz_state, fz_part, fz_cnt, fz_ids, fz_all, df_cnt, df_ids, df_part, df_stat, qtkey, tseg, tile_stats, cov_part, cov_out;
         hipGraphExec_t graph_exec = nullptr;
         GraphKey graph_key;
         std::vector<double> inits_uploaded;
@@ -2936,6 +3145,9 @@ struct sf_icp {
     int fz_fetches = 0;             // fetched alignments since fz_from was last reset to its default (every FZ_PROBE_EVERY-th starts over)
     int fz_step = 0;                // stepping paths: launches since the pass began
     sf::DevBuf fz_state, fz_part, fz_cnt, fz_ids, fz_all;
+    int defer = 1;                  // sf_icp_set_defer_search: the verifying launches of the frozen-pairs schedule list their stragglers for a dense pass (k_nn_red_df)
+    sf::DevBuf df_cnt, df_ids, df_part, df_stat;
+    bool df_planned = false;        // the last alignment's launch list held a deferring launch (fz_from as it stood THEN: a fetch may re-learn it)
     int64_t nn_stats_used = 0;
     static constexpr int64_t NN_STATS_CAP = 1024;
     // robust kernel of P2PLANE (sf_icp_set_robust_kernel): read at enqueue, passed to the kernels by value
@@ -3367,7 +3579,7 @@ void prof_collect(sf_icp *icp)
 sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
 {
     sf_icp::GraphKey k;
-    k.mode = mode; k.iters = icp->prm.num_iters; k.batch = icp->batch; k.window = icp->map->window.kind; k.ordered = (int)icp->ordered | ((int)icp->tile_on << 1); k.reuse = (int)icp->reuse | (icp->freeze << 1) | (icp->fz_from << 3);
+    k.mode = mode; k.iters = icp->prm.num_iters; k.batch = icp->batch; k.window = icp->map->window.kind; k.ordered = (int)icp->ordered | ((int)icp->tile_on << 1); k.reuse = (int)icp->reuse | (icp->freeze << 1) | (icp->fz_from << 3) | (icp->defer << 16);
     k.n = (mode == SF_ICP_REF_CPP && icp->batch == 1) ? -icp->n_cap : icp->n; // REF_CPP, one scan: any count of the same capacity replays
     k.map = (const void *)icp->map;
     k.map_generation = icp->map->generation;
@@ -3376,7 +3588,7 @@ sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
     if (icp->cov_on) { const double cp[5] = {icp->cov_arg.sensor_sigma, icp->cov_arg.thr_t, icp->cov_arg.thr_r, icp->cov_arg.infl_t, icp->cov_arg.infl_r}; std::memcpy(k.cov_prm, cp, sizeof(cp)); }
     k.max_corr = icp->prm.max_corr; k.accept = icp->prm.accept; k.eps = icp->prm.eps + icp->fz_prm.guard_scale * 1.0e-3f + icp->fz_prm.guard_min + icp->fz_prm.guard_max + (float)icp->fz_prm.max_tries; // (the freeze parameters travel by value too)
     const sf::DevBuf *bufs[] = {&icp->X0, &icp->X0r, &icp->X, &icp->Xq, &icp->qcache, &icp->corr, &icp->state, &icp->partials, &icp->d_box, &icp->d_boxes, &icp->n_dev,
-                                &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &icp->fz_state, &icp->fz_part, &icp->fz_cnt, &icp->fz_ids, &icp->fz_all, &icp->tseg, &icp->tile_stats, &icp->cov_part, &icp->cov_out};
+                                &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &icp->fz_state, &icp->fz_part, &icp->fz_cnt, &icp->fz_ids, &icp->fz_all, &icp->df_cnt, &icp->df_ids, &icp->df_part, &icp->df_stat, &icp->tseg, &icp->tile_stats, &icp->cov_part, &icp->cov_out};
     k.epochs = (uint64_t)icp->plane;
     for (const sf::DevBuf *b : bufs) k.epochs = (k.epochs * 1000003ull + b->epoch) * 1000003ull + (uint64_t)(uintptr_t)b->p; // (the address too: the two source sets take turns under one lane's graph)
     return k;
@@ -3475,10 +3687,14 @@ int freeze_alloc(sf_icp *icp)
     SF_TRY(icp->fz_cnt.reserve(sizeof(uint32_t) * rows));
     SF_TRY(icp->fz_ids.reserve(sizeof(uint16_t) * FZ_CAP * rows));
     SF_TRY(icp->fz_all.reserve(sizeof(uint32_t) * FZ_CAP * rows));
+    SF_TRY(icp->df_cnt.reserve(sizeof(uint8_t) * (BLK / 64) * rows));
+    SF_TRY(icp->df_ids.reserve(sizeof(uint16_t) * (BLK / 64) * DF_WCAP * rows));
+    SF_TRY(icp->df_part.reserve(sizeof(double) * REC_STRIDE * FZ_FEW * (size_t)icp->batch));
+    SF_TRY(icp->df_stat.reserve(sizeof(uint32_t) * 2));
     return SF_OK;
 }
 
-FreezeBufs freeze_bufs(sf_icp *icp, bool on)
+FreezeBufs freeze_bufs(sf_icp *icp, bool on, bool deferred = false)
 {
     FreezeBufs fb;
     fb.fz = on ? icp->fz_state.as<FreezeState>() : nullptr;
@@ -3486,7 +3702,50 @@ FreezeBufs freeze_bufs(sf_icp *icp, bool on)
     fb.act_cnt = icp->fz_cnt.as<uint32_t>();
     fb.act_ids = icp->fz_ids.as<uint16_t>();
     fb.act_all = icp->fz_all.as<uint32_t>();
+    fb.df_part = deferred ? icp->df_part.as<double>() : nullptr;
     return fb;
+}
+
+DeferBufs defer_bufs(sf_icp *icp)
+{
+    DeferBufs d;
+    d.cnt = icp->df_cnt.as<uint8_t>();
+    d.ids = icp->df_ids.as<uint16_t>();
+    d.part = icp->df_part.as<double>();
+    d.stat = icp->df_stat.as<uint32_t>();
+    return d;
+}
+
+// Deferred search (k_nn_red_df): launch index k of the frozen-pairs schedule hands its stragglers to the dense pass -- the
+// last launch through k_nn_red before the first chance to freeze, when it runs two queries per lane and every wave first
+// tries to verify.  The freeze launch and the launches after it search in place (the freeze launch has next to nothing left
+// to search: the pass behind it measured as a loss, profiles/LADDER.md round 6), as do the sharded paths.
+bool defer_now(const sf_icp *icp, int mode, int k)
+{
+    return freeze_on(icp, mode) && icp->defer != 0 && !icp->shard && k >= VERIFY_FROM_SEARCH && k + 1 == icp->fz_from;
+}
+
+bool defer_planned(const sf_icp *icp, int mode) { return defer_now(icp, mode, icp->fz_from - 1); }
+
+void launch_nn_deferred(sf_icp *icp, uint32_t *stats)
+{
+    sf_map *m = icp->map;
+    hipLaunchKernelGGL((k_nn_deferred<SF_WIDE_QPL>), dim3((unsigned)FZ_FEW, (unsigned)icp->batch), dim3(BLK), 0, icp->ctx->stream, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2),
+                       (int)icp->n, icp->state.as<IcpState>(), o3d_thr(icp), icp->nblocks_nn, icp->qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
+}
+
+// launch_nn_red<2> of a wide scan's two-queries-per-lane launch with the deferral, and its dense pass: one profiled launch
+void launch_nn_red_df(sf_icp *icp)
+{
+    sf_map *m = icp->map;
+    const int nb = icp->nblocks_nn;
+    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)icp->batch), blk(BLK);
+    ProfScope ps(icp);
+    uint32_t *stats = nullptr;
+    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + 2 * NN_STATS_SHARDS * icp->nn_stats_used++;
+    hipLaunchKernelGGL((k_nn_red_df<SF_WIDE_QPL>), grid, blk, 0, icp->ctx->stream, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, icp->state.as<IcpState>(),
+                       o3d_thr(icp), icp->partials.as<double>(), nb, icp->qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
+    launch_nn_deferred(icp, stats);
 }
 
 // few: FZ_FEW workgroups per scan (k_nn_red_fz_few: the launches after the first chance to freeze)
@@ -3531,7 +3790,7 @@ int freeze_start_pass(sf_icp *icp, int mode)
     icp->fz_step = 0;
     if (!freeze_on(icp, mode)) return SF_OK;
     SF_TRY(freeze_alloc(icp));
-    hipLaunchKernelGGL(k_fz_init, dim3(nblk(icp->batch, 64)), dim3(64), 0, icp->ctx->stream, icp->fz_state.as<FreezeState>(), icp->batch);
+    hipLaunchKernelGGL(k_fz_init, dim3(nblk(icp->batch, 64)), dim3(64), 0, icp->ctx->stream, icp->fz_state.as<FreezeState>(), icp->batch, icp->df_stat.as<uint32_t>());
     return SF_OK;
 }
 
@@ -3627,18 +3886,20 @@ int enqueue_align(sf_icp *icp, int mode)
     } else if (mode == SF_ICP_P2PLANE) {
         const bool fz = freeze_on(icp, mode);
         if (fz) { // (buffers: freeze_alloc, before any capture)
-            hipLaunchKernelGGL(k_fz_init, dim3(nblk(B, 64)), dim3(64), 0, s, icp->fz_state.as<FreezeState>(), B);
+            hipLaunchKernelGGL(k_fz_init, dim3(nblk(B, 64)), dim3(64), 0, s, icp->fz_state.as<FreezeState>(), B, icp->df_stat.as<uint32_t>());
         }
         // wide scans: the first launches -- nearly every query searches -- run one query per lane (fewer registers: measured
         // 929, 804, 508, 414 against 954, 836, 539, 439 us); from the launch in which waves start to certify whole, two
         const bool wide = icp->qpl > 1 && !icp->shard;
         for (int k = 0; k < K; ++k) {
             const bool q1 = wide && k < VERIFY_FROM_SEARCH; // (the same schedule with the reuse off: it is part of the summation order, and reuse on == off bit for bit)
+            const bool df = !q1 && defer_now(icp, mode, k);
             if (fz && k >= icp->fz_from) launch_nn_red_fz(icp, false, k > icp->fz_from);
             else if (tile_launch(icp, k)) launch_tile_search<2>(icp, q1);
+            else if (df) launch_nn_red_df(icp);
             else launch_nn_red<2>(icp, false, q1);
             if (fz && k + 1 >= icp->fz_from) // (after a one-query-per-lane launch too: an ordinary record of twice as many rows, and the solve may ask for the freeze launch)
-                hipLaunchKernelGGL(k_reduce_solve_fz, dim3(B), dim3(RBLK), 0, s, st, part, q1 ? icp->nblocks : icp->nblocks_nn, n, K, icp->d_boxes.as<ScanBox>(), freeze_bufs(icp, true),
+                hipLaunchKernelGGL(k_reduce_solve_fz, dim3(B), dim3(RBLK), 0, s, st, part, q1 ? icp->nblocks : icp->nblocks_nn, n, K, icp->d_boxes.as<ScanBox>(), freeze_bufs(icp, true, df),
                                    icp->fz_prm, (int)(k + 2 < K));
             else if (q1)
                 hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, icp->nblocks, n, k, K, icp->d_boxes.as<ScanBox>());
@@ -4135,6 +4396,26 @@ extern "C" int sf_icp_tile_info(sf_icp *icp, int64_t out[12])
     return SF_OK;
 }
 
+extern "C" int sf_icp_set_defer_search(sf_icp *icp, int on)
+{
+    SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
+    icp->defer = on != 0;
+    return SF_OK;
+}
+
+extern "C" int sf_icp_defer_stats(sf_icp *icp, int64_t out[2])
+{
+    SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
+    out[0] = out[1] = 0;
+    if (!icp->df_planned || !icp->df_stat.p) return SF_OK; // (not freeze_on() as it is NOW: sf_icp_fetch_results may have moved fz_from since)
+    uint32_t h[2] = {0u, 0u};
+    SF_HIP(hipMemcpyAsync(h, icp->df_stat.p, sizeof(h), hipMemcpyDeviceToHost, icp->ctx->stream));
+    SF_HIP(hipStreamSynchronize(icp->ctx->stream));
+    out[0] = (int64_t)h[0]; // queries that went to the dense pass
+    out[1] = (int64_t)h[1]; // waves with more failing queries than DF_WCAP: searched in place
+    return SF_OK;
+}
+
 extern "C" int sf_icp_set_freeze(sf_icp *icp, int on)
 {
     SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
@@ -4285,7 +4566,8 @@ void lane_flip(sf_icp *icp)
     raw_swap(icp->X, o.X); raw_swap(icp->qcache, o.qcache); raw_swap(icp->Xq, o.Xq); raw_swap(icp->qkeys, o.qkeys); raw_swap(icp->qkeys2, o.qkeys2);
     raw_swap(icp->qidx, o.qidx); raw_swap(icp->qidx2, o.qidx2); raw_swap(icp->corr, o.corr); raw_swap(icp->state, o.state); raw_swap(icp->d_inits, o.d_inits);
     raw_swap(icp->partials, o.partials); raw_swap(icp->fz_state, o.fz_state); raw_swap(icp->fz_part, o.fz_part); raw_swap(icp->fz_cnt, o.fz_cnt);
-    raw_swap(icp->fz_ids, o.fz_ids); raw_swap(icp->fz_all, o.fz_all); raw_swap(icp->qtkey, o.qtkey); raw_swap(icp->tseg, o.tseg); raw_swap(icp->tile_stats, o.tile_stats);
+    raw_swap(icp->fz_ids, o.fz_ids); raw_swap(icp->fz_all, o.fz_all); raw_swap(icp->df_cnt, o.df_cnt); raw_swap(icp->df_ids, o.df_ids); raw_swap(icp->df_part, o.df_part);
+    raw_swap(icp->df_stat, o.df_stat); raw_swap(icp->qtkey, o.qtkey); raw_swap(icp->tseg, o.tseg); raw_swap(icp->tile_stats, o.tile_stats);
     raw_swap(icp->cov_part, o.cov_part); raw_swap(icp->cov_out, o.cov_out);
     std::swap(icp->graph_exec, o.graph_exec);
     std::swap(icp->graph_key, o.graph_key);
@@ -4384,6 +4666,7 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = fused_eligible(icp, mode);
+    icp->df_planned = !icp->last_fused && defer_planned(icp, mode);
     SF_TRY(order_lut_prepare(icp));
     // the launch list takes a lane (see sf_icp::Lane); the single launch, profiled runs and a count left on the device stay on the context's stream
     const bool beside = icp->unfetched; // an alignment of this object is still unfetched: this one may run beside it
@@ -4667,6 +4950,7 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = false;
+    if (first) icp->df_planned = defer_planned(icp, mode);
     if (first) SF_TRY(order_lut_prepare(icp));
     if (first == 1) SF_TRY(launch_state_init(icp));
     if (icp->shard) {
@@ -4688,11 +4972,13 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
         ProfScope ps(icp, SF_PROF_REDUCE);
         hipLaunchKernelGGL(k_reduce_only<1>, dim3(icp->batch), dim3(SBLK), 0, s, icp->state.as<IcpState>(), icp->partials.as<double>(), nb, x, off, icp->qpl, freeze_bufs(icp, false));
     } else {
+        const bool df = !q1 && defer_now(icp, mode, icp->fz_step);
         if (freeze_nn_now(icp, mode)) launch_nn_red_fz(icp, icp->shard, icp->fz_step > icp->fz_from);
+        else if (df) launch_nn_red_df(icp);
         else launch_nn_red<2>(icp, icp->shard, q1);
         ProfScope ps(icp, SF_PROF_REDUCE);
         hipLaunchKernelGGL(k_reduce_only<2>, dim3(icp->batch), dim3(SBLK), 0, s, icp->state.as<IcpState>(), icp->partials.as<double>(), nb, x, off, qpl_now,
-                           freeze_bufs(icp, freeze_nn_now(icp, mode)));
+                           freeze_bufs(icp, freeze_nn_now(icp, mode), df));
     }
     SF_HIP(hipGetLastError());
     return SF_OK;
