@@ -165,8 +165,8 @@ int sf_map_cell_size(sf_map *m, float *cell, int32_t dims[3]);
  * the cloud since: the entries that stay keep their order (one streaming pass), only the new centroids are sorted.
  * Takes the build itself whenever that does not hold (the merge took its full path, the cloud changed in between, the
  * smallest coordinate of the map moved, 64-bit cell ids); *patched (may be NULL) says which way it went: 1 = merged,
- * SF_PATCH_* (<= 0) = built, and why.  Normals and the window are dropped as sf_map_build drops them; re-attach the map
- * to its sf_icp (sf_icp_set_target). */
+ * SF_PATCH_* (<= 0) = built, and why.  Normals and the window are dropped as sf_map_build drops them (the normals stay with
+ * sf_map_set_normals_carry, below); re-attach the map to its sf_icp (sf_icp_set_target). */
 #define SF_PATCH_NO_MERGE        0   /* no usable record: the merge took its full path, the cloud changed since, another cloud's index */
 #define SF_PATCH_BOUND_REPLACED (-1) /* (not returned any more: a replaced bound costs one reduction over the cloud, then the patch goes on) */
 #define SF_PATCH_ORIGIN_MOVED   (-2) /* a new centroid lies below the grid origin: every cell changes */
@@ -200,6 +200,26 @@ int sf_map_estimate_normals(sf_map *m, float radius);
 int sf_map_estimate_normals_cov(sf_map *m, float radius, int with_covariance);
 int sf_map_download_covariances(sf_map *m, double *cov6, int64_t cap_points, int64_t *n); /* original point order */
 int sf_map_set_normals(sf_map *m, const float *normals, int64_t n); /* original point order */
+/* Normals (and covariances) carried over sf_map_patch.  Off (0, the default): sf_map_patch drops them as described there.  On: the
+ * map remembers the `radius` and `with_covariance` of its last sf_map_estimate_normals[_cov] (sf_map_set_normals and
+ * sf_map_build forget them), and after sf_map_patch it has normals -- and covariances, if it had them -- that equal
+ * sf_map_patch followed by sf_map_estimate_normals_cov(m, radius, with_covariance) bit for bit, on every path:
+ *  - where the index was merged (*patched = 1), the entries that stay take their normal, neighbour count and covariance along
+ *    in the patch's own pass, and only the new centroids and the points within `radius` of a position the merge added or
+ *    removed are estimated again, by the arithmetic of the full pass on the patched index (an untouched neighbourhood is
+ *    visited in the same order, so its float64 sums come out the same);
+ *  - where the build ran (SF_PATCH_* <= 0), the full estimate runs after it with the remembered arguments.
+ * Normals given through sf_map_set_normals are NOT carried (there is nothing to re-estimate the changed part with): the patch
+ * drops them, switch on or off.  The window is dropped either way, and the map is re-attached with sf_icp_set_target as before.
+ * The re-estimate is enqueued on the context's stream behind the patch; every call that reads the normals is ordered after it. */
+int sf_map_set_normals_carry(sf_map *m, int on);
+/* what the last sf_map_patch did with the normals:
+ * out[0]: 1 = carried over the patch, 0 = re-estimated in full (the patch took the build),
+ *         -1 = dropped (switch off, or nothing to carry: no normals, or normals from sf_map_set_normals)
+ * out[1]: changed positions (centroids added + old points removed; 0 unless carried)
+ * out[2]: points re-estimated (0 when dropped, all indexed points after a build)
+ * out[3]: map points */
+int sf_map_normals_carry_info(sf_map *m, int64_t out[4]);
 int sf_map_download_normals(sf_map *m, float *normals, int32_t *n_neighbors, int64_t cap, int64_t *n);
 /* raw exact 1-NN (a9 without the threshold): idx in ORIGINAL point order, d2 squared
  * float32 summed x,y,z like FLANN L2_Simple; idx = -1 if nothing within max_d2. */

@@ -430,6 +430,19 @@ class Map:
     def estimate_normals(self, radius, covariance=False):
         _check(self.lib.sf_map_estimate_normals_cov(self.h, C.c_float(radius), C.c_int(int(covariance))))
 
+    def set_normals_carry(self, on=True):
+        """sf_map_set_normals_carry: `patch` keeps the estimated normals (and covariances) -- carried with the entries that stay,
+        re-estimated where the merge changed a neighbourhood; bit-equal to patch + estimate_normals with the last arguments."""
+        _check(self.lib.sf_map_set_normals_carry(self.h, C.c_int(int(bool(on)))))
+        return self
+
+    def normals_carry_info(self):
+        """sf_map_normals_carry_info of the last `patch`: (how, changed positions, points re-estimated, map points); how = 1 carried,
+        0 re-estimated in full (the patch took the build), -1 dropped."""
+        out = (C.c_int64 * 4)()
+        _check(self.lib.sf_map_normals_carry_info(self.h, out))
+        return tuple(int(v) for v in out)
+
     def download_covariances(self):
         """[n, 6] float64: xx xy xz yy yz zz of each point's neighbourhood (original point order)."""
         n = len(self)

@@ -181,6 +181,15 @@ struct sf_map {
     uint64_t src_stamp = 0;   // sf_cloud::stamp of the cloud the index describes
     sf::DevBuf d_window; // the window in device memory (REF_CPP kernels read it there: a captured launch list survives a moving crop)
     sf::DevBuf cov6;   // optional: the 6 unique entries of each point's neighbourhood covariance (sorted order), sf_map_estimate_normals
+    // sf_map_set_normals_carry: sf_map_patch carries nrm4 / cov6 into second buffers (swapped like pts4_alt) and re-estimates
+    // the points whose neighbourhood the merge changed; carry_tmp holds the bitmap over the new sorted positions, its block
+    // counts and their prefix, carry_list the dirty positions in ascending order
+    sf::DevBuf nrm4_alt, cov6_alt, carry_tmp, carry_list;
+    bool normals_carry = false;
+    bool nrm_estimated = false; // the normals come from sf_map_estimate_normals_cov with the arguments below (not sf_map_set_normals)
+    float nrm_radius = 0;
+    bool nrm_with_cov = false;
+    int64_t carry_info[4] = {-1, 0, 0, 0}; // sf_map_normals_carry_info
     int64_t n = 0;
     bool built = false, has_normals = false, has_cov = false;
     uint64_t generation = 0; // process-unique stamp of the index contents (build / normals): captured hipGraphs key on it

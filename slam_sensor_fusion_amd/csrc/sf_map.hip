@@ -163,6 +163,7 @@ extern "C" void sf_map_destroy(sf_map *m)
     (void)e;
     m->pts4.release(); m->nrm4.release(); m->cov6.release(); m->d_window.release(); m->cell_start.release(); m->keys.release(); m->vals.release();
     m->keys2.release(); m->vals2.release(); m->pts4_alt.release(); m->patch_tmp.release();
+    m->nrm4_alt.release(); m->cov6_alt.release(); m->carry_tmp.release(); m->carry_list.release();
     sf_ctx *ctx = m->ctx;
     delete m;
     sf::ctx_release(ctx);
@@ -179,6 +180,7 @@ extern "C" int sf_map_build(sf_map *m, sf_cloud *cloud, float cell)
     const int64_t n = cloud->n;
     m->built = false;
     m->has_normals = false;
+    m->nrm_estimated = false; // (sf_map_patch remembers the estimate it carries before it comes here)
     m->n = 0;
     m->window.kind = 0;
     const float *xyz = cloud->xyz.as<float>();
@@ -377,11 +379,16 @@ __device__ __forceinline__ uint32_t patch_del_before(const uint32_t *__restrict_
     return c + (uint32_t)__popc(bitmap[blk * 8u + w] & ((1u << (p & 31u)) - 1u));
 }
 
-// one lane per OLD entry, in sorted order: where it goes, with its new id
+// one lane per OLD entry, in sorted order: where it goes, with its new id.  CARRY (sf_map_set_normals_carry): 1 = its normal
+// goes with it, 2 = its normal and the 6 doubles of its covariance (16 B / 64 B more per point, streaming like the point
+// itself); 0 compiles to the pass without them
+template <int CARRY>
 __global__ __launch_bounds__(256) void k_patch_old(PatchGeom geo, const float4 *__restrict__ pts, int64_t n_old, const uint32_t *__restrict__ bitmap, const uint32_t *__restrict__ blk_pre,
                                                     const uint64_t *__restrict__ packed, const uint32_t *__restrict__ range, const uint32_t *__restrict__ coarse,
                                                     const uint32_t *__restrict__ fresh_rank,
-                                                    float4 *__restrict__ pts_out, uint32_t *__restrict__ keys_out, PatchFlags *__restrict__ ext)
+                                                    float4 *__restrict__ pts_out, uint32_t *__restrict__ keys_out, PatchFlags *__restrict__ ext,
+                                                    const float4 *__restrict__ nrm, float4 *__restrict__ nrm_out, const double2 *__restrict__ cov, double2 *__restrict__ cov_out,
+                                                    int64_t n_out)
 {
     __shared__ uint32_t words[8], wpre[8];
     const int64_t p0 = (int64_t)blockIdx.x * 256, p = p0 + threadIdx.x;
@@ -413,8 +420,19 @@ __global__ __launch_bounds__(256) void k_patch_old(PatchGeom geo, const float4 *
     const uint32_t del = wpre[w] + (uint32_t)__popc(words[w] & ((1u << bit) - 1u));
     const size_t o = (size_t)p - (size_t)del + (size_t)lo;
     const uint32_t id = j + f;
+    // o is this entry's rank in the merged sequence, hence below n_out, unless k_patch_groups gave up on a voxel (ext->moved)
+    // and left the bitmap short: that pass's output is abandoned.  The carrying passes write nothing then; the plain pass is
+    // kept instruction for instruction as it was (all its outputs are reserved alike, with the allocator's slack)
+    if (CARRY >= 1 && o >= (size_t)n_out) return;
     pts_out[o] = make_float4(a.x, a.y, a.z, __uint_as_float(id));
     keys_out[o] = key;
+    if (CARRY >= 1) {
+        nrm_out[o] = nrm[p];
+        if (CARRY == 2) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) cov_out[3 * o + d] = cov[3 * (size_t)p + d];
+        }
+    }
 }
 
 // one lane per centroid, in (cell, id) order: the old entries in front of it, less the replaced ones, plus its own rank
@@ -440,6 +458,10 @@ __global__ __launch_bounds__(256) void k_patch_new(PatchGeom geo, const float4 *
     keys_out[o] = key;
 }
 
+// the normals after a patch (defined with the normals kernels below): which points the merge left with another neighbourhood,
+// and those re-estimated on the patched index
+int carry_reestimate(sf_map *m, const sf_cloud::MergeRecord &rec, const int old_dim[3], float radius, bool with_cov, int64_t *n_dirty);
+
 } // namespace
 
 extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
@@ -456,9 +478,20 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     const SfGrid old = m->grid;
     const uint64_t old_cells = (uint64_t)old.dim[0] * (uint64_t)old.dim[1] * (uint64_t)old.dim[2];
     const int64_t n_old = rec.n_old, ng = rec.n_groups, n_out = cloud->n;
+    // the estimate to carry (sf_map_set_normals_carry): normals that sf_map_estimate_normals_cov wrote, with its arguments
+    const bool carry = m->normals_carry && m->has_normals && m->nrm_estimated;
+    const float carry_radius = m->nrm_radius;
+    const bool carry_cov = carry && m->has_cov && m->nrm_with_cov;
+    m->carry_info[0] = -1; m->carry_info[1] = m->carry_info[2] = 0; m->carry_info[3] = m->n;
     auto rebuild = [&](int why) -> int { // *patched: 0 / negative = the build ran, and why
         if (patched) *patched = why;
-        return sf_map_build(m, cloud, cell);
+        SF_TRY(sf_map_build(m, cloud, cell));
+        m->carry_info[3] = m->n;
+        if (!carry) return SF_OK;
+        SF_TRY(sf_map_estimate_normals_cov(m, carry_radius, carry_cov ? 1 : 0)); // nothing of the old estimate survives a build: in full, as remembered
+        m->carry_info[0] = 0;
+        m->carry_info[2] = m->grid.n;
+        return SF_OK;
     };
     if (!rec.valid || rec.epoch != ctx->merge_epoch || rec.stamp_after != cloud->stamp || rec.stamp_before != m->src_stamp || n_old != m->n || old.n != m->n || ng <= 0 ||
         n_out != n_old + rec.n_fresh)
@@ -520,6 +553,8 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     PatchFlags *h_ext = reinterpret_cast<PatchFlags *>(static_cast<unsigned char *>(ctx->h_pinned) + 256);
     SF_TRY(m->pts4_alt.reserve(sizeof(float4) * (size_t)n_out));
     SF_TRY(m->keys.reserve(sizeof(uint32_t) * (size_t)n_out));
+    if (carry) SF_TRY(m->nrm4_alt.reserve(sizeof(float4) * (size_t)n_out));
+    if (carry_cov) SF_TRY(m->cov6_alt.reserve(sizeof(double) * 6 * (size_t)n_out));
     SF_HIP(hipMemsetAsync(bitmap, 0, off_range - off_bitmap, st)); // bitmap, block counts, their prefix
     SF_HIP(hipMemsetAsync(d_ext, 0, sizeof(PatchFlags), st));
     hipLaunchKernelGGL(k_patch_groups, dim3(nblk(ng)), dim3(256), 0, st, pg, rec.g_rank, rec.g_fresh, rec.g_centroid, rec.g_old, ng, old.pts, n_old, ins_key, ins_val, bitmap, blk_cnt,
@@ -535,7 +570,15 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     // 4. the merge
     float4 *pts_out = m->pts4_alt.as<float4>();
     uint32_t *keys_out = m->keys.as<uint32_t>();
-    hipLaunchKernelGGL(k_patch_old, dim3(nblk(n_old)), dim3(256), 0, st, pg, old.pts, n_old, bitmap, blk_pre, packed, range, rec.coarse, rec.fresh_rank, pts_out, keys_out, d_ext);
+    if (carry_cov)
+        hipLaunchKernelGGL(k_patch_old<2>, dim3(nblk(n_old)), dim3(256), 0, st, pg, old.pts, n_old, bitmap, blk_pre, packed, range, rec.coarse, rec.fresh_rank, pts_out, keys_out, d_ext,
+                           old.nrm, m->nrm4_alt.as<float4>(), m->cov6.as<double2>(), m->cov6_alt.as<double2>(), n_out);
+    else if (carry)
+        hipLaunchKernelGGL(k_patch_old<1>, dim3(nblk(n_old)), dim3(256), 0, st, pg, old.pts, n_old, bitmap, blk_pre, packed, range, rec.coarse, rec.fresh_rank, pts_out, keys_out, d_ext,
+                           old.nrm, m->nrm4_alt.as<float4>(), nullptr, nullptr, n_out);
+    else
+        hipLaunchKernelGGL(k_patch_old<0>, dim3(nblk(n_old)), dim3(256), 0, st, pg, old.pts, n_old, bitmap, blk_pre, packed, range, rec.coarse, rec.fresh_rank, pts_out, keys_out, d_ext,
+                           nullptr, nullptr, nullptr, nullptr, n_out);
     hipLaunchKernelGGL(k_patch_new, dim3(nblk(ng)), dim3(256), 0, st, pg, old.pts, n_old, bitmap, blk_pre, skey, sval, ng, rec.g_rank, rec.fresh_pos, rec.g_centroid, pts_out, keys_out);
     SF_HIP(hipMemcpyAsync(h_ext, d_ext, sizeof(PatchFlags), hipMemcpyDeviceToHost, st));
 
@@ -551,6 +594,7 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     m->n = n_out;
     m->built = true;
     m->has_normals = false;
+    m->nrm_estimated = false;
     m->window.kind = 0;
     SfGrid &G = m->grid;
     for (int d = 0; d < 3; ++d) G.dim[d] = g.dim[d];
@@ -563,6 +607,24 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     m->generation = sf::next_generation();
     for (int d = 0; d < 3; ++d) { m->src_mn[d] = new_mn[d]; m->src_mx[d] = new_mx[d]; }
     m->src_stamp = cloud->stamp;
+    m->carry_info[3] = m->n;
+    if (carry) {
+        // the entries that stayed brought their normals along (k_patch_old); the slots of the centroids and of every point
+        // within the radius of a position that was added or removed are estimated on the patched index
+        m->nrm4.swap(m->nrm4_alt);
+        if (carry_cov) m->cov6.swap(m->cov6_alt);
+        G.nrm = m->nrm4.as<float4>();
+        int64_t n_dirty = 0;
+        SF_TRY(carry_reestimate(m, rec, pg.old_dim, carry_radius, carry_cov, &n_dirty));
+        m->has_normals = true;
+        m->has_cov = carry_cov;
+        m->nrm_estimated = true;
+        m->nrm_radius = carry_radius;
+        m->nrm_with_cov = carry_cov;
+        m->carry_info[0] = 1;
+        m->carry_info[1] = 2 * ng - rec.n_fresh; // every centroid, and the old point of every voxel that had one
+        m->carry_info[2] = n_dirty;
+    }
     if (patched) *patched = 1;
     return SF_OK;
 }
@@ -742,10 +804,11 @@ __device__ void smallest_eigvec(const double C[9], double nrm[3])
     nrm[0] = x; nrm[1] = y; nrm[2] = z;
 }
 
-__global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, int R, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+// the estimate of sorted position j: cells z-major, then y, then one contiguous x-run per row, ascending id inside a cell.  The
+// order of these float64 sums is what makes a carried estimate (sf_map_patch) the bits of a full one: k_normals and
+// k_normals_list both come here
+__device__ __forceinline__ void normals_point(const SfGrid &g, double r2, int R, int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
 {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= g.n) return;
     const float4 p = g.pts[j];
     const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
     const int cx = (int)fminf(fmaxf(floorf((p.x - g.org[0]) * g.inv_h), 0.0f), (float)(nx - 1));
@@ -789,6 +852,120 @@ __global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, int R, flo
     }
 }
 
+__global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, int R, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= g.n) return;
+    normals_point(g, r2, R, j, nrm4, cov6);
+}
+
+// ---- the estimate carried over sf_map_patch: only where a neighbourhood changed
+// One lane per changed position -- t < n_groups: the centroid of voxel t (added), beyond: the old point of voxel t - n_groups
+// where it had one (removed).  Every point of the patched index that has it within the radius gets its bit: the cells within
+// R of the position's cell, k_normals' own predicate (symmetric in the two points, so "it is my neighbour" and "I am within
+// its radius" agree exactly).  A removed point is looked up in the cell the OLD grid had it in (its clamp to the old upper
+// face is the one its neighbours' walks saw).  Exact rather than whole cells: the re-estimate costs two walks of 27 cells per
+// marked point, the mark one; a sphere holds a sixth of the points of the cube of cells around it.
+__global__ __launch_bounds__(256) void k_normals_mark(SfGrid g, int odx, int ody, int odz, double r2, int R, const uint32_t *__restrict__ g_fresh, const float *__restrict__ g_centroid,
+                                                       const float *__restrict__ g_old, int64_t n_groups, uint32_t *__restrict__ bitmap)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * n_groups) return;
+    const bool removed = t >= n_groups;
+    const int64_t v = removed ? t - n_groups : t;
+    if (removed && g_fresh[v]) return;
+    const float *src = removed ? g_old : g_centroid;
+    const float px = src[3 * v], py = src[3 * v + 1], pz = src[3 * v + 2];
+    const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
+    const int cx = (int)fminf(fmaxf(floorf((px - g.org[0]) * g.inv_h), 0.0f), (float)((removed ? odx : nx) - 1));
+    const int cy = (int)fminf(fmaxf(floorf((py - g.org[1]) * g.inv_h), 0.0f), (float)((removed ? ody : ny) - 1));
+    const int cz = (int)fminf(fmaxf(floorf((pz - g.org[2]) * g.inv_h), 0.0f), (float)((removed ? odz : nz) - 1));
+    const int x0 = max(cx - R, 0), x1 = min(cx + R, nx - 1);
+    const int y0 = max(cy - R, 0), y1 = min(cy + R, ny - 1);
+    const int z0 = max(cz - R, 0), z1 = min(cz + R, nz - 1);
+    if (x0 > x1) return; // (a removed point beyond a grid that shrank; only x is tested: the x-run reads cell_start before its own loop test, empty y / z ranges never enter theirs)
+    for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y) {
+            const size_t row = ((size_t)z * ny + y) * nx;
+            const uint32_t a = g.cell_start[row + x0], b = g.cell_start[row + x1 + 1];
+            for (uint32_t k = a; k < b; ++k) {
+                const float4 q = g.pts[k];
+                const double ex = (double)px - (double)q.x, ey = (double)py - (double)q.y, ez = (double)pz - (double)q.z;
+                if (!(ex * ex + ey * ey + ez * ez <= r2)) continue;
+                const uint32_t bit = 1u << (k & 31u);
+                if (!(bitmap[k >> 5] & bit)) atomicOr(&bitmap[k >> 5], bit); // (neighbouring positions mark the same points: most find the bit set)
+            }
+        }
+}
+
+// dirty positions per block of 256 (8 words of the bitmap)
+__global__ void k_normals_count(const uint32_t *__restrict__ bitmap, int64_t n_blocks, uint32_t *__restrict__ blk_cnt)
+{
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_blocks) return;
+    const uint4 lo = reinterpret_cast<const uint4 *>(bitmap)[2 * b], hi = reinterpret_cast<const uint4 *>(bitmap)[2 * b + 1];
+    blk_cnt[b] = (uint32_t)(__popc(lo.x) + __popc(lo.y) + __popc(lo.z) + __popc(lo.w) + __popc(hi.x) + __popc(hi.y) + __popc(hi.z) + __popc(hi.w));
+}
+
+// bitmap -> the dirty positions in ascending order: one lane per position, its slot = the dirty ones in front of it
+__global__ __launch_bounds__(256) void k_normals_compact(const uint32_t *__restrict__ bitmap, const uint32_t *__restrict__ blk_pre, int64_t n, int64_t cap, uint32_t *__restrict__ list)
+{
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t w = threadIdx.x >> 5, bit = threadIdx.x & 31u;
+    const uint32_t *words = bitmap + (size_t)blockIdx.x * 8;
+    const uint32_t mine = words[w];
+    if (!((mine >> bit) & 1u)) return;
+    uint32_t o = blk_pre[blockIdx.x] + (uint32_t)__popc(mine & ((1u << bit) - 1u));
+    for (uint32_t k = 0; k < w; ++k) o += (uint32_t)__popc(words[k]);
+    if ((int64_t)o < cap) list[o] = (uint32_t)p;
+}
+
+__global__ __launch_bounds__(256) void k_normals_list(SfGrid g, double r2, int R, const uint32_t *__restrict__ list, int64_t n_list, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_list) return;
+    normals_point(g, r2, R, (int64_t)list[t], nrm4, cov6);
+}
+
+inline int normals_reach(float radius, float h) { return std::max(1, (int)std::ceil((double)radius / (double)h - 1e-9)); }
+
+int carry_reestimate(sf_map *m, const sf_cloud::MergeRecord &rec, const int old_dim[3], float radius, bool with_cov, int64_t *n_dirty)
+{
+    sf_ctx *ctx = m->ctx;
+    hipStream_t st = ctx->stream;
+    const SfGrid &g = m->grid;
+    const int64_t n = g.n, ng = rec.n_groups;
+    *n_dirty = 0;
+    if (n <= 0) return SF_OK;
+    const double r2 = (double)radius * (double)radius;
+    const int R = normals_reach(radius, g.h);
+    // [bitmap: 8 words per block of 256 positions | counts | their exclusive prefix (one entry more: the total)]
+    const int64_t nb = sf::div_up(n, 256);
+    const size_t off_cnt = 4 * 8 * (size_t)nb, off_pre = off_cnt + 4 * (size_t)(nb + 1), total = off_pre + 4 * (size_t)(nb + 1);
+    SF_TRY(m->carry_tmp.reserve(total));
+    unsigned char *base = m->carry_tmp.as<unsigned char>();
+    uint32_t *bitmap = reinterpret_cast<uint32_t *>(base), *blk_cnt = reinterpret_cast<uint32_t *>(base + off_cnt), *blk_pre = reinterpret_cast<uint32_t *>(base + off_pre);
+    SF_HIP(hipMemsetAsync(base, 0, off_pre, st)); // bitmap and counts (the count behind the last block stays 0)
+    hipLaunchKernelGGL(k_normals_mark, dim3(nblk(2 * ng)), dim3(256), 0, st, g, old_dim[0], old_dim[1], old_dim[2], r2, R, rec.g_fresh, rec.g_centroid, rec.g_old, ng, bitmap);
+    hipLaunchKernelGGL(k_normals_count, dim3(nblk(nb)), dim3(256), 0, st, bitmap, nb, blk_cnt);
+    SF_TRY(sf::scan_u32<0>(ctx, blk_cnt, blk_pre, nb + 1));
+    uint32_t *h_cnt = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(ctx->h_pinned) + 320);
+    SF_HIP(hipMemcpyAsync(h_cnt, blk_pre + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipStreamSynchronize(st)); // the one read-back: the size of the list launch (and sf_map_normals_carry_info)
+    const int64_t nd = (int64_t)*h_cnt;
+    *n_dirty = nd;
+    if (nd <= 0) return SF_OK;
+    // (the list grows in steps: a growth step's share of the map moves little from one step to the next)
+    SF_TRY(m->carry_list.reserve(sizeof(uint32_t) * (size_t)std::max<int64_t>(nd + nd / 2, 1 << 16)));
+    uint32_t *list = m->carry_list.as<uint32_t>();
+    hipLaunchKernelGGL(k_normals_compact, dim3((unsigned)nb), dim3(256), 0, st, bitmap, blk_pre, n, nd, list);
+    hipLaunchKernelGGL(k_normals_list, dim3(nblk(nd)), dim3(256), 0, st, g, r2, R, list, nd, m->nrm4.as<float4>(), with_cov ? m->cov6.as<double>() : nullptr);
+    SF_HIP(hipGetLastError());
+    return SF_OK; // enqueued behind the patch: every reader of the normals is on this stream
+}
+
 __global__ void k_normals_from_host_order(SfGrid g, const float *__restrict__ nrm_orig, float4 *__restrict__ nrm4)
 {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -827,7 +1004,7 @@ extern "C" int sf_map_estimate_normals_cov(sf_map *m, float radius, int with_cov
     SF_TRY(m->nrm4.reserve(sizeof(float4) * (size_t)std::max<int64_t>(m->n, 1)));
     m->has_cov = false;
     if (with_covariance) SF_TRY(m->cov6.reserve(sizeof(double) * 6 * (size_t)std::max<int64_t>(m->n, 1)));
-    const int R = std::max(1, (int)std::ceil((double)radius / (double)m->grid.h - 1e-9));
+    const int R = normals_reach(radius, m->grid.h);
     if (m->grid.n > 0)
         hipLaunchKernelGGL(k_normals, dim3(nblk(m->grid.n)), dim3(256), 0, ctx->stream, m->grid, (double)radius * (double)radius, R, m->nrm4.as<float4>(),
                            with_covariance ? m->cov6.as<double>() : nullptr);
@@ -836,7 +1013,24 @@ extern "C" int sf_map_estimate_normals_cov(sf_map *m, float radius, int with_cov
     m->grid.nrm = m->nrm4.as<float4>();
     m->has_normals = true;
     m->has_cov = with_covariance != 0;
+    m->nrm_estimated = true; // what sf_map_patch carries (sf_map_set_normals_carry)
+    m->nrm_radius = radius;
+    m->nrm_with_cov = with_covariance != 0;
     m->generation = sf::next_generation();
+    return SF_OK;
+}
+
+extern "C" int sf_map_set_normals_carry(sf_map *m, int on)
+{
+    SF_CHECK(m, SF_ERR_INVALID, "bad arguments");
+    m->normals_carry = on != 0;
+    return SF_OK;
+}
+
+extern "C" int sf_map_normals_carry_info(sf_map *m, int64_t out[4])
+{
+    SF_CHECK(m && out, SF_ERR_INVALID, "bad arguments");
+    for (int k = 0; k < 4; ++k) out[k] = m->carry_info[k];
     return SF_OK;
 }
 
@@ -876,6 +1070,7 @@ extern "C" int sf_map_set_normals(sf_map *m, const float *normals, int64_t n)
     m->grid.nrm = m->nrm4.as<float4>();
     m->has_normals = true;
     m->has_cov = false;
+    m->nrm_estimated = false; // normals of the caller's: nothing to re-estimate them with, sf_map_patch drops them
     m->generation = sf::next_generation();
     return SF_OK;
 }

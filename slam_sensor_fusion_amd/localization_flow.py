@@ -341,10 +341,28 @@ class ImuEkfMappingFlow(EkfLocalizationFlow):
     gyro_bias_walk_, accel_bias_walk_ = 1e-5, 1e-4
     start_velocity_var_ = 1.0
 
-    def __init__(self, ctx, map_points, map_T_global, altitude_table=None, grow_every=None, voxel_flavour="pcl", icp_covariance=None):
+    carry_normals_ = True              # icp_mode "p2plane": the map's normals ride along with sf_map_patch (sf_map_set_normals_carry)
+
+    def __init__(self, ctx, map_points, map_T_global, altitude_table=None, grow_every=None, voxel_flavour="pcl", icp_covariance=None, icp_mode=None,
+                 normal_radius=None):
         super().__init__(ctx, map_points, map_T_global, altitude_table, icp_covariance=icp_covariance)
         if grow_every is not None:
             self.grow_every_ = int(grow_every)
+        # point-to-plane against the growing map (with it the robust kernels, the frozen pairs and the pose covariance): the map
+        # needs normals after every growth step.  They are estimated once here, at `normal_radius`, and carried from then on.
+        if icp_mode is not None:
+            if icp_mode not in api.MODES:
+                raise ValueError("icp_mode must be one of %s" % sorted(api.MODES))
+            self.icp_mode_ = icp_mode
+        self.normal_radius_ = None
+        if self.icp_mode_ == "p2plane":
+            if normal_radius is None or not float(normal_radius) > 0:
+                raise ValueError("icp_mode 'p2plane' needs normal_radius > 0 (the neighbourhood of the map normals, metres)")
+            self.normal_radius_ = float(normal_radius)
+        elif normal_radius is not None:                       # (a radius without the mode that reads normals: the map would have none)
+            raise ValueError("normal_radius is only used with icp_mode='p2plane' (the mode is %r)" % self.icp_mode_)
+        self.normals_carried_ = 0                             # growth steps whose normals came over the patch
+        self.normals_recomputed_points_ = 0                   # map points whose normal was estimated again, over all growth steps
         self.icp_.set_num_iterations(self.mapping_icp_iterations_)
         self.icp_.set_max_correspondence_dist(self.mapping_max_corr_)
         self.map_index_.set_origin_lattice(self.origin_lattice_cells_)   # a map that grows: the grid origin survives growth in any direction (sf_map_patch)
@@ -354,6 +372,10 @@ class ImuEkfMappingFlow(EkfLocalizationFlow):
             self.index_cloud_.subsample(self.index_stride_)
             self.map_index_.build(self.index_cloud_, 0.0)
             self.map_cloud_ = self.index_cloud_
+            self.icp_.set_target(self.map_index_)
+        if self.normal_radius_ is not None:
+            self.map_index_.estimate_normals(self.normal_radius_)
+            self.map_index_.set_normals_carry(self.carry_normals_)
             self.icp_.set_target(self.map_index_)
         self.voxel_flavour_ = voxel_flavour
         self.map_full_ = api.Cloud(ctx, np.asarray(map_points, dtype=np.float32))   # the voxel-filtered map at full resolution
@@ -401,6 +423,13 @@ class ImuEkfMappingFlow(EkfLocalizationFlow):
         if self.scans_since_growth_ >= self.grow_every_:
             self.grow_map()
 
+    def estimate_map_normals(self):
+        """The full normals pass after a build (a build drops them): nothing to carry from."""
+        if self.normal_radius_ is None:
+            return
+        self.map_index_.estimate_normals(self.normal_radius_)
+        self.normals_recomputed_points_ += len(self.map_index_)
+
     def grow_map(self):
         if self.on_grow is not None:
             self.on_grow(self)
@@ -414,13 +443,22 @@ class ImuEkfMappingFlow(EkfLocalizationFlow):
             if self.index_cloud_ is self.map_full_:           # ... and carried over the growth step when it indexed this very cloud before the merge
                 self.patches_ += int(self.map_index_.patch(self.map_full_))
                 self.patch_codes_[self.map_index_.last_patch] = self.patch_codes_.get(self.map_index_.last_patch, 0) + 1
+                if self.normal_radius_ is not None:
+                    how, _, redone, _ = self.map_index_.normals_carry_info()
+                    if how < 0:                               # the carry is off: the full pass
+                        self.estimate_map_normals()
+                    else:
+                        self.normals_carried_ += int(how == 1)
+                        self.normals_recomputed_points_ += redone
             else:
                 self.index_cloud_ = self.map_full_
                 self.map_index_.build(self.index_cloud_, 0.0)
+                self.estimate_map_normals()
         else:
             self.index_cloud_.copy_from(self.map_full_)
             self.index_cloud_.subsample(self.index_stride_)
             self.map_index_.build(self.index_cloud_, 0.0)
+            self.estimate_map_normals()
         self.map_cloud_ = self.index_cloud_
         self.icp_.set_target(self.map_index_)
         self.have_window_ = False                             # the rebuilt index has no window yet: set at the next scan
