@@ -284,7 +284,15 @@ int sf_icp_align(sf_icp *icp, int mode, sf_icp_result *out);
 
 /* batched throughput form: `batch` scans of n_per_scan points each (xyz contiguous,
  * scan-major), one initial transform per scan (inits = batch*16 doubles, NULL = identity),
- * all registered concurrently against the same target map in ONE kernel sequence. */
+ * all registered concurrently against the same target map in ONE kernel sequence.
+ * Lifetime of `xyz` (pinned memory: the copy is asynchronous): with the pipeline on (sf_icp_set_pipeline), a host buffer set
+ * while an alignment is unfetched is read on an internal stream, not on the context's -- synchronising the context's stream
+ * does not mean it has been consumed -- and it is free again only once that batch's alignment has been fetched
+ * (sf_icp_fetch_results / sf_icp_fetch_previous).  A streaming loop therefore takes two host buffers in turn.  Otherwise
+ * (nothing unfetched, pipeline off) the copy is ordered on the context's stream.
+ * A source set ahead in this way is adopted by whichever alignment comes next, also a stepped or a sharded one
+ * (sf_icp_step_begin with first != 0, sf_icp_align_sharded*, sf_icp_align_group): it waits for the upload and sizes its
+ * buffers for the new batch. */
 int sf_icp_set_source_batch(sf_icp *icp, const float *xyz, int64_t n_per_scan, int batch);
 int sf_icp_set_source_batch_device(sf_icp *icp, const void *d_xyz, int64_t n_per_scan, int batch);
 int sf_icp_set_initial_batch_f64(sf_icp *icp, const double *inits);
@@ -318,7 +326,9 @@ int sf_icp_fused_count(sf_icp *icp, int64_t *launches);
 /* Residency of a single-launch grid is kept by a per-device ledger of the grids in flight (all contexts of the process);
  * an alignment that does not fit takes the launch list.  Should a grid barrier still give up (another PROCESS holding the
  * compute units), the alignment is redone through the launch list inside sf_icp_fetch_results and the object stays on
- * the launch list: sf_icp_fused_redone counts how often that happened. */
+ * the launch list: sf_icp_fused_redone counts how often that happened.  The redo aligns what was enqueued -- that
+ * alignment's source, priors and mode -- also when the next batch's source and priors have been set since (pipeline on: the
+ * two source sets); with the pipeline off a source set since has replaced it in place, and the fetch returns SF_ERR_STATE. */
 int sf_icp_fused_redone(sf_icp *icp, int64_t *redone);
 int sf_icp_test_inject_barrier_timeout(sf_icp *icp); /* test hook: treat the next single-launch alignment as timed out (exercises the redo) */
 /* Order in which the points of a scan are walked by O3D_P2P / P2PLANE.  The correspondences and

@@ -533,8 +533,9 @@ class Icp:
         self.batch = xyz.shape[0]
 
     def set_source_batch_host_ptr(self, ptr, n_per_scan, batch):
-        """batch x n_per_scan x 3 float32 at a raw HOST address (e.g. pinned memory: the copy is then asynchronous and
-        stream-ordered -- the buffer must stay untouched until the stream has passed it)"""
+        """batch x n_per_scan x 3 float32 at a raw HOST address (e.g. pinned memory: the copy is then asynchronous).  With the
+        pipeline on, a buffer set while an alignment is unfetched is read on an internal stream: it is free again only once that
+        batch's alignment has been fetched; otherwise once the context's stream has passed it (include/slamfusion.h)"""
         _check(self.lib.sf_icp_set_source_batch(self.h, C.c_void_p(ptr), C.c_int64(n_per_scan), C.c_int(batch)))
         self.batch = batch
 
@@ -723,6 +724,8 @@ class Icp:
 
     def step_begin(self, mode, first):
         _check(self.lib.sf_icp_step_begin(self.h, C.c_int(MODES[mode]), C.c_int(int(first))))
+        if int(first) == 1:                                   # a new alignment: fetch_results returns ITS scans (a source set since an earlier align_batch_async may hold another number)
+            self._last_batch = self.batch
 
     def step_end(self, mode, last):
         _check(self.lib.sf_icp_step_end(self.h, C.c_int(MODES[mode]), C.c_int(int(last))))

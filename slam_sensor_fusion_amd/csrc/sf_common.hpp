@@ -100,7 +100,7 @@ struct sf_ctx {
     sf::DevBuf scratch2;  // block counts / small reductions
     sf::DevBuf sort_hist, scan_tiles; // sf_sort.hpp: digit histograms of the radix sort, tile sums of the scans
     sf::DevBuf merge_tmp;  // sf_cloud_voxel_merge: per-voxel tables of the pending points
-    uint64_t merge_epoch = 0; // bumped by every merge that rewrites merge_tmp (sf_cloud::MergeRecord::epoch)
+    uint64_t merge_epoch = 0; // bumped by every merge BEFORE it first reserves or writes merge_tmp, whichever path it then takes (sf_cloud::MergeRecord::epoch)
     sf::DevBuf vox_tmp[6]; // voxel grids: keys, keys', point ids, point ids', head flags, positions -- kept between calls (a growing map re-voxelises every few scans)
     void *h_pinned = nullptr; // small pinned staging (4 KiB)
     // pageable -> device uploads go through two pinned buffers in turn (sf::upload_staged): the runtime's own staging of

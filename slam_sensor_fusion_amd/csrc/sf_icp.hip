@@ -3111,6 +3111,8 @@ struct sf_icp {
         bool cov = false; // it ran with the covariance switch on: cov_out of its lane holds its sf_icp_covariance entries
         int batch = 0, mode = 0;
         std::vector<double> inits;
+        int src_set = 0;          // the source set it read, and that set's version then: a redo after a barrier timeout aligns THAT source
+        uint64_t src_version = 0;
     } meta, other_meta;
     bool prev_ok = false;         // the alignment before the latest one ran on the other lane and has not been overwritten or fetched
     std::vector<IcpState> h_prev;
@@ -4083,12 +4085,13 @@ int launch_fused(sf_icp *icp, int mode)
 // a grid barrier of the single-launch form gave up (another process holding the CUs its workgroups needed): the counters
 // are put back, this object takes the launch list from now on, and the alignment is redone that way -- the initial
 // transforms and the source are untouched, so the caller gets the result it asked for, late
+// count: the scans of the alignment being fetched (a source set since, for the next alignment, may hold another number)
 int redo_after_barrier_timeout(sf_icp *icp);
-int check_barrier_flags(sf_icp *icp)
+int check_barrier_flags(sf_icp *icp, int count)
 {
     if (!icp->last_fused) return SF_OK;
     bool bad = false;
-    for (int b = 0; b < icp->batch; ++b) bad = bad || (icp->h_state[(size_t)b].flags & SF_ICP_FLAG_BARRIER_TIMEOUT);
+    for (int b = 0; b < count; ++b) bad = bad || (icp->h_state[(size_t)b].flags & SF_ICP_FLAG_BARRIER_TIMEOUT);
     bad = bad || icp->inject_timeout;
     icp->inject_timeout = false;
     if (!bad) return SF_OK;
@@ -4657,6 +4660,25 @@ struct LaneScope {
         if (piped) { hipError_t e = hipStreamWaitEvent(main, icp->lane_done[icp->lane], 0); (void)e; }
     }
 };
+
+// The stepping and the sharded entry points run on the context's stream in the buffers at hand, without a LaneScope.  A source that
+// SrcScope wrote ahead of an unfetched alignment (on a lane's stream, icp_alloc(outputs = false)) is theirs to adopt at the start of
+// an alignment: the context's stream waits for the upload, and everything an alignment writes per scan -- states, initial poses,
+// partial rows, the exchange records -- is sized for the source now at hand.  They leave no event on the source set they read: the
+// next source written ahead waits for the context's stream instead (src_unmarked_use).
+int step_adopt_source(sf_icp *icp)
+{
+    if (icp->src_ahead) {
+        SF_HIP(hipStreamWaitEvent(icp->ctx->stream, icp->src_ready, 0));
+        icp->src_ahead = false;
+    }
+    const auto e0 = icp->state.epoch;
+    SF_TRY(lane_reserve(icp));
+    if (icp->state.epoch != e0) icp->meta.valid = false; // (as icp_alloc: the states of the last alignment went with the old allocation)
+    SF_TRY(icp->xchg_own.reserve(sizeof(double) * REC_STRIDE * (size_t)std::max(icp->batch, 1)));
+    icp->src_unmarked_use = true;
+    return SF_OK;
+}
 } // namespace
 
 extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
@@ -4681,6 +4703,8 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     icp->meta.batch = icp->batch;
     icp->meta.mode = mode;
     icp->meta.inits = icp->inits;
+    icp->meta.src_set = icp->src_set;
+    icp->meta.src_version = icp->src_version;
     hipStream_t s = icp->ctx->stream;
     if (icp->cov_on) SF_TRY(cov_alloc(icp)); // (before any capture, and before the graph key is formed)
     SF_TRY(launch_state_init(icp));
@@ -4731,13 +4755,41 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
 }
 
 namespace {
+// The alignment that is redone is the one being fetched, as it was enqueued (icp->meta): its source, its priors, its mode.  A source
+// and priors set since belong to the NEXT alignment.  With the lanes on that source went into the other source set (SrcScope), so
+// the set the alignment read is still whole: it is flipped in for the redo and out again afterwards, and the upload written ahead
+// keeps its mark (src_ahead) for the alignment that will read it.  A source that replaced the alignment's own in place (no lanes)
+// leaves nothing to redo from: an error, not another batch's poses.
 int redo_after_barrier_timeout(sf_icp *icp)
 {
-    SF_TRY(sf_icp_align_batch_async(icp, icp->last_mode)); // fused_limit is zero now: the launch list
-    SF_TRY(states_to_host(icp));
-    for (int b = 0; b < icp->batch; ++b)
-        SF_CHECK(!(icp->h_state[(size_t)b].flags & SF_ICP_FLAG_BARRIER_TIMEOUT), SF_ERR_HIP, "alignment redone through the launch list still carries a barrier flag");
-    return SF_OK;
+    const sf_icp::LaneMeta was = icp->meta;
+    const bool flip = was.valid && was.src_set != icp->src_set;
+    SF_CHECK(!was.valid || flip || was.src_version == icp->src_version, SF_ERR_STATE,
+             "a grid barrier timed out and the alignment cannot be redone: its source was replaced before the fetch");
+    const bool ahead = icp->src_ahead;
+    std::vector<double> next_inits;
+    if (was.valid) {
+        if (flip) src_flip(icp);
+        icp->src_ahead = false; // (the redo reads nothing of the upload written ahead, and runs on the context's stream)
+        next_inits.swap(icp->inits);
+        icp->inits = was.inits;
+    }
+    int rc = sf_icp_align_batch_async(icp, was.valid ? was.mode : icp->last_mode); // fused_limit is zero now: the launch list
+    if (rc == SF_OK) rc = states_to_host(icp);
+    if (rc == SF_OK) {
+        icp->unfetched = false; // (the states are on the host)
+        for (int b = 0; b < icp->batch && rc == SF_OK; ++b)
+            if (icp->h_state[(size_t)b].flags & SF_ICP_FLAG_BARRIER_TIMEOUT) {
+                sf::set_error("alignment redone through the launch list still carries a barrier flag");
+                rc = SF_ERR_HIP;
+            }
+    }
+    if (was.valid) { // what the next alignment will see: the source and the priors set for it
+        icp->inits.swap(next_inits);
+        if (flip) src_flip(icp);
+        icp->src_ahead = ahead;
+    }
+    return rc;
 }
 } // namespace
 
@@ -4752,7 +4804,7 @@ extern "C" int sf_icp_fetch_results(sf_icp *icp, sf_icp_result *out)
     icp->unfetched = false;
     fused_release(icp); // the grid has drained
     if (icp->profiling) prof_collect(icp);
-    if (nb == icp->batch) SF_TRY(check_barrier_flags(icp));
+    SF_TRY(check_barrier_flags(icp, nb));
     for (int b = 0; b < nb; ++b)
         fill_result(icp, described ? icp->meta.mode : icp->last_mode, icp->h_state[(size_t)b], described ? &icp->meta.inits[(size_t)b * 16] : &icp->inits[(size_t)b * 16], out + b);
     if (nb == icp->batch) freeze_learn_schedule(icp);
@@ -4950,6 +5002,16 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = false;
+    if (first) SF_TRY(step_adopt_source(icp)); // (sf_icp_align_group and the all-reduce form of sf_icp_align_sharded_async start here too)
+    if (first == 1) { // sf_icp_fetch_results describes the latest alignment as it was enqueued: this one
+        icp->meta.valid = true;
+        icp->meta.cov = false;
+        icp->meta.batch = icp->batch;
+        icp->meta.mode = mode;
+        icp->meta.inits = icp->inits;
+        icp->meta.src_set = icp->src_set;
+        icp->meta.src_version = icp->src_version;
+    }
     if (first) icp->df_planned = defer_planned(icp, mode);
     if (first) SF_TRY(order_lut_prepare(icp));
     if (first == 1) SF_TRY(launch_state_init(icp));
@@ -5104,6 +5166,8 @@ extern "C" int sf_icp_align_sharded_async(sf_icp *icp, int mode, sf_comm *comm, 
     SF_CHECK(icp->shard, SF_ERR_STATE, "sf_icp_set_shard first");
     SF_CHECK(first == 1 || first == 2, SF_ERR_INVALID, "first must be 1 (start) or 2 (resume)");
     SF_CHECK(!icp->cov_on, SF_ERR_STATE, COV_DECLINE_MSG);
+    SF_HIP(hipSetDevice(icp->ctx->device));
+    SF_TRY(step_adopt_source(icp)); // (before the exchange is sized: shard_step_p2p does not pass sf_icp_step_begin)
     const int steps = sharded_steps(icp, mode);
     int rc = SF_OK;
     for (int k = 0; k < steps && rc == SF_OK; ++k) {

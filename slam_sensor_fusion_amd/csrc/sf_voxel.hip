@@ -462,6 +462,10 @@ extern "C" int sf_cloud_voxel_merge(sf_cloud *map, sf_cloud *pending, double lea
     // (both reductions enqueued, ONE synchronisation: on a map of a few million points the merge is bound by its host round trips)
     sf::DevBuf &mt = ctx->merge_tmp;
     const int64_t n_coarse = n / 64 + 2;
+    // from here on merge_tmp is reserved (freed and reallocated when it grows) and written -- the reductions below already land in it,
+    // at an offset that depends on THIS call's m --, whichever way this call ends: the record of every earlier merge on this context,
+    // of this cloud or another, stops being valid now and not only once the merge path is certain (sf_map_patch compares the epochs)
+    ++ctx->merge_epoch;
     SF_TRY(mt.reserve(sizeof(uint32_t) * 4 * (size_t)m + sizeof(float) * 6 * (size_t)m + 64 + 2 * sizeof(sf::MinMaxDev) + sizeof(uint32_t) * (size_t)n_coarse));
     sf::MinMaxDev *d_mm = reinterpret_cast<sf::MinMaxDev *>(mt.as<unsigned char>() + sizeof(uint32_t) * 4 * (size_t)m + sizeof(float) * 6 * (size_t)m + 64);
     uint32_t *coarse = reinterpret_cast<uint32_t *>(d_mm + 2);
@@ -511,7 +515,6 @@ extern "C" int sf_cloud_voxel_merge(sf_cloud *map, sf_cloud *pending, double lea
     SF_TRY(pos.reserve(sizeof(uint32_t) * (size_t)(n + 2 * m)));
     // per group: rank, fresh flag, fresh prefix, fresh ranks, centroid; + the "keys not ascending" flag (mt reserved above)
     uint32_t *g_rank = mt.as<uint32_t>(), *g_fresh = g_rank + m, *fresh_pos = g_fresh + m, *fresh_rank = fresh_pos + m;
-    ++ctx->merge_epoch;
     float *g_centroid = reinterpret_cast<float *>(fresh_rank + m), *g_old = g_centroid + 3 * m;
     uint32_t *bad = reinterpret_cast<uint32_t *>(g_old + 3 * m);
     MergeExtremes *d_ext = reinterpret_cast<MergeExtremes *>(bad + 4); // (inside the 64 spare bytes)

@@ -211,6 +211,104 @@ def test_index_patch_equals_rebuild(api, ctx, synth):
         api.voxel_merge_min_points(prev)
 
 
+@pytest.mark.parametrize("case", ["grow after reserve", "no reallocation", "B takes the merge path", "B below the threshold", "grow after reserve, normals carried"])
+def test_a_merge_on_another_cloud_never_corrupts_a_patch(api, synth, case):
+    """The merge tables are the context's (ctx->merge_tmp), the record that points into them is the cloud's: merge(A, pendA) on
+    cloud A, then something on cloud B of the same context, then patch(A).  Whatever B's call did to the tables, the index of A is,
+    bit for bit, sf_map_build of A's cloud at the same cell (points with their ids, cell table, geometry), and the patch says
+    truthfully whether it merged.  Every case on a context of its own, so the size of the scratch is the one this case left.
+
+    grow after reserve     pendB three times pendA's size and all NaN: B's merge reserves the scratch -- beyond pendA's, so it is
+                           freed and allocated anew -- and then falls back (no finite pending point).  A's record points at freed
+                           memory: patch(A) must say SF_PATCH_NO_MERGE.
+    no reallocation        pendB a thirtieth of pendA's size with one point 100 km away: nothing is reallocated, B's merge writes its
+                           two bounding-box records at byte 40 m_B + 64 of the scratch -- inside A's g_rank table, among the groups
+                           in use (both checked below with numpy) -- and falls back because dx dy dz > INT32_MAX (restated below).
+                           patch(A) must say SF_PATCH_NO_MERGE.
+    B takes the merge path merged for B: A's record is older than the tables, SF_PATCH_NO_MERGE.
+    B below the threshold  B has fewer points than sf_cloud_voxel_merge_min_points: its merge returns before it touches the scratch,
+                           and A's patch must still merge (patched == 1).
+    ..., normals carried   the first case with sf_map_set_normals_carry and covariances: normals, neighbour counts and covariances
+                           equal a build followed by sf_map_estimate_normals_cov, bit for bit (tests/test_gpu_normals_carry.py).
+
+    What makes the first two and the last pass: `++ctx->merge_epoch` standing BEFORE `mt.reserve(...)` in sf_cloud_voxel_merge
+    (csrc/sf_voxel.hip), so that the fall-backs behind the reserve invalidate A's record too (sf_map_patch compares rec.epoch with
+    ctx->merge_epoch, csrc/sf_map.hip).  With the bump behind the fall-backs patch(A) walks freed or overwritten tables.  The third
+    held before (the merge path always bumped); the fourth pins that the early return -- which touches nothing -- does not bump."""
+    from test_gpu_normals_carry import _assert_same_normals
+    rng = np.random.default_rng(33)
+    carry = case.endswith("normals carried")
+    own = api.Context(0)
+    prev = api.voxel_merge_min_points(1000)
+    made = []
+
+    def keep(obj):
+        made.append(obj)
+        return obj
+    try:
+        base = synth.make_map(400_000)                                # 20 m x 20 m x 10 m
+        in_a = base[(np.abs(base[:, 0]) < 6.0) & (np.abs(base[:, 1]) < 6.0)]
+        in_b = in_a[:600] if case == "B below the threshold" else base[(np.abs(base[:, 0]) < 5.0) & (np.abs(base[:, 1]) < 5.0)]
+        a, b = keep(api.Cloud(own, in_a)), keep(api.Cloud(own, in_b))
+        assert a.voxel_downsample(0.1, "pcl") == 0 and b.voxel_downsample(0.1, "pcl") == 0
+        assert len(a) >= 1000 and (len(b) < 1000) == (case == "B below the threshold") and 0 < len(b) <= len(a)
+        new_map = lambda cloud, c: keep(api.Map(own)).set_origin_lattice(64).build(cloud, c)
+        mp = new_map(a, 0.25)
+        h = mp.cell_size()[0]
+        if carry:
+            mp.estimate_normals(0.25, True)
+            mp.set_normals_carry(True)
+        near = lambda src, n: (src[rng.choice(len(src), n, replace=False)] + rng.normal(0, 0.004, (n, 3))).astype(np.float32)
+        core_a = in_a[(np.abs(in_a[:, 0]) < 5.5) & (np.abs(in_a[:, 1]) < 5.5) & (np.abs(in_a[:, 2]) < 4.5)]   # (away from the points that hold the extremes)
+        core_b = in_b if len(in_b) < 1000 else in_b[(np.abs(in_b[:, 0]) < 4.5) & (np.abs(in_b[:, 1]) < 4.5) & (np.abs(in_b[:, 2]) < 4.5)]
+        pend_a = near(core_a, 30_000)
+        m_a = len(pend_a)
+        st, merged = a.voxel_merge(keep(api.Cloud(own, pend_a)), 0.1)
+        assert st == 0 and merged, case
+
+        if case.startswith("grow after reserve"):
+            pend_b = np.full((3 * m_a, 3), np.nan, np.float32)         # (DevBuf::reserve keeps an eighth to spare: well beyond it)
+            expect_b, expect_a = False, 0
+        elif case == "no reallocation":
+            pend_b = np.concatenate([near(core_b, 1_000), np.array([[100_000.0, 0.0, 0.0]], np.float32)])
+            m_b = len(pend_b)
+            assert 2 * m_b <= m_a and np.isfinite(pend_b).all()
+            # sf_cloud_voxel_merge: the bounds of the union in float32, the voxel counts per axis in int64
+            old_b = b.download()
+            inv = np.float32(1.0) / np.float32(0.1)
+            mn = np.minimum(old_b.min(0), pend_b.min(0)).astype(np.float32)
+            mx = np.maximum(old_b.max(0), pend_b.max(0)).astype(np.float32)
+            dxyz = [int(np.int64((mx[d] - mn[d]) * inv)) + 1 for d in range(3)]
+            assert dxyz[0] * dxyz[1] * dxyz[2] > 2 ** 31 - 1, dxyz
+            # where the two 32-byte records of the bounds land: in A's first table (g_rank: 4 m_A bytes), at groups that exist
+            first, last = (40 * m_b + 64) // 4, (40 * m_b + 64 + 64) // 4
+            groups_a = len(np.unique(np.floor(pend_a.astype(np.float64) / 0.1).astype(np.int64), axis=0))
+            assert last <= m_a and last < groups_a - 100, (first, last, m_a, groups_a)
+            expect_b, expect_a = False, 0
+        elif case == "B takes the merge path":
+            pend_b = near(core_b, 20_000)
+            expect_b, expect_a = True, 0
+        else:
+            pend_b = near(core_b, 300)
+            expect_b, expect_a = False, 1
+        st_b, merged_b = b.voxel_merge(keep(api.Cloud(own, pend_b)), 0.1)
+        assert merged_b == expect_b, (case, st_b)
+
+        patched = mp.patch(a)
+        assert mp.last_patch == expect_a and patched == (expect_a > 0), (case, mp.last_patch)   # (0 is SF_PATCH_NO_MERGE)
+        ref = new_map(a, h)
+        assert _same_index(mp.index(), ref.index()) == "", (case, _same_index(mp.index(), ref.index()))
+        assert mp.cell_size() == ref.cell_size() and len(mp) == len(ref) == len(a)
+        if carry:
+            ref.estimate_normals(0.25, True)
+            _assert_same_normals(mp, ref, True, case)
+    finally:
+        api.voxel_merge_min_points(prev)
+        for obj in reversed(made):
+            obj.close()
+        own.close()
+
+
 def test_index_patch_registration_identical(api, ctx, synth):
     """A registration against the patched index equals one against the rebuilt index, bit for bit, normals re-estimated on both."""
     rng = np.random.default_rng(10)

@@ -343,6 +343,60 @@ def test_two_contexts_both_on_the_single_launch_path(api, ctx, orc, synth):
     ctx2.synchronize()
 
 
+@pytest.mark.parametrize("mode", ["ref_cpp", "o3d_p2p", "p2plane"])
+def test_a_redone_alignment_is_the_one_that_was_enqueued(api, ctx, synth, small_world, mode):
+    """A barrier timeout (injected) on a single-launch alignment of batch S0, and -- before the fetch -- the next batch S1 with its
+    own priors set on the object (lanes on: the upload goes ahead into the other source set).  The fetch redoes the alignment
+    through the launch list: the result must be S0's with S0's priors, bitwise that of a clean launch-list object, not S1's; and
+    the alignment after it must see S1 and S1's priors.  The same with a next batch of another shape (two scans of fewer points),
+    where the fetch must still look at the barrier flags of the three scans it fetches.
+
+    What makes it pass: redo_after_barrier_timeout (csrc/sf_icp.hip) flips the source set the fetched alignment read back in
+    (icp->meta.src_set, recorded by sf_icp_align_batch_async), restores its priors and mode from icp->meta for the redo, and puts
+    the next batch's source, priors and src_ahead back afterwards; sf_icp_fetch_results checks the barrier flags of the scans it
+    fetches whatever the batch now at hand.  Before, the redo aligned whatever source and priors were at hand: S1 returned as S0."""
+    m = small_world["map"]
+    mp = api.Map(ctx, api.Cloud(ctx, m), 0.25)
+    mp.estimate_normals(0.25)
+    batch = lambda k, n, nb: np.stack([synth.make_scan(m, n, scan_id=700 + 10 * k + b)[0][:n] for b in range(nb)])
+    prior = lambda k, nb: np.stack([synth.make_T((0.02 * (k + 1), -0.01 * b, 0.01), (0.1 * b, 0.05 * (k + 1), 0.2)) for b in range(nb)])
+    S = [batch(0, 6000, 3), batch(1, 6000, 3), batch(2, 4000, 2)]
+    P = [prior(0, 3), prior(1, 3), prior(2, 2)]
+
+    def make(fused):
+        icp = api.Icp(ctx, 0.5, 12, 0.05, 1e-5)
+        icp.set_target(mp)
+        icp.set_fused(fused)
+        icp.set_pipeline(True)
+        return icp
+
+    def same(got, want):
+        assert len(got) == len(want)
+        for g, w in zip(got, want):
+            assert np.array_equal(g["T64"], w["T64"]) and g["iterations"] == w["iterations"] and g["n_corr"] == w["n_corr"] and g["rmse"] == w["rmse"] and g["flags"] == w["flags"]
+    clean, want = make(False), []
+    for k in range(3):
+        clean.set_source_batch(S[k])
+        clean.set_initial_batch(P[k])
+        want.append(clean.align_batch(mode))
+    assert not np.array_equal(want[0][0]["T64"], want[1][0]["T64"])       # (the two batches are told apart by their results)
+    for nxt in (1, 2):
+        icp = make(True)
+        icp.set_source_batch(S[0])
+        icp.set_initial_batch(P[0])
+        n0 = icp.fused_count()
+        icp.test_inject_barrier_timeout()
+        icp.align_batch_async(mode)
+        assert icp.fused_count() == n0 + 1                                # the single launch took it
+        icp.set_source_batch(S[nxt])                                      # the next batch, ahead of the fetch
+        icp.set_initial_batch(P[nxt])
+        same(icp.fetch_results(), want[0])
+        assert icp.fused_redone() == 1
+        same(icp.align_batch(mode), want[nxt])
+        icp.close()
+    clean.close()
+
+
 def test_start_outside_the_map_recrops_until_the_crop_holds_points(api, ctx, orc, synth):
     """ADVICE r2 (sf_node.cpp:134): the reference re-crops while ref_cropped_map_cloud_ is EMPTY (localization_node.cpp:299),
     e.g. after a first fix more than the 10 m crop radius away from every map point -- every callback, not only after 3 m of
