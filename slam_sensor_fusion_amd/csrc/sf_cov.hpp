@@ -11,7 +11,7 @@
 //   k_cov_solve<MODE>       one workgroup per scan: the rows summed in reduce_partials' fixed order (the same bits run to
 //                           run, and whichever path produced the pose -- both walk the same query arrays), then on one lane
 //                           H, the 6x6 Jacobi eigen-solve, cov, the two 3x3 solves of the marginals, the flags.
-// One query per lane for every scan size: rows of 256 queries (sf_icp::nblocks of them), wide scans included.
+// One query per lane for every scan size: rows of 256 queries (SrcSet::nblocks of them), wide scans included.
 
 constexpr int NREC_COV_PLANE = 24;
 constexpr int NREC_COV_P2P = 11;

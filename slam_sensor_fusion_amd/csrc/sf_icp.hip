@@ -7,8 +7,8 @@
 // 233-237; adds the point-to-plane Gauss-Newton extension.
 //
 // Once per alignment (O3D_P2P / P2PLANE, enough work to pay for it): every scan's points are
-// ordered by the map cell they fall in under the initial pose (k_query_keys, rocPRIM radix sort,
-// k_gather_queries), so that the scans in flight walk the map together.
+// ordered by the map cell they fall in under the initial pose (k_order_hist / k_order_scan /
+// k_order_scatter / k_order_gather, sf_order.hpp), so that the scans in flight walk the map together.
 // Per iteration:
 //   k_nn_red        one lane per source point: s = T*x0 (float64); the neighbour found by the
 //                   point's last search is kept when a bound proved by that search shows it
@@ -2985,41 +2985,23 @@ struct sf_icp {
     sf_ctx *ctx = nullptr;
     IcpParams prm{};
     int debug = 0;
-    // source
-    sf::DevBuf X0, X;        // SoA: x[B*n], y[B*n], z[B*n]
-    sf::DevBuf X0r;          // the same points as float4 records (gather source of the query ordering)
-    sf::DevBuf qcache;       // neighbour reuse, two float4 arrays of cache_n entries: (neighbour, its index), (neighbour's normal, E) -- O3D_P2P: the second array holds E alone, as floats
-    int64_t cache_n = 0;
+    int64_t cache_n = 0;     // entries per array of the lane's qcache
     bool reuse = true;       // sf_icp_set_nn_reuse
-    sf::DevBuf Xq, qkeys, qkeys2, qidx, qidx2; // cell-ordered copy of X0 and the sort's buffers
     int order = SF_ORDER_AUTO;
     bool ordered = false;    // this alignment reads Xq
-    sf::DevBuf corr;         // float4 [B*n] (REF_CPP): a point's target (x, y, z, sorted position or -1 = dead)
-    int64_t n = 0;           // points per scan
-    bool n_on_device = false; // sf_icp_set_source_scan: n is an upper bound, the count itself is in n_dev (single scan, REF_CPP)
-    int64_t n_cap = 0;       // single scan: n rounded up (launch geometry of the REF_CPP kernels)
-    int64_t plane = 0;       // component stride of the SoA arrays X0 / X / Xq
-    sf::DevBuf n_dev;        // the point count in device memory (single-scan REF_CPP kernels read it)
-    int batch = 0;
     std::vector<double> inits; // batch * 16
-    std::vector<double> inits_uploaded; // what d_inits holds (the copy is skipped while nothing changed)
     double *h_inits = nullptr;          // pinned staging of the batch's initial transforms
     size_t h_inits_cap = 0;
     hipEvent_t inits_ev = nullptr;      // recorded after the staging buffer's last copy
     bool inits_ev_pending = false;
-    uint32_t d_inits_epoch = 0xffffffffu;
-    bool have_source = false;
     // target
     sf_map *map = nullptr;
     sf_map *own_map = nullptr;
     sf_cloud *own_cloud = nullptr;
     // device state
-    sf::DevBuf state, d_inits, partials, xchg_own;
+    sf::DevBuf xchg_own;
     void *xchg = nullptr;
     int64_t xchg_bytes = 0;
-    int nblocks = 0;         // workgroups of 256 points covering a scan (REF_CPP kernels, owned-query compaction)
-    int nblocks_nn = 0;      // k_nn_red workgroups per scan = slab rows (256 * qpl queries each)
-    int qpl = 1;             // queries per lane of k_nn_red: 1 up to wide_from points per scan, SF_WIDE_QPL beyond (part of the summation order)
     int64_t wide_from = WIDE_SCAN_POINTS; // sf_icp_set_wide_scan_points: scans above this many points take two queries per lane (and may freeze)
     bool wide_auto = true;   // no explicit limit: scans above WIDE_AUTO_POINTS are wide too when the batch is beyond every single-launch kernel (set_source_common)
     std::vector<IcpState> h_state;
@@ -3032,8 +3014,6 @@ struct sf_icp {
     float own_margin = 1.0f;                          // sf_icp_set_shard_margin
     int own_nblocks = 1;                              // workgroups per scan on the sharded path (largest scan)
     sf::DevBuf d_box;                        // sf::MinMaxDev: bounding box of the source batch (finite points), left on the device
-    sf::DevBuf d_boxes, d_box_parts;         // ScanBox per scan (motion bound of the reuse certificate, owned-array margin), and the partial boxes of their reduction
-    sf::DevBuf stage;                        // persistent upload staging of sf_icp_set_source* (AoS)
     int last_mode = 0;
     // REF_CPP in one launch (k_ref_fused)
     bool fused = true;       // sf_icp_set_fused
@@ -3048,7 +3028,6 @@ struct sf_icp {
     size_t h_pin_cap = 0;
     // graph
     bool use_graph = false;
-    hipGraphExec_t graph_exec = nullptr;
     int64_t graph_captures = 0, graph_replays = 0; // sf_icp_graph_counts
     // everything a captured launch list bakes in: kernel arguments passed by value (thresholds, IcpParams, the
     // SfGrid geometry and pointers) and the addresses of this object's buffers.  A replay is only valid while all of
@@ -3068,44 +3047,8 @@ struct sf_icp {
                    map_generation == o.map_generation && epochs == o.epochs && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
                    robust_kind == o.robust_kind && robust_k == o.robust_k && cov_on == o.cov_on && std::memcmp(cov_prm, o.cov_prm, sizeof(cov_prm)) == 0;
         }
-    } graph_key;
-    // Consecutive asynchronous alignments of the launch list overlap: an alignment's last launches (frozen pairs: fourteen 16 us
-    // kernels on an otherwise idle device) run under the next one's searching launches.  Two LANES take turns; each has its own
-    // stream and its own copy of everything an alignment writes (`other` holds the lane that is not in the members of this struct).
-    // Ordering (LaneScope): a lane starts after the context's stream as it stood when the inputs -- source, initial poses,
-    // target -- last changed, and the context's stream waits for every alignment right after it is enqueued, so whatever the caller
-    // enqueues next (a fetch, an upload, a map rebuild) is ordered behind it as before; only back-to-back alignments of unchanged
-    // inputs run side by side.  Same kernels, same data, same results (tests/test_gpu_pipeline.py).
-    struct Lane {
-        sf::DevBuf X, qcache, Xq, qkeys, qkeys2, qidx, qidx2, corr, state, d_inits, partials, fz_state, fz_part, fz_cnt, fz_ids, fz_all, df_cnt, df_ids, df_part, df_stat, qtkey, tseg, tile_stats, cov_part, cov_out;
-        hipGraphExec_t graph_exec = nullptr;
-        GraphKey graph_key;
-        std::vector<double> inits_uploaded;
-        uint32_t d_inits_epoch = 0xffffffffu;
-    } other;
-    // Two SOURCE SETS (the members hold one, `other_src` the other): a source set while an alignment of this object is still
-    // unfetched goes into the set that alignment does not read, on the stream of the lane the next alignment will take, so the
-    // next batch's upload / conversion runs beside the alignment in flight instead of behind it (SrcScope).  Per set an event
-    // marks the end of the last alignment that read it; `src_ready` the end of the last upload that ran on a lane's stream.
-    struct SrcSet {
-        sf::DevBuf X0, X0r, stage, d_boxes, d_box_parts, n_dev;
-        int64_t n = 0, n_cap = 0, plane = 0;
-        int batch = 0, nblocks = 0, nblocks_nn = 0, qpl = 1;
-        bool have_source = false, n_on_device = false;
-    } other_src;
-    int src_set = 0;              // which set the members hold
-    hipEvent_t src_used[2] = {nullptr, nullptr}, src_ready = nullptr;
-    bool src_used_rec[2] = {false, false};
-    bool src_ahead = false;       // the members' source was written on a lane's stream (src_ready) and no alignment has been ordered behind it yet
-    // started[l]: recorded on lane l's stream when its latest alignment begins (behind everything it waits for).  A source written
-    // ahead starts its upload behind the START of the alignment on the other lane: two uploads issued back to back -- the host
-    // fetched two results that became ready together -- would otherwise share the link, end together and let both alignments
-    // start together, a lockstep in which nothing overlaps (measured: upload + upload, then alignment + alignment, for good).
-    hipEvent_t started[2] = {nullptr, nullptr};
-    bool started_rec[2] = {false, false};
-    hipEvent_t unmarked_ev = nullptr;
-    bool src_unmarked_use = false; // an alignment read a source set before the lanes' events existed (the per-scan path never creates them): the first source written ahead waits for the context's stream instead
-    // what the lane's last alignment was (sf_icp_fetch_previous reads the OTHER lane's states with the other lane's description)
+    };
+    // what a lane's last alignment was (sf_icp_fetch_previous reads prev()'s states with prev()'s description)
     struct LaneMeta {
         bool valid = false;
         bool cov = false; // it ran with the covariance switch on: cov_out of its lane holds its sf_icp_covariance entries
@@ -3113,17 +3056,81 @@ struct sf_icp {
         std::vector<double> inits;
         int src_set = 0;          // the source set it read, and that set's version then: a redo after a barrier timeout aligns THAT source
         uint64_t src_version = 0;
-    } meta, other_meta;
-    bool prev_ok = false;         // the alignment before the latest one ran on the other lane and has not been overwritten or fetched
+    };
+    // Consecutive asynchronous alignments of the launch list overlap: an alignment's last launches (frozen pairs: fourteen 16 us
+    // kernels on an otherwise idle device) run under the next one's searching launches.  Two LANES take turns; each has its own
+    // stream and its own copy of everything an alignment writes.  cur() = lanes[lane] is the lane of the latest alignment, prev()
+    // the other; taking turns is `lane ^= 1`, so a lane's allocations -- and the graph captured over them -- never move.
+    // Ordering (LaneScope): a lane starts after the context's stream as it stood when the inputs -- source, initial poses,
+    // target -- last changed, and the context's stream waits for every alignment right after it is enqueued, so whatever the caller
+    // enqueues next (a fetch, an upload, a map rebuild) is ordered behind it as before; only back-to-back alignments of unchanged
+    // inputs run side by side.  Same kernels, same data, same results (tests/test_gpu_pipeline.py).
+    struct Lane {
+        sf::DevBuf X;            // SoA: x[B*n], y[B*n], z[B*n] (REF_CPP: the moving points)
+        sf::DevBuf qcache;       // neighbour reuse, two float4 arrays of cache_n entries: (neighbour, its index), (neighbour's normal, E) -- O3D_P2P: the second array holds E alone, as floats
+        sf::DevBuf Xq, qkeys, qkeys2, qidx, qidx2; // cell-ordered copy of X0 and the sort's buffers
+        sf::DevBuf corr;         // float4 [B*n] (REF_CPP): a point's target (x, y, z, sorted position or -1 = dead)
+        sf::DevBuf state, d_inits, partials;
+        sf::DevBuf fz_state, fz_part, fz_cnt, fz_ids, fz_all; // frozen pairs (k_nn_red_fz)
+        sf::DevBuf df_cnt, df_ids, df_part, df_stat;          // deferred search (k_nn_red_df)
+        sf::DevBuf qtkey, tseg, tile_stats; // tile search: tile key of every ordered query; per (tile, scan) segment starts; counters
+        sf::DevBuf cov_part, cov_out;       // pose covariance (sf_cov.hpp): the rows and the result
+        hipGraphExec_t graph_exec = nullptr;
+        GraphKey graph_key;
+        std::vector<double> inits_uploaded; // what d_inits holds (the copy is skipped while nothing changed)
+        uint32_t d_inits_epoch = 0xffffffffu;
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr; // the end of the lane's last alignment, whatever stream it ran on
+        bool used = false;         // `done` has been recorded
+        // started: recorded on the lane's stream when its latest alignment begins (behind everything it waits for).  A source written
+        // ahead starts its upload behind the START of the alignment on the other lane: two uploads issued back to back -- the host
+        // fetched two results that became ready together -- would otherwise share the link, end together and let both alignments
+        // start together, a lockstep in which nothing overlaps (measured: upload + upload, then alignment + alignment, for good).
+        hipEvent_t started = nullptr;
+        bool started_rec = false;
+        LaneMeta meta;
+    } lanes[2];
+    int lane = 0;                 // index of cur()
+    Lane &cur() { return lanes[lane]; }
+    const Lane &cur() const { return lanes[lane]; }
+    Lane &prev() { return lanes[lane ^ 1]; }
+    // Two SOURCE SETS: srcs[src_set] = src() is the set at hand, the one the next alignment reads and sf_icp_set_source* writes.  A
+    // source set while an alignment of this object is still unfetched goes into the OTHER set (`src_set ^= 1` first), the one that
+    // alignment does not read, on the stream of the lane the next alignment will take, so the next batch's upload / conversion runs
+    // beside the alignment in flight instead of behind it (SrcScope).  Per set an event marks the end of the last alignment that
+    // read it; `src_ready` the end of the last upload that ran on a lane's stream.
+    struct SrcSet {
+        sf::DevBuf X0;           // SoA: x[B*n], y[B*n], z[B*n]
+        sf::DevBuf X0r;          // the same points as float4 records (gather source of the query ordering)
+        sf::DevBuf stage;        // persistent upload staging of sf_icp_set_source* (AoS)
+        sf::DevBuf d_boxes, d_box_parts; // ScanBox per scan (motion bound of the reuse certificate, owned-array margin), and the partial boxes of their reduction
+        sf::DevBuf n_dev;        // the point count in device memory (single-scan REF_CPP kernels read it)
+        int64_t n = 0;           // points per scan
+        int64_t n_cap = 0;       // single scan: n rounded up (launch geometry of the REF_CPP kernels)
+        int64_t plane = 0;       // component stride of the SoA arrays X0 / X / Xq
+        int batch = 0;
+        int nblocks = 0;         // workgroups of 256 points covering a scan (REF_CPP kernels, owned-query compaction)
+        int nblocks_nn = 0;      // k_nn_red workgroups per scan = slab rows (256 * qpl queries each)
+        int qpl = 1;             // queries per lane of k_nn_red: 1 up to wide_from points per scan, SF_WIDE_QPL beyond (part of the summation order)
+        bool have_source = false;
+        bool n_on_device = false; // sf_icp_set_source_scan: n is an upper bound, the count itself is in n_dev (single scan, REF_CPP)
+        hipEvent_t used = nullptr; // the end of the last alignment that read this set
+        bool used_rec = false;
+    } srcs[2];
+    int src_set = 0;              // index of src()
+    SrcSet &src() { return srcs[src_set]; }
+    const SrcSet &src() const { return srcs[src_set]; }
+    hipEvent_t src_ready = nullptr;
+    bool src_ahead = false;       // src() was written on a lane's stream (src_ready) and no alignment has been ordered behind it yet
+    hipEvent_t unmarked_ev = nullptr;
+    bool src_unmarked_use = false; // an alignment read a source set before the lanes' events existed (the per-scan path never creates them): the first source written ahead waits for the context's stream instead
+    bool prev_ok = false;         // the alignment before the latest one ran on prev() and has not been overwritten or fetched
     std::vector<IcpState> h_prev;
     sf::DevBuf order_lut;         // k_order_lut_*: histogram (uint32) and key table (uint16) over the walk order of the attached index
     uint64_t order_lut_gen = 0;   // sf_map::generation the table was built for
     int order_lut_shift = 0, order_lut_on = 1; // order_lut_on: SF_ORDER_LUT=0 in the environment switches the table off (A/B runs)
-    int lane = 0;                 // the lane the members hold
     int pipeline = 1;             // sf_icp_set_pipeline: 0 = every alignment on the context's stream
-    hipStream_t lane_stream[2] = {nullptr, nullptr};
-    hipEvent_t lane_done[2] = {nullptr, nullptr}, main_mark = nullptr;
-    bool lane_used[2] = {false, false}; // lane_done[l] has been recorded
+    hipEvent_t main_mark = nullptr;
     bool unfetched = false;       // an alignment has been enqueued since the last fetch (the next one may run beside it)
     bool mark_valid = false;      // main_mark stands for the inputs as described by the fields below
     uint64_t src_version = 0, mark_src_version = 0, mark_map_generation = 0;
@@ -3146,9 +3153,7 @@ struct sf_icp {
     bool fz_from_auto = true;       // learnt from the last fetched alignment (sf_icp_fetch_results); sf_icp_set_freeze_params fixes it
     int fz_fetches = 0;             // fetched alignments since fz_from was last reset to its default (every FZ_PROBE_EVERY-th starts over)
     int fz_step = 0;                // stepping paths: launches since the pass began
-    sf::DevBuf fz_state, fz_part, fz_cnt, fz_ids, fz_all;
     int defer = 1;                  // sf_icp_set_defer_search: the verifying launches of the frozen-pairs schedule list their stragglers for a dense pass (k_nn_red_df)
-    sf::DevBuf df_cnt, df_ids, df_part, df_stat;
     bool df_planned = false;        // the last alignment's launch list held a deferring launch (fz_from as it stood THEN: a fetch may re-learn it)
     int64_t nn_stats_used = 0;
     static constexpr int64_t NN_STATS_CAP = 1024;
@@ -3158,23 +3163,24 @@ struct sf_icp {
     // pose covariance (sf_cov.hpp): read at enqueue, passed to the kernels by value; the rows and the result live per lane
     int cov_on = 0;
     CovArg cov_arg{0.0, 0.0, 0.0, 0.0, 0.0};
-    sf::DevBuf cov_part, cov_out;
     bool prev_cov_ok = false; // sf_icp_fetch_covariance_previous has something to read (set with prev_ok, cleared by its own fetch)
     // tile search (sf_tile.hpp): the searching launches of large batches
     int tile_mode = 0;              // sf_icp_set_tile_search: 0 off, 1 when the batch is large enough to gain (TILE_AUTO_MIN_QUERIES), 2 whenever possible
     bool tile_on = false;           // this alignment's queries are sorted by tile and its searching launches run k_tile_search
     sf::SfTiles tiles{};
-    sf::DevBuf qtkey, tseg, tile_stats; // tile key of every ordered query; per (tile, scan) segment starts; counters
 };
 
 namespace {
 
+using Lane = sf_icp::Lane;
+using SrcSet = sf_icp::SrcSet;
 float *soa(sf::DevBuf &b, int64_t total, int axis) { return b.as<float>() + (size_t)axis * (size_t)total; }
 // the query arrays this alignment walks: the cell-ordered copy or the scans as given
-const float *src(sf_icp *icp, int axis)
+const float *queries(sf_icp *icp, int axis)
 {
-    if (icp->shard) return soa(icp->Xq, icp->own_total, axis); // compact, cell-ordered owned queries (shard_build)
-    return soa(icp->ordered ? icp->Xq : icp->X0, icp->plane, axis);
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
+    if (icp->shard) return soa(ln.Xq, icp->own_total, axis); // compact, cell-ordered owned queries (shard_build)
+    return soa(icp->ordered ? ln.Xq : ss.X0, ss.plane, axis);
 }
 
 int fused_capacity(sf_icp *icp, int mode, bool robust = false); // (workgroups the single-launch kernels keep resident; defined with them)
@@ -3187,15 +3193,18 @@ RobustArg robust_arg(const sf_icp *icp) { return RobustArg{icp->robust_kind, icp
 // scans, 20 iterations: 1 scan in flight +1.5 % (break-even), 2: +8 %, 4: +32 %, 32: +65 %
 constexpr int64_t ORDER_AUTO_MIN_QUERIES = 300000;
 
-// key = position of the query's cell in the walk order (order_cell), shifted down to the 20 bits the sort takes
-int order_key_shift(const SfGrid &g)
+// the cells the walk order (order_cell) spans, and the bits that number them
+struct OrderSpan { uint64_t cells; int bits; };
+OrderSpan order_span(const SfGrid &g)
 {
     const uint64_t ny_pad = ((uint64_t)g.dim[1] + ORDER_YBLK - 1) / ORDER_YBLK * ORDER_YBLK; // order_cell pads y to whole blocks
-    const uint64_t ncell = (uint64_t)g.dim[0] * ny_pad * (uint64_t)g.dim[2];
-    int cbits = 0;
-    while (cbits < 63 && (1ull << cbits) < ncell) ++cbits;
-    return std::max(0, cbits - sf::ORD_KEY_BITS);
+    OrderSpan sp{(uint64_t)g.dim[0] * ny_pad * (uint64_t)g.dim[2], 0};
+    while (sp.bits < 63 && (1ull << sp.bits) < sp.cells) ++sp.bits;
+    return sp;
 }
+
+// key = position of the query's cell in the walk order, shifted down to the bits the sort takes (sf::ORD_KEY_BITS)
+int order_key_shift(const SfGrid &g) { return std::max(0, order_span(g).bits - sf::ORD_KEY_BITS); }
 
 // neighbour reuse starts empty at every alignment (a zero bound certifies nothing)
 int reuse_reset(sf_icp *icp, int64_t count)
@@ -3204,7 +3213,7 @@ int reuse_reset(sf_icp *icp, int64_t count)
     const size_t c = (size_t)std::max<int64_t>(count, 1);
     // nothing is cleared: a scan's entries count only once IcpState::cache_live says they have been written (every lane
     // writes its entry in the first launch after a start or a rebuild of the owned arrays)
-    SF_TRY(icp->qcache.reserve(sizeof(float4) * 2 * c));
+    SF_TRY(icp->cur().qcache.reserve(sizeof(float4) * 2 * c));
     icp->cache_n = (int64_t)c;
     return SF_OK;
 }
@@ -3253,18 +3262,17 @@ bool tile_plan(const SfGrid &g, sf::SfTiles *out)
 
 bool tile_wanted(const sf_icp *icp, int mode)
 {
+    const SrcSet &ss = icp->src();
     // (k_red_cached sums unit weights: under a robust kernel the searching launches stay with k_nn_red_rob)
     if (icp->tile_mode == 0 || robust_on(icp, mode) || icp->shard || icp->map->window.kind != 0 || (mode != SF_ICP_P2PLANE && mode != SF_ICP_O3D_P2P)) return false;
-    if (icp->qpl == 1) return false; // scans the single-launch kernels can take keep their summation order (and their launch list)
-    return icp->tile_mode == 2 || icp->n * icp->batch >= TILE_AUTO_MIN_QUERIES;
+    if (ss.qpl == 1) return false; // scans the single-launch kernels can take keep their summation order (and their launch list)
+    return icp->tile_mode == 2 || ss.n * ss.batch >= TILE_AUTO_MIN_QUERIES;
 }
 
 // launches of an alignment that run tile by tile: those in which nearly every query searches -- all of them with the neighbour
 // reuse off, the first VERIFY_FROM_SEARCH with it on (afterwards whole waves certify and k_nn_red streams the cache)
 bool tile_launch(const sf_icp *icp, int k) { return icp->tile_on && (!icp->reuse || k < VERIFY_FROM_SEARCH); }
 
-// the segmented stable bucket sort of sf_order.hpp: nseg segments (uniform: nseg scans of icp->n queries; sharded: the
-// owned-query candidates of each scan, seg_off / src_idx on the device), `longest` = the longest segment
 // The key table of the attached index (k_order_lut_*), (re)built when the index has changed.  Enqueued on the context's stream
 // BEFORE an alignment takes a lane: the lanes order themselves behind the context's stream whenever the target changes
 // (LaneScope), so both see the finished table.
@@ -3274,12 +3282,9 @@ int order_lut_prepare(sf_icp *icp)
     if (!icp->order_lut_on || !icp->map || !icp->map->built) return SF_OK;
     const SfGrid &g = icp->map->grid;
     if (g.n <= 0 || (icp->order_lut.p && icp->order_lut_gen == icp->map->generation)) return SF_OK;
-    const uint64_t ny_pad = ((uint64_t)g.dim[1] + ORDER_YBLK - 1) / ORDER_YBLK * ORDER_YBLK;
-    const uint64_t span = (uint64_t)g.dim[0] * ny_pad * (uint64_t)g.dim[2];
-    int cbits = 0;
-    while (cbits < 63 && (1ull << cbits) < span) ++cbits;
-    icp->order_lut_shift = std::max(0, cbits - ORDER_LUT_LOG2);
-    const int nbins = (int)(span >> icp->order_lut_shift) + 1;
+    const OrderSpan sp = order_span(g);
+    icp->order_lut_shift = std::max(0, sp.bits - ORDER_LUT_LOG2);
+    const int nbins = (int)(sp.cells >> icp->order_lut_shift) + 1;
     SF_TRY(icp->order_lut.reserve(sizeof(uint32_t) * (size_t)ORDER_LUT_BINS + sizeof(uint16_t) * (size_t)ORDER_LUT_BINS));
     uint32_t *hist = icp->order_lut.as<uint32_t>();
     uint16_t *lut = reinterpret_cast<uint16_t *>(hist + ORDER_LUT_BINS);
@@ -3292,21 +3297,22 @@ int order_lut_prepare(sf_icp *icp)
     return SF_OK;
 }
 
+// the segmented stable bucket sort of sf_order.hpp: nseg segments (uniform: nseg scans of n queries; sharded: the
+// owned-query candidates of each scan, seg_off / src_idx on the device), `longest` = the longest segment
 int run_order_sort(sf_icp *icp, int nseg, int64_t longest, int64_t total, const uint32_t *seg_off, const uint32_t *src_idx)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     const SfGrid &g = icp->map->grid;
-    const int64_t all = icp->n * icp->batch;
     if (seg_off) icp->tile_on = false; // (the sharded path's owned-query arrays keep the cell order)
     sf::OrderSrc src;
     src.src_idx = src_idx;
     src.seg_off = seg_off;
-    src.n = (int)icp->n;
+    src.n = (int)ss.n;
     src.tiles = (int)std::max<int64_t>(1, sf::div_up(longest, sf::ORD_TILE));
     CellKeyFn kf;
     kf.g = g;
-    kf.x = soa(icp->X0, icp->plane, 0); kf.y = soa(icp->X0, icp->plane, 1); kf.z = soa(icp->X0, icp->plane, 2);
-    (void)all;
-    kf.st = icp->state.as<IcpState>();
+    kf.x = soa(ss.X0, ss.plane, 0); kf.y = soa(ss.X0, ss.plane, 1); kf.z = soa(ss.X0, ss.plane, 2);
+    kf.st = ln.state.as<IcpState>();
     kf.shift = order_key_shift(g);
     kf.lut = nullptr;
     kf.lut_shift = 0;
@@ -3315,12 +3321,12 @@ int run_order_sort(sf_icp *icp, int nseg, int64_t longest, int64_t total, const 
         kf.lut_shift = icp->order_lut_shift;
     }
     const size_t cap = (size_t)std::max<int64_t>(total, 1);
-    SF_TRY(icp->Xq.reserve(sizeof(float) * 3 * std::max(cap, (size_t)(seg_off ? 0 : icp->plane))));
-    SF_TRY(icp->qkeys.reserve(sizeof(uint16_t) * cap));                                                      // bucket key of every element
-    SF_TRY(icp->qkeys2.reserve(sizeof(uint32_t) * (size_t)nseg * (size_t)(src.tiles + 1) * sf::ORD_BINS));  // per-tile bucket counts / starts
-    SF_TRY(icp->qidx.reserve(sizeof(uint32_t) * cap));                                                       // ordered query ids
-    uint16_t *keys = icp->qkeys.as<uint16_t>();
-    uint32_t *counts = icp->qkeys2.as<uint32_t>(), *ordered = icp->qidx.as<uint32_t>();
+    SF_TRY(ln.Xq.reserve(sizeof(float) * 3 * std::max(cap, (size_t)(seg_off ? 0 : ss.plane))));
+    SF_TRY(ln.qkeys.reserve(sizeof(uint16_t) * cap));                                                      // bucket key of every element
+    SF_TRY(ln.qkeys2.reserve(sizeof(uint32_t) * (size_t)nseg * (size_t)(src.tiles + 1) * sf::ORD_BINS));  // per-tile bucket counts / starts
+    SF_TRY(ln.qidx.reserve(sizeof(uint32_t) * cap));                                                       // ordered query ids
+    uint16_t *keys = ln.qkeys.as<uint16_t>();
+    uint32_t *counts = ln.qkeys2.as<uint32_t>(), *ordered = ln.qidx.as<uint32_t>();
     hipStream_t s = icp->ctx->stream;
     src.nseg = nseg;
     const dim3 grid(sf::order_grid(src.tiles, nseg)), blk(sf::ORD_BLK);
@@ -3328,12 +3334,12 @@ int run_order_sort(sf_icp *icp, int nseg, int64_t longest, int64_t total, const 
         TileKeyFn tk;
         tk.g = g; tk.tl = icp->tiles;
         tk.x = kf.x; tk.y = kf.y; tk.z = kf.z;
-        tk.st = kf.st; tk.n = (int)icp->n;
+        tk.st = kf.st; tk.n = (int)ss.n;
         const bool two = icp->tiles.ntiles > sf::ORD_BINS;
         uint32_t *first = ordered;
         if (two) {
-            SF_TRY(icp->qidx2.reserve(sizeof(uint32_t) * cap));
-            first = icp->qidx2.as<uint32_t>();
+            SF_TRY(ln.qidx2.reserve(sizeof(uint32_t) * cap));
+            first = ln.qidx2.as<uint32_t>();
         }
         tk.digit = 0;
         hipLaunchKernelGGL(k_order_hist_tile, grid, blk, 0, s, src, tk, keys, counts);
@@ -3352,27 +3358,27 @@ int run_order_sort(sf_icp *icp, int nseg, int64_t longest, int64_t total, const 
         hipLaunchKernelGGL(sf::k_order_scan, dim3((unsigned)nseg), dim3(sf::ORD_BINS), 0, s, counts, src.tiles);
         hipLaunchKernelGGL(k_order_scatter, grid, blk, 0, s, src, keys, counts, ordered);
     }
-    const int64_t qplane = seg_off ? total : icp->plane; // sharded: the compact arrays have their own length
+    const int64_t qplane = seg_off ? total : ss.plane; // sharded: the compact arrays have their own length
     if (seg_off) {
-        hipLaunchKernelGGL(k_order_gather, dim3(nblk(total, GATHER_TILE)), dim3(256), 0, s, icp->X0r.as<float4>(), ordered, total, 0, 0, 0, soa(icp->Xq, qplane, 0),
-                           soa(icp->Xq, qplane, 1), soa(icp->Xq, qplane, 2));
+        hipLaunchKernelGGL(k_order_gather, dim3(nblk(total, GATHER_TILE)), dim3(256), 0, s, ss.X0r.as<float4>(), ordered, total, 0, 0, 0, soa(ln.Xq, qplane, 0),
+                           soa(ln.Xq, qplane, 1), soa(ln.Xq, qplane, 2));
     } else {
-        const int gt = (int)std::max<int64_t>(1, sf::div_up(icp->n, GATHER_TILE));
-        hipLaunchKernelGGL(k_order_gather, dim3(sf::order_grid(gt, nseg)), dim3(256), 0, s, icp->X0r.as<float4>(), ordered, total, (int)icp->n, gt, nseg,
-                           soa(icp->Xq, qplane, 0), soa(icp->Xq, qplane, 1), soa(icp->Xq, qplane, 2));
+        const int gt = (int)std::max<int64_t>(1, sf::div_up(ss.n, GATHER_TILE));
+        hipLaunchKernelGGL(k_order_gather, dim3(sf::order_grid(gt, nseg)), dim3(256), 0, s, ss.X0r.as<float4>(), ordered, total, (int)ss.n, gt, nseg,
+                           soa(ln.Xq, qplane, 0), soa(ln.Xq, qplane, 1), soa(ln.Xq, qplane, 2));
     }
     if (icp->tile_on) { // where each tile's queries start in every scan's ordered array
         TileKeyFn tk;
         tk.g = g; tk.tl = icp->tiles;
-        tk.x = soa(icp->Xq, qplane, 0); tk.y = soa(icp->Xq, qplane, 1); tk.z = soa(icp->Xq, qplane, 2);
-        tk.st = kf.st; tk.n = (int)icp->n; tk.digit = 0;
+        tk.x = soa(ln.Xq, qplane, 0); tk.y = soa(ln.Xq, qplane, 1); tk.z = soa(ln.Xq, qplane, 2);
+        tk.st = kf.st; tk.n = (int)ss.n; tk.digit = 0;
         const int64_t rows = (int64_t)icp->tiles.ntiles + 1;
-        SF_TRY(icp->qtkey.reserve(sizeof(uint32_t) * cap));
-        SF_TRY(icp->tseg.reserve(sizeof(uint32_t) * (size_t)rows * (size_t)nseg));
-        SF_TRY(icp->tile_stats.reserve(sizeof(unsigned long long) * TILE_STATS));
-        SF_HIP(hipMemsetAsync(icp->tile_stats.p, 0, sizeof(unsigned long long) * TILE_STATS, s));
-        hipLaunchKernelGGL(k_tile_keys, dim3(nblk(total)), dim3(256), 0, s, tk, total, icp->qtkey.as<uint32_t>());
-        hipLaunchKernelGGL(k_tile_starts, dim3(nblk(rows * nseg)), dim3(256), 0, s, icp->qtkey.as<uint32_t>(), (int)icp->n, nseg, icp->tiles.ntiles, icp->tseg.as<uint32_t>());
+        SF_TRY(ln.qtkey.reserve(sizeof(uint32_t) * cap));
+        SF_TRY(ln.tseg.reserve(sizeof(uint32_t) * (size_t)rows * (size_t)nseg));
+        SF_TRY(ln.tile_stats.reserve(sizeof(unsigned long long) * TILE_STATS));
+        SF_HIP(hipMemsetAsync(ln.tile_stats.p, 0, sizeof(unsigned long long) * TILE_STATS, s));
+        hipLaunchKernelGGL(k_tile_keys, dim3(nblk(total)), dim3(256), 0, s, tk, total, ln.qtkey.as<uint32_t>());
+        hipLaunchKernelGGL(k_tile_starts, dim3(nblk(rows * nseg)), dim3(256), 0, s, ln.qtkey.as<uint32_t>(), (int)ss.n, nseg, icp->tiles.ntiles, ln.tseg.as<uint32_t>());
     }
     SF_HIP(hipGetLastError());
     return SF_OK;
@@ -3380,43 +3386,27 @@ int run_order_sort(sf_icp *icp, int nseg, int64_t longest, int64_t total, const 
 
 int order_queries(sf_icp *icp, int mode)
 {
-    const int64_t total = icp->n * icp->batch;
+    SrcSet &ss = icp->src();
+    const int64_t total = ss.n * ss.batch;
     const bool want = icp->order == SF_ORDER_CELL || (icp->order == SF_ORDER_AUTO && total >= ORDER_AUTO_MIN_QUERIES);
     icp->ordered = false;
     icp->tile_on = false;
-    if (!want || total == 0 || icp->map->grid.n == 0 || icp->n_on_device) return SF_OK; // (a count left on the device: the tail of the arrays is not data)
+    if (!want || total == 0 || icp->map->grid.n == 0 || ss.n_on_device) return SF_OK; // (a count left on the device: the tail of the arrays is not data)
     icp->tile_on = tile_wanted(icp, mode) && tile_plan(icp->map->grid, &icp->tiles);
-    SF_TRY(run_order_sort(icp, icp->batch, icp->n, total, nullptr, nullptr));
+    SF_TRY(run_order_sort(icp, ss.batch, ss.n, total, nullptr, nullptr));
     icp->ordered = true;
     return SF_OK;
-}
-
-void raw_swap(sf::DevBuf &a, sf::DevBuf &b) // the allocations change places, epochs included (a captured graph keeps pointing at ITS lane's buffers)
-{
-    std::swap(a.p, b.p);
-    std::swap(a.cap, b.cap);
-    std::swap(a.epoch, b.epoch);
-}
-
-void src_flip(sf_icp *icp)
-{
-    sf_icp::SrcSet &o = icp->other_src;
-    raw_swap(icp->X0, o.X0); raw_swap(icp->X0r, o.X0r); raw_swap(icp->stage, o.stage); raw_swap(icp->d_boxes, o.d_boxes); raw_swap(icp->d_box_parts, o.d_box_parts);
-    raw_swap(icp->n_dev, o.n_dev);
-    std::swap(icp->n, o.n); std::swap(icp->n_cap, o.n_cap); std::swap(icp->plane, o.plane);
-    std::swap(icp->batch, o.batch); std::swap(icp->nblocks, o.nblocks); std::swap(icp->nblocks_nn, o.nblocks_nn); std::swap(icp->qpl, o.qpl);
-    std::swap(icp->have_source, o.have_source); std::swap(icp->n_on_device, o.n_on_device);
-    icp->src_set ^= 1;
 }
 
 // the lanes' streams and every event of the pipeline, once
 int ensure_lanes(sf_icp *icp)
 {
     for (int l = 0; l < 2; ++l) {
-        if (!icp->lane_stream[l]) SF_HIP(hipStreamCreateWithFlags(&icp->lane_stream[l], hipStreamNonBlocking));
-        if (!icp->lane_done[l]) SF_HIP(hipEventCreateWithFlags(&icp->lane_done[l], hipEventDisableTiming));
-        if (!icp->src_used[l]) SF_HIP(hipEventCreateWithFlags(&icp->src_used[l], hipEventDisableTiming));
-        if (!icp->started[l]) SF_HIP(hipEventCreateWithFlags(&icp->started[l], hipEventDisableTiming));
+        Lane &ln = icp->lanes[l];
+        if (!ln.stream) SF_HIP(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+        if (!ln.done) SF_HIP(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
+        if (!icp->srcs[l].used) SF_HIP(hipEventCreateWithFlags(&icp->srcs[l].used, hipEventDisableTiming));
+        if (!ln.started) SF_HIP(hipEventCreateWithFlags(&ln.started, hipEventDisableTiming));
     }
     if (!icp->main_mark) SF_HIP(hipEventCreateWithFlags(&icp->main_mark, hipEventDisableTiming));
     if (!icp->src_ready) SF_HIP(hipEventCreateWithFlags(&icp->src_ready, hipEventDisableTiming));
@@ -3424,40 +3414,45 @@ int ensure_lanes(sf_icp *icp)
     return SF_OK;
 }
 
+// src() was written on a lane's stream and nothing has been ordered behind that upload yet: stream `s` waits for it
+int wait_src_ahead(sf_icp *icp, hipStream_t s)
+{
+    if (!icp->src_ahead) return SF_OK;
+    SF_HIP(hipStreamWaitEvent(s, icp->src_ready, 0));
+    icp->src_ahead = false;
+    return SF_OK;
+}
+
 // RAII around a call that writes the source.  While an alignment of this object is unfetched (and the lanes are on) the new
-// source goes into the OTHER source set, on the stream of the lane the next alignment will take: it waits for the last
-// alignment that read that set, not for the alignment in flight.  Otherwise: the set at hand on the context's stream, as before.
+// source goes into the OTHER source set -- the constructor flips src_set, so src() is the set being written from then on -- on
+// the stream of prev(), the lane the next alignment will take: it waits for the last alignment that read that set, not for the
+// alignment in flight.  Otherwise: the set at hand on the context's stream, as before.
 struct SrcScope {
     sf_icp *icp;
     hipStream_t main = nullptr;
     bool ahead = false;
     uint64_t version0 = 0;
     int rc = SF_OK;
-    SrcScope(sf_icp *i, bool allowed) : icp(i)
+    SrcScope(sf_icp *i, bool allowed) : icp(i), main(i->ctx->stream), version0(i->src_version)
     {
-        main = icp->ctx->stream;
-        version0 = icp->src_version;
         static const bool ahead_on = []() { const char *e = std::getenv("SF_SRC_AHEAD"); return !e || std::atoi(e) != 0; }(); // (A/B switch)
         const bool go = ahead_on && allowed && icp->pipeline != 0 && icp->unfetched && !icp->shard && !icp->profiling;
-        if (!go) {
-            // the set at hand on the context's stream: behind an upload that went to a lane's stream, if there was one
-            if (icp->src_ahead) {
-                if (hipStreamWaitEvent(main, icp->src_ready, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-                icp->src_ahead = false;
-            }
+        if (!go) { // the set at hand on the context's stream: behind an upload that went to a lane's stream, if there was one
+            rc = wait_src_ahead(icp, main);
             return;
         }
         rc = ensure_lanes(icp);
         if (rc != SF_OK) return;
-        if (!icp->src_ahead) src_flip(icp); // (a second source before any alignment: the same set, the same stream, again)
-        hipStream_t ls = icp->lane_stream[icp->lane ^ 1];
+        if (!icp->src_ahead) icp->src_set ^= 1; // (a second source before any alignment: the same set, the same stream, again)
+        const SrcSet &ss = icp->src();
+        hipStream_t ls = icp->prev().stream;
         if (icp->src_unmarked_use) { // readers that left no event: everything the context's stream holds
             if (hipEventRecord(icp->unmarked_ev, main) != hipSuccess || hipStreamWaitEvent(ls, icp->unmarked_ev, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
             icp->src_unmarked_use = false;
         }
-        if (icp->src_used_rec[icp->src_set] && hipStreamWaitEvent(ls, icp->src_used[icp->src_set], 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
+        if (ss.used_rec && hipStreamWaitEvent(ls, ss.used, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
         static const bool stagger_on = []() { const char *e = std::getenv("SF_UPLOAD_STAGGER"); return !e || std::atoi(e) != 0; }(); // (A/B switch)
-        if (stagger_on && icp->started_rec[icp->lane] && hipStreamWaitEvent(ls, icp->started[icp->lane], 0) != hipSuccess) { rc = SF_ERR_HIP; return; } // see sf_icp::started
+        if (stagger_on && icp->cur().started_rec && hipStreamWaitEvent(ls, icp->cur().started, 0) != hipSuccess) { rc = SF_ERR_HIP; return; } // see Lane::started
         icp->ctx->stream = ls;
         ahead = true;
     }
@@ -3472,25 +3467,31 @@ struct SrcScope {
     }
 };
 
+// what an alignment of the source at hand writes per scan, in the lane at hand
+int lane_reserve(sf_icp *icp)
+{
+    Lane &ln = icp->cur(); const SrcSet &ss = icp->src();
+    const int batch = std::max(ss.batch, 1);
+    SF_TRY(ln.state.reserve(sizeof(IcpState) * (size_t)batch));
+    SF_TRY(ln.d_inits.reserve(sizeof(double) * 16 * (size_t)batch));
+    SF_TRY(ln.partials.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(ss.nblocks, 1) * (size_t)batch));
+    return SF_OK;
+}
+
 // outputs = false (a source written ahead of an alignment in flight): the lane's output buffers are left to lane_reserve at the next enqueue
 int icp_alloc(sf_icp *icp, int64_t n, int batch, bool outputs = true)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     const int64_t total = n * batch;
     // plane = distance between the x, y and z components of the SoA arrays: rounded up and never shrinking, so that the
     // component pointers a captured launch list holds survive scans of slightly different sizes
-    icp->plane = std::max<int64_t>(icp->plane, sf::div_up(std::max<int64_t>(total, 1), 4096) * 4096);
-    SF_TRY(icp->X0.reserve(sizeof(float) * 3 * (size_t)icp->plane));
-    SF_TRY(icp->X0r.reserve(sizeof(float4) * (size_t)icp->plane));
-    if (outputs) {
-        const auto e0 = icp->state.epoch;
-        SF_TRY(icp->state.reserve(sizeof(IcpState) * (size_t)batch));
-        if (icp->state.epoch != e0) icp->meta.valid = false; // (the states of this lane's last alignment went with the old allocation: sf_icp_fetch_previous has nothing to read)
-        SF_TRY(icp->d_inits.reserve(sizeof(double) * 16 * (size_t)batch));
-    }
+    ss.plane = std::max<int64_t>(ss.plane, sf::div_up(std::max<int64_t>(total, 1), 4096) * 4096);
+    SF_TRY(ss.X0.reserve(sizeof(float) * 3 * (size_t)ss.plane));
+    SF_TRY(ss.X0r.reserve(sizeof(float4) * (size_t)ss.plane));
     // single scan: workgroups for the point count rounded up to 4096 (the kernels bound themselves by the count in
     // device memory), so the launch geometry -- and with it a captured graph -- is shared by scans of similar size
-    icp->n_cap = batch == 1 ? sf::div_up(std::max<int64_t>(n, 1), 4096) * 4096 : n;
-    icp->nblocks = (int)std::max<int64_t>(1, sf::div_up(icp->n_cap, BLK));
+    ss.n_cap = batch == 1 ? sf::div_up(std::max<int64_t>(n, 1), 4096) * 4096 : n;
+    ss.nblocks = (int)std::max<int64_t>(1, sf::div_up(ss.n_cap, BLK));
     // Two queries per lane are part of the summation order, so the choice must not depend on which path runs an alignment: above
     // wide_from always; between WIDE_AUTO_POINTS and wide_from when no single-launch kernel could take the batch anyway (more
     // rows than any of them keeps resident) -- a 64-ring sensor's 130 k points in a batch then run wide and may freeze.
@@ -3499,10 +3500,15 @@ int icp_alloc(sf_icp *icp, int64_t n, int batch, bool outputs = true)
         const int64_t cap = std::max(fused_capacity(icp, SF_ICP_O3D_P2P), fused_capacity(icp, SF_ICP_P2PLANE));
         wide = sf::div_up(n, BLK) * (int64_t)batch > cap;
     }
-    icp->qpl = wide ? SF_WIDE_QPL : 1;
-    icp->nblocks_nn = (int)std::max<int64_t>(1, sf::div_up(n, BLK * icp->qpl));
+    ss.qpl = wide ? SF_WIDE_QPL : 1;
+    ss.nblocks_nn = (int)std::max<int64_t>(1, sf::div_up(n, BLK * ss.qpl));
+    // (set before the outputs: lane_reserve sizes them from the set, so after a failed reservation the set says n and batch as it says n_cap / nblocks / qpl; batch >= 1 from every caller, so its max(.., 1) is idle)
+    ss.n = n;
+    ss.batch = batch;
     if (outputs) {
-        SF_TRY(icp->partials.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)icp->nblocks * (size_t)batch));
+        const auto e0 = ln.state.epoch;
+        SF_TRY(lane_reserve(icp));
+        if (ln.state.epoch != e0) ln.meta.valid = false; // (the states of this lane's last alignment went with the old allocation: sf_icp_fetch_previous has nothing to read)
         SF_TRY(icp->xchg_own.reserve(sizeof(double) * REC_STRIDE * (size_t)batch));
     }
     if (icp->inits.size() != (size_t)batch * 16) { // (by the priors' own size, not by the batch of whichever source set was at hand)
@@ -3510,32 +3516,31 @@ int icp_alloc(sf_icp *icp, int64_t n, int batch, bool outputs = true)
         for (int b = 0; b < batch; ++b)
             for (int d = 0; d < 4; ++d) icp->inits[(size_t)b * 16 + 5 * d] = 1.0;
     }
-    icp->n = n;
-    icp->batch = batch;
     icp->h_state.resize((size_t)batch);
     return SF_OK;
 }
 
 int icp_set_source_device_aos(sf_icp *icp, const float *d_aos, int64_t n, int batch, bool ahead = false)
 {
+    SrcSet &ss = icp->src();
     SF_TRY(icp_alloc(icp, n, batch, !ahead));
-    icp->n_on_device = false;
+    ss.n_on_device = false;
     const int64_t total = n * batch;
     if (total > 0)
-        hipLaunchKernelGGL(k_soa_from_aos, dim3(nblk(total)), dim3(256), 0, icp->ctx->stream, d_aos, total, soa(icp->X0, icp->plane, 0), soa(icp->X0, icp->plane, 1),
-                           soa(icp->X0, icp->plane, 2), icp->X0r.as<float4>());
-    SF_TRY(icp->n_dev.reserve(sizeof(int)));
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, icp->ctx->stream, icp->n_dev.as<int>(), (int)n);
+        hipLaunchKernelGGL(k_soa_from_aos, dim3(nblk(total)), dim3(256), 0, icp->ctx->stream, d_aos, total, soa(ss.X0, ss.plane, 0), soa(ss.X0, ss.plane, 1),
+                           soa(ss.X0, ss.plane, 2), ss.X0r.as<float4>());
+    SF_TRY(ss.n_dev.reserve(sizeof(int)));
+    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, icp->ctx->stream, ss.n_dev.as<int>(), (int)n);
     SF_HIP(hipGetLastError());
     // bounding box of every scan on its own, reduced on the device and left there (no host synchronisation per scan): what moves
     // a scan's points is bounded by ITS box (a batch of 10 m scans spread over a 100 m map has a 100 m box and every rotation a
     // 50 m lever arm).  (The box of the whole batch, which rounds 1-3 also formed here, had no reader left.)
-    SF_TRY(icp->d_boxes.reserve(sizeof(ScanBox) * (size_t)std::max(batch, 1)));
-    SF_TRY(icp->d_box_parts.reserve(sizeof(ScanBox) * BOX_PARTS * (size_t)std::max(batch, 1)));
-    hipLaunchKernelGGL(k_scan_boxes_partial, dim3(BOX_PARTS, (unsigned)std::max(batch, 1)), dim3(256), 0, icp->ctx->stream, soa(icp->X0, icp->plane, 0), soa(icp->X0, icp->plane, 1),
-                       soa(icp->X0, icp->plane, 2), (int)n, icp->d_box_parts.as<ScanBox>());
-    hipLaunchKernelGGL(k_scan_boxes_final, dim3(nblk(std::max(batch, 1), 64)), dim3(64), 0, icp->ctx->stream, icp->d_box_parts.as<ScanBox>(), std::max(batch, 1), icp->d_boxes.as<ScanBox>());
-    icp->have_source = true;
+    SF_TRY(ss.d_boxes.reserve(sizeof(ScanBox) * (size_t)std::max(batch, 1)));
+    SF_TRY(ss.d_box_parts.reserve(sizeof(ScanBox) * BOX_PARTS * (size_t)std::max(batch, 1)));
+    hipLaunchKernelGGL(k_scan_boxes_partial, dim3(BOX_PARTS, (unsigned)std::max(batch, 1)), dim3(256), 0, icp->ctx->stream, soa(ss.X0, ss.plane, 0), soa(ss.X0, ss.plane, 1),
+                       soa(ss.X0, ss.plane, 2), (int)n, ss.d_box_parts.as<ScanBox>());
+    hipLaunchKernelGGL(k_scan_boxes_final, dim3(nblk(std::max(batch, 1), 64)), dim3(64), 0, icp->ctx->stream, ss.d_box_parts.as<ScanBox>(), std::max(batch, 1), ss.d_boxes.as<ScanBox>());
+    ss.have_source = true;
     icp->src_version += 1;
     return SF_OK;
 }
@@ -3580,18 +3585,19 @@ void prof_collect(sf_icp *icp)
 
 sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
 {
+    const Lane &ln = icp->cur(); const SrcSet &ss = icp->src();
     sf_icp::GraphKey k;
-    k.mode = mode; k.iters = icp->prm.num_iters; k.batch = icp->batch; k.window = icp->map->window.kind; k.ordered = (int)icp->ordered | ((int)icp->tile_on << 1); k.reuse = (int)icp->reuse | (icp->freeze << 1) | (icp->fz_from << 3) | (icp->defer << 16);
-    k.n = (mode == SF_ICP_REF_CPP && icp->batch == 1) ? -icp->n_cap : icp->n; // REF_CPP, one scan: any count of the same capacity replays
+    k.mode = mode; k.iters = icp->prm.num_iters; k.batch = ss.batch; k.window = icp->map->window.kind; k.ordered = (int)icp->ordered | ((int)icp->tile_on << 1); k.reuse = (int)icp->reuse | (icp->freeze << 1) | (icp->fz_from << 3) | (icp->defer << 16);
+    k.n = (mode == SF_ICP_REF_CPP && ss.batch == 1) ? -ss.n_cap : ss.n; // REF_CPP, one scan: any count of the same capacity replays
     k.map = (const void *)icp->map;
     k.map_generation = icp->map->generation;
     k.robust_kind = robust_on(icp, mode) ? icp->robust_kind : SF_ROBUST_NONE; k.robust_k = robust_on(icp, mode) ? icp->robust_k : 0.0; // (passed by value to the robust kernels)
     k.cov_on = icp->cov_on;
     if (icp->cov_on) { const double cp[5] = {icp->cov_arg.sensor_sigma, icp->cov_arg.thr_t, icp->cov_arg.thr_r, icp->cov_arg.infl_t, icp->cov_arg.infl_r}; std::memcpy(k.cov_prm, cp, sizeof(cp)); }
     k.max_corr = icp->prm.max_corr; k.accept = icp->prm.accept; k.eps = icp->prm.eps + icp->fz_prm.guard_scale * 1.0e-3f + icp->fz_prm.guard_min + icp->fz_prm.guard_max + (float)icp->fz_prm.max_tries; // (the freeze parameters travel by value too)
-    const sf::DevBuf *bufs[] = {&icp->X0, &icp->X0r, &icp->X, &icp->Xq, &icp->qcache, &icp->corr, &icp->state, &icp->partials, &icp->d_box, &icp->d_boxes, &icp->n_dev,
-                                &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &icp->fz_state, &icp->fz_part, &icp->fz_cnt, &icp->fz_ids, &icp->fz_all, &icp->df_cnt, &icp->df_ids, &icp->df_part, &icp->df_stat, &icp->tseg, &icp->tile_stats, &icp->cov_part, &icp->cov_out};
-    k.epochs = (uint64_t)icp->plane;
+    const sf::DevBuf *bufs[] = {&ss.X0, &ss.X0r, &ln.X, &ln.Xq, &ln.qcache, &ln.corr, &ln.state, &ln.partials, &icp->d_box, &ss.d_boxes, &ss.n_dev,
+                                &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &ln.fz_state, &ln.fz_part, &ln.fz_cnt, &ln.fz_ids, &ln.fz_all, &ln.df_cnt, &ln.df_ids, &ln.df_part, &ln.df_stat, &ln.tseg, &ln.tile_stats, &ln.cov_part, &ln.cov_out};
+    k.epochs = (uint64_t)ss.plane;
     for (const sf::DevBuf *b : bufs) k.epochs = (k.epochs * 1000003ull + b->epoch) * 1000003ull + (uint64_t)(uintptr_t)b->p; // (the address too: the two source sets take turns under one lane's graph)
     return k;
 }
@@ -3603,12 +3609,13 @@ float o3d_thr(const sf_icp *icp) { return (float)((double)icp->prm.max_corr * (d
 template <int MODE>
 void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    const int nb = sharded ? (one_per_lane ? icp->own_nblocks * icp->qpl : icp->own_nblocks) : (one_per_lane ? icp->nblocks : icp->nblocks_nn);
-    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)icp->batch), blk(BLK); // see the XCD mapping in k_nn_red
-    const float *x = src(icp, 0), *y = src(icp, 1), *z = src(icp, 2);
-    const IcpState *st = icp->state.as<IcpState>();
-    double *part = icp->partials.as<double>();
+    const int nb = sharded ? (one_per_lane ? icp->own_nblocks * ss.qpl : icp->own_nblocks) : (one_per_lane ? ss.nblocks : ss.nblocks_nn);
+    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), blk(BLK); // see the XCD mapping in k_nn_red
+    const float *x = queries(icp, 0), *y = queries(icp, 1), *z = queries(icp, 2);
+    const IcpState *st = ln.state.as<IcpState>();
+    double *part = ln.partials.as<double>();
     const float thr = o3d_thr(icp);
     hipStream_t s = icp->ctx->stream;
     ProfScope ps(icp);
@@ -3618,9 +3625,9 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
     if (MODE == 2 && robust_on(icp, MODE)) {
         const RobustArg rk = robust_arg(icp);
 #define SF_LAUNCH_NNRED_ROB(W, S, QQ)                                                                                                                         \
-    hipLaunchKernelGGL((k_nn_red_rob<W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)icp->n, st, thr, icp->xlo, icp->xhi, part, nb, \
-                       icp->own_off.as<uint32_t>(), icp->reuse ? icp->qcache.as<float4>() : nullptr, icp->cache_n, stats, rk)
-        const bool q1 = icp->qpl == 1 || one_per_lane;
+    hipLaunchKernelGGL((k_nn_red_rob<W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb, \
+                       icp->own_off.as<uint32_t>(), icp->reuse ? ln.qcache.as<float4>() : nullptr, icp->cache_n, stats, rk)
+        const bool q1 = ss.qpl == 1 || one_per_lane;
         if (win && sharded) { if (q1) SF_LAUNCH_NNRED_ROB(true, true, 1); else SF_LAUNCH_NNRED_ROB(true, true, SF_WIDE_QPL); }
         else if (win) { if (q1) SF_LAUNCH_NNRED_ROB(true, false, 1); else SF_LAUNCH_NNRED_ROB(true, false, SF_WIDE_QPL); }
         else if (sharded) { if (q1) SF_LAUNCH_NNRED_ROB(false, true, 1); else SF_LAUNCH_NNRED_ROB(false, true, SF_WIDE_QPL); }
@@ -3629,11 +3636,11 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
         return;
     }
 #define SF_LAUNCH_NNRED_Q(W, S, QQ)                                                                                                                              \
-    hipLaunchKernelGGL((k_nn_red<MODE, W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)icp->n, st, thr, icp->xlo, icp->xhi, part, nb, \
-                       icp->own_off.as<uint32_t>(), icp->reuse ? icp->qcache.as<float4>() : nullptr, icp->cache_n, stats)
+    hipLaunchKernelGGL((k_nn_red<MODE, W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb, \
+                       icp->own_off.as<uint32_t>(), icp->reuse ? ln.qcache.as<float4>() : nullptr, icp->cache_n, stats)
 #define SF_LAUNCH_NNRED(W, S)                                  \
     do {                                                       \
-        if (icp->qpl == 1 || one_per_lane) SF_LAUNCH_NNRED_Q(W, S, 1); \
+        if (ss.qpl == 1 || one_per_lane) SF_LAUNCH_NNRED_Q(W, S, 1); \
         else SF_LAUNCH_NNRED_Q(W, S, SF_WIDE_QPL);             \
     } while (0)
     if (win && sharded) SF_LAUNCH_NNRED(true, true);
@@ -3649,72 +3656,77 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
 template <int MODE>
 void launch_tile_search(sf_icp *icp, bool one_per_lane)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    const int nb = one_per_lane ? icp->nblocks : icp->nblocks_nn;
-    const float *x = src(icp, 0), *y = src(icp, 1), *z = src(icp, 2);
-    const IcpState *st = icp->state.as<IcpState>();
+    const int nb = one_per_lane ? ss.nblocks : ss.nblocks_nn;
+    const float *x = queries(icp, 0), *y = queries(icp, 1), *z = queries(icp, 2);
+    const IcpState *st = ln.state.as<IcpState>();
     const float thr = o3d_thr(icp);
     hipStream_t s = icp->ctx->stream;
     ProfScope ps(icp);
-    unsigned long long *stats = icp->profiling ? icp->tile_stats.as<unsigned long long>() : nullptr;
+    unsigned long long *stats = icp->profiling ? ln.tile_stats.as<unsigned long long>() : nullptr;
     if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) icp->nn_stats_used++; // (keeps the per-launch statistics slots of k_nn_red aligned with the launch list)
     const unsigned tgrid = (unsigned)((icp->tiles.ntiles + 7) & ~7);
-    hipLaunchKernelGGL((k_tile_search<MODE>), dim3(tgrid), dim3(sf::TILE_BLK), 0, s, m->grid, icp->tiles, x, y, z, (int)icp->n, icp->batch, st, thr, icp->tseg.as<uint32_t>(),
-                       icp->qcache.as<float4>(), icp->cache_n, (int)icp->reuse, stats);
-    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)icp->batch), blk(BLK);
-    if (icp->qpl == 1 || one_per_lane)
-        hipLaunchKernelGGL((k_red_cached<MODE, 1>), grid, blk, 0, s, x, y, z, (int)icp->n, st, thr, icp->partials.as<double>(), nb, icp->qcache.as<float4>(), icp->cache_n);
+    hipLaunchKernelGGL((k_tile_search<MODE>), dim3(tgrid), dim3(sf::TILE_BLK), 0, s, m->grid, icp->tiles, x, y, z, (int)ss.n, ss.batch, st, thr, ln.tseg.as<uint32_t>(),
+                       ln.qcache.as<float4>(), icp->cache_n, (int)icp->reuse, stats);
+    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), blk(BLK);
+    if (ss.qpl == 1 || one_per_lane)
+        hipLaunchKernelGGL((k_red_cached<MODE, 1>), grid, blk, 0, s, x, y, z, (int)ss.n, st, thr, ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n);
     else
-        hipLaunchKernelGGL((k_red_cached<MODE, SF_WIDE_QPL>), grid, blk, 0, s, x, y, z, (int)icp->n, st, thr, icp->partials.as<double>(), nb, icp->qcache.as<float4>(), icp->cache_n);
+        hipLaunchKernelGGL((k_red_cached<MODE, SF_WIDE_QPL>), grid, blk, 0, s, x, y, z, (int)ss.n, st, thr, ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n);
 }
 
 // frozen pairs: P2PLANE launch list of wide scans with the neighbour reuse on, whole map; sharded: each rank freezes its own
 // owned queries (what it contributes to the all-reduced record is the same sum either way)
 bool freeze_on(const sf_icp *icp, int mode)
 {
+    const SrcSet &ss = icp->src();
     // a frozen launch costs one wave's chain of round trips (16 us) + the solve, whatever the batch: for a small batch a verifying
     // launch is cheaper than that (200 k-point scans, ms per alignment without / with: one scan 0.39 / 0.45, four 0.77 / 0.75,
     // eight 1.07 / 0.97, sixteen 1.68 / 1.42)
-    const int64_t queries = icp->shard ? icp->own_total : icp->n * icp->batch;
-    const bool wanted = icp->freeze == 2 || (icp->freeze == 1 && queries >= FREEZE_AUTO_MIN_QUERIES);
-    return mode == SF_ICP_P2PLANE && wanted && !robust_on(icp, mode) && icp->reuse && icp->qpl == SF_WIDE_QPL && icp->map->window.kind == 0 && icp->prm.num_iters > icp->fz_from + 1 &&
+    const int64_t nq = icp->shard ? icp->own_total : ss.n * ss.batch;
+    const bool wanted = icp->freeze == 2 || (icp->freeze == 1 && nq >= FREEZE_AUTO_MIN_QUERIES);
+    return mode == SF_ICP_P2PLANE && wanted && !robust_on(icp, mode) && icp->reuse && ss.qpl == SF_WIDE_QPL && icp->map->window.kind == 0 && icp->prm.num_iters > icp->fz_from + 1 &&
            icp->fz_from >= VERIFY_FROM_SEARCH;
 }
 
 int freeze_alloc(sf_icp *icp)
 {
-    const size_t rows = (size_t)icp->batch * (size_t)std::max(icp->nblocks_nn, icp->shard ? icp->own_nblocks : 0);
-    SF_TRY(icp->fz_state.reserve(sizeof(FreezeState) * (size_t)icp->batch));
-    SF_TRY(icp->fz_part.reserve(sizeof(double) * FZ_NMOM * rows));
-    SF_TRY(icp->fz_cnt.reserve(sizeof(uint32_t) * rows));
-    SF_TRY(icp->fz_ids.reserve(sizeof(uint16_t) * FZ_CAP * rows));
-    SF_TRY(icp->fz_all.reserve(sizeof(uint32_t) * FZ_CAP * rows));
-    SF_TRY(icp->df_cnt.reserve(sizeof(uint8_t) * (BLK / 64) * rows));
-    SF_TRY(icp->df_ids.reserve(sizeof(uint16_t) * (BLK / 64) * DF_WCAP * rows));
-    SF_TRY(icp->df_part.reserve(sizeof(double) * REC_STRIDE * FZ_FEW * (size_t)icp->batch));
-    SF_TRY(icp->df_stat.reserve(sizeof(uint32_t) * 2));
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
+    const size_t rows = (size_t)ss.batch * (size_t)std::max(ss.nblocks_nn, icp->shard ? icp->own_nblocks : 0);
+    SF_TRY(ln.fz_state.reserve(sizeof(FreezeState) * (size_t)ss.batch));
+    SF_TRY(ln.fz_part.reserve(sizeof(double) * FZ_NMOM * rows));
+    SF_TRY(ln.fz_cnt.reserve(sizeof(uint32_t) * rows));
+    SF_TRY(ln.fz_ids.reserve(sizeof(uint16_t) * FZ_CAP * rows));
+    SF_TRY(ln.fz_all.reserve(sizeof(uint32_t) * FZ_CAP * rows));
+    SF_TRY(ln.df_cnt.reserve(sizeof(uint8_t) * (BLK / 64) * rows));
+    SF_TRY(ln.df_ids.reserve(sizeof(uint16_t) * (BLK / 64) * DF_WCAP * rows));
+    SF_TRY(ln.df_part.reserve(sizeof(double) * REC_STRIDE * FZ_FEW * (size_t)ss.batch));
+    SF_TRY(ln.df_stat.reserve(sizeof(uint32_t) * 2));
     return SF_OK;
 }
 
 FreezeBufs freeze_bufs(sf_icp *icp, bool on, bool deferred = false)
 {
+    Lane &ln = icp->cur();
     FreezeBufs fb;
-    fb.fz = on ? icp->fz_state.as<FreezeState>() : nullptr;
-    fb.mom_part = icp->fz_part.as<double>();
-    fb.act_cnt = icp->fz_cnt.as<uint32_t>();
-    fb.act_ids = icp->fz_ids.as<uint16_t>();
-    fb.act_all = icp->fz_all.as<uint32_t>();
-    fb.df_part = deferred ? icp->df_part.as<double>() : nullptr;
+    fb.fz = on ? ln.fz_state.as<FreezeState>() : nullptr;
+    fb.mom_part = ln.fz_part.as<double>();
+    fb.act_cnt = ln.fz_cnt.as<uint32_t>();
+    fb.act_ids = ln.fz_ids.as<uint16_t>();
+    fb.act_all = ln.fz_all.as<uint32_t>();
+    fb.df_part = deferred ? ln.df_part.as<double>() : nullptr;
     return fb;
 }
 
 DeferBufs defer_bufs(sf_icp *icp)
 {
+    Lane &ln = icp->cur();
     DeferBufs d;
-    d.cnt = icp->df_cnt.as<uint8_t>();
-    d.ids = icp->df_ids.as<uint16_t>();
-    d.part = icp->df_part.as<double>();
-    d.stat = icp->df_stat.as<uint32_t>();
+    d.cnt = ln.df_cnt.as<uint8_t>();
+    d.ids = ln.df_ids.as<uint16_t>();
+    d.part = ln.df_part.as<double>();
+    d.stat = ln.df_stat.as<uint32_t>();
     return d;
 }
 
@@ -3731,49 +3743,52 @@ bool defer_planned(const sf_icp *icp, int mode) { return defer_now(icp, mode, ic
 
 void launch_nn_deferred(sf_icp *icp, uint32_t *stats)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    hipLaunchKernelGGL((k_nn_deferred<SF_WIDE_QPL>), dim3((unsigned)FZ_FEW, (unsigned)icp->batch), dim3(BLK), 0, icp->ctx->stream, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2),
-                       (int)icp->n, icp->state.as<IcpState>(), o3d_thr(icp), icp->nblocks_nn, icp->qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
+    hipLaunchKernelGGL((k_nn_deferred<SF_WIDE_QPL>), dim3((unsigned)FZ_FEW, (unsigned)ss.batch), dim3(BLK), 0, icp->ctx->stream, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2),
+                       (int)ss.n, ln.state.as<IcpState>(), o3d_thr(icp), ss.nblocks_nn, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
 }
 
 // launch_nn_red<2> of a wide scan's two-queries-per-lane launch with the deferral, and its dense pass: one profiled launch
 void launch_nn_red_df(sf_icp *icp)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    const int nb = icp->nblocks_nn;
-    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)icp->batch), blk(BLK);
+    const int nb = ss.nblocks_nn;
+    const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), blk(BLK);
     ProfScope ps(icp);
     uint32_t *stats = nullptr;
     if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + 2 * NN_STATS_SHARDS * icp->nn_stats_used++;
-    hipLaunchKernelGGL((k_nn_red_df<SF_WIDE_QPL>), grid, blk, 0, icp->ctx->stream, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, icp->state.as<IcpState>(),
-                       o3d_thr(icp), icp->partials.as<double>(), nb, icp->qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
+    hipLaunchKernelGGL((k_nn_red_df<SF_WIDE_QPL>), grid, blk, 0, icp->ctx->stream, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(),
+                       o3d_thr(icp), ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
     launch_nn_deferred(icp, stats);
 }
 
 // few: FZ_FEW workgroups per scan (k_nn_red_fz_few: the launches after the first chance to freeze)
 void launch_nn_red_fz(sf_icp *icp, bool sharded, bool few)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    const int nb = sharded ? icp->own_nblocks : icp->nblocks_nn;
-    const dim3 grid_full((unsigned)((nb + 7) & ~7), (unsigned)icp->batch), grid_few((unsigned)FZ_FEW, (unsigned)icp->batch), blk(BLK);
+    const int nb = sharded ? icp->own_nblocks : ss.nblocks_nn;
+    const dim3 grid_full((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), grid_few((unsigned)FZ_FEW, (unsigned)ss.batch), blk(BLK);
     ProfScope ps(icp);
     FzArgs A;
-    A.X0x = src(icp, 0); A.X0y = src(icp, 1); A.X0z = src(icp, 2);
-    A.n = (int)icp->n;
-    A.st = icp->state.as<IcpState>();
+    A.X0x = queries(icp, 0); A.X0y = queries(icp, 1); A.X0z = queries(icp, 2);
+    A.n = (int)ss.n;
+    A.st = ln.state.as<IcpState>();
     A.thr = o3d_thr(icp); A.xlo = icp->xlo; A.xhi = icp->xhi;
-    A.partials = icp->partials.as<double>();
+    A.partials = ln.partials.as<double>();
     A.nblocks = nb;
     A.own_off = icp->own_off.as<uint32_t>();
-    A.qcache = icp->qcache.as<float4>();
+    A.qcache = ln.qcache.as<float4>();
     A.cache_n = icp->cache_n;
     A.stats = nullptr;
     if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) A.stats = icp->nn_stats.as<uint32_t>() + 2 * NN_STATS_SHARDS * icp->nn_stats_used++;
-    A.fz = icp->fz_state.as<FreezeState>();
-    A.mom_part = icp->fz_part.as<double>();
-    A.act_cnt = icp->fz_cnt.as<uint32_t>();
-    A.act_ids = icp->fz_ids.as<uint16_t>();
-    A.act_all = icp->fz_all.as<uint32_t>();
+    A.fz = ln.fz_state.as<FreezeState>();
+    A.mom_part = ln.fz_part.as<double>();
+    A.act_cnt = ln.fz_cnt.as<uint32_t>();
+    A.act_ids = ln.fz_ids.as<uint16_t>();
+    A.act_all = ln.fz_all.as<uint32_t>();
     hipStream_t s = icp->ctx->stream;
     if (few) {
         if (sharded) hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, true>), grid_few, blk, 0, s, m->grid, m->window, A);
@@ -3789,10 +3804,11 @@ bool freeze_nn_now(const sf_icp *icp, int mode) { return freeze_on(icp, mode) &&
 bool freeze_solve_now(const sf_icp *icp, int mode) { return freeze_on(icp, mode) && icp->fz_step + 1 >= icp->fz_from; }
 int freeze_start_pass(sf_icp *icp, int mode)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     icp->fz_step = 0;
     if (!freeze_on(icp, mode)) return SF_OK;
     SF_TRY(freeze_alloc(icp));
-    hipLaunchKernelGGL(k_fz_init, dim3(nblk(icp->batch, 64)), dim3(64), 0, icp->ctx->stream, icp->fz_state.as<FreezeState>(), icp->batch, icp->df_stat.as<uint32_t>());
+    hipLaunchKernelGGL(k_fz_init, dim3(nblk(ss.batch, 64)), dim3(64), 0, icp->ctx->stream, ln.fz_state.as<FreezeState>(), ss.batch, ln.df_stat.as<uint32_t>());
     return SF_OK;
 }
 
@@ -3801,16 +3817,17 @@ int freeze_start_pass(sf_icp *icp, int mode)
 // batches travel in the kernel arguments; larger ones through a pinned staging buffer, and only when they changed.
 int launch_state_init(sf_icp *icp)
 {
+    Lane &ln = icp->cur();
     hipStream_t s = icp->ctx->stream;
-    const int B = icp->batch;
+    const int B = icp->src().batch;
     InitArgs args;
     if (B <= INIT_ARGS_MAX) {
         std::memcpy(args.T, icp->inits.data(), sizeof(double) * 16 * (size_t)B);
-        hipLaunchKernelGGL(k_state_init, dim3(1), dim3(64), 0, s, icp->state.as<IcpState>(), (const double *)nullptr, args, B);
+        hipLaunchKernelGGL(k_state_init, dim3(1), dim3(64), 0, s, ln.state.as<IcpState>(), (const double *)nullptr, args, B);
         return SF_OK;
     }
     const size_t bytes = sizeof(double) * 16 * (size_t)B;
-    if (icp->inits_uploaded != icp->inits || icp->d_inits_epoch != icp->d_inits.epoch) {
+    if (ln.inits_uploaded != icp->inits || ln.d_inits_epoch != ln.d_inits.epoch) {
         if (icp->h_inits_cap < bytes) {
             if (icp->inits_ev_pending) { SF_HIP(hipEventSynchronize(icp->inits_ev)); icp->inits_ev_pending = false; }
             if (icp->h_inits) { hipError_t e = hipHostFree(icp->h_inits); (void)e; icp->h_inits = nullptr; }
@@ -3820,13 +3837,13 @@ int launch_state_init(sf_icp *icp)
         if (!icp->inits_ev) SF_HIP(hipEventCreateWithFlags(&icp->inits_ev, hipEventDisableTiming));
         if (icp->inits_ev_pending) SF_HIP(hipEventSynchronize(icp->inits_ev)); // the previous copy has left the staging buffer
         std::memcpy(icp->h_inits, icp->inits.data(), bytes);
-        SF_HIP(hipMemcpyAsync(icp->d_inits.p, icp->h_inits, bytes, hipMemcpyHostToDevice, s));
+        SF_HIP(hipMemcpyAsync(ln.d_inits.p, icp->h_inits, bytes, hipMemcpyHostToDevice, s));
         SF_HIP(hipEventRecord(icp->inits_ev, s));
         icp->inits_ev_pending = true;
-        icp->inits_uploaded = icp->inits;
-        icp->d_inits_epoch = icp->d_inits.epoch;
+        ln.inits_uploaded = icp->inits;
+        ln.d_inits_epoch = ln.d_inits.epoch;
     }
-    hipLaunchKernelGGL(k_state_init, dim3(nblk(B, 64)), dim3(64), 0, s, icp->state.as<IcpState>(), icp->d_inits.as<double>(), args, B);
+    hipLaunchKernelGGL(k_state_init, dim3(nblk(B, 64)), dim3(64), 0, s, ln.state.as<IcpState>(), ln.d_inits.as<double>(), args, B);
     return SF_OK;
 }
 
@@ -3836,30 +3853,32 @@ int launch_state_init(sf_icp *icp)
 // single scan's count from device memory there, as its own kernels do -- a captured graph bakes neither in).
 int cov_alloc(sf_icp *icp)
 {
-    const size_t B = (size_t)std::max(icp->batch, 1);
-    SF_TRY(icp->cov_part.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(icp->nblocks, 1) * B));
-    SF_TRY(icp->cov_out.reserve(sizeof(sf_icp_covariance) * B));
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
+    const size_t B = (size_t)std::max(ss.batch, 1);
+    SF_TRY(ln.cov_part.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(ss.nblocks, 1) * B));
+    SF_TRY(ln.cov_out.reserve(sizeof(sf_icp_covariance) * B));
     return SF_OK;
 }
 
 template <int MODE>
 void launch_cov(sf_icp *icp, bool in_list)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
     hipStream_t s = icp->ctx->stream;
-    const int nb = icp->nblocks, B = icp->batch;
+    const int nb = ss.nblocks, B = ss.batch;
     const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)B), blk(BLK);
     const bool win = m->window.kind != 0;
     const float thr = MODE == 0 ? icp->prm.max_corr : o3d_thr(icp); // REF_CPP: the squared-vs-unsquared quirk, icp_point_to_point.cpp:70
     const SfWindow *wdev = (MODE == 0 && win && in_list) ? m->d_window.as<SfWindow>() : nullptr;
-    const int *nl = (MODE == 0 && B == 1) ? icp->n_dev.as<int>() : nullptr;
+    const int *nl = (MODE == 0 && B == 1) ? ss.n_dev.as<int>() : nullptr;
     const RobustArg rk = robust_on(icp, MODE) ? robust_arg(icp) : RobustArg{SF_ROBUST_NONE, 0.0};
-    double *part = icp->cov_part.as<double>();
+    double *part = ln.cov_part.as<double>();
     if (win)
-        hipLaunchKernelGGL((k_nn_cov<MODE, true>), grid, blk, 0, s, m->grid, m->window, wdev, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, nl, icp->state.as<IcpState>(), thr, part, nb, rk);
+        hipLaunchKernelGGL((k_nn_cov<MODE, true>), grid, blk, 0, s, m->grid, m->window, wdev, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), thr, part, nb, rk);
     else
-        hipLaunchKernelGGL((k_nn_cov<MODE, false>), grid, blk, 0, s, m->grid, m->window, wdev, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, nl, icp->state.as<IcpState>(), thr, part, nb, rk);
-    hipLaunchKernelGGL(k_cov_solve<MODE>, dim3((unsigned)B), dim3(COV_SBLK), 0, s, part, nb, icp->cov_arg, icp->cov_out.as<sf_icp_covariance>());
+        hipLaunchKernelGGL((k_nn_cov<MODE, false>), grid, blk, 0, s, m->grid, m->window, wdev, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), thr, part, nb, rk);
+    hipLaunchKernelGGL(k_cov_solve<MODE>, dim3((unsigned)B), dim3(COV_SBLK), 0, s, part, nb, icp->cov_arg, ln.cov_out.as<sf_icp_covariance>());
 }
 
 void enqueue_cov(sf_icp *icp, int mode, bool in_list)
@@ -3872,27 +3891,28 @@ void enqueue_cov(sf_icp *icp, int mode, bool in_list)
 // enqueue the whole alignment (no host synchronisation)
 int enqueue_align(sf_icp *icp, int mode)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
     hipStream_t s = icp->ctx->stream;
-    IcpState *st = icp->state.as<IcpState>();
-    double *part = icp->partials.as<double>();
+    IcpState *st = ln.state.as<IcpState>();
+    double *part = ln.partials.as<double>();
     const int K = icp->prm.num_iters;
-    const int B = icp->batch;
-    const int n = (int)icp->n;
+    const int B = ss.batch;
+    const int n = (int)ss.n;
     if (mode == SF_ICP_O3D_P2P) {
         for (int k = 0; k <= K; ++k) {
             if (tile_launch(icp, k)) launch_tile_search<1>(icp, false);
             else launch_nn_red<1>(icp);
-            hipLaunchKernelGGL(k_reduce_solve<1>, dim3(B), dim3(RBLK), 0, s, st, part, icp->nblocks_nn, n, k, K, icp->d_boxes.as<ScanBox>());
+            hipLaunchKernelGGL(k_reduce_solve<1>, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks_nn, n, k, K, ss.d_boxes.as<ScanBox>());
         }
     } else if (mode == SF_ICP_P2PLANE) {
         const bool fz = freeze_on(icp, mode);
         if (fz) { // (buffers: freeze_alloc, before any capture)
-            hipLaunchKernelGGL(k_fz_init, dim3(nblk(B, 64)), dim3(64), 0, s, icp->fz_state.as<FreezeState>(), B, icp->df_stat.as<uint32_t>());
+            hipLaunchKernelGGL(k_fz_init, dim3(nblk(B, 64)), dim3(64), 0, s, ln.fz_state.as<FreezeState>(), B, ln.df_stat.as<uint32_t>());
         }
         // wide scans: the first launches -- nearly every query searches -- run one query per lane (fewer registers: measured
         // 929, 804, 508, 414 against 954, 836, 539, 439 us); from the launch in which waves start to certify whole, two
-        const bool wide = icp->qpl > 1 && !icp->shard;
+        const bool wide = ss.qpl > 1 && !icp->shard;
         for (int k = 0; k < K; ++k) {
             const bool q1 = wide && k < VERIFY_FROM_SEARCH; // (the same schedule with the reuse off: it is part of the summation order, and reuse on == off bit for bit)
             const bool df = !q1 && defer_now(icp, mode, k);
@@ -3901,33 +3921,33 @@ int enqueue_align(sf_icp *icp, int mode)
             else if (df) launch_nn_red_df(icp);
             else launch_nn_red<2>(icp, false, q1);
             if (fz && k + 1 >= icp->fz_from) // (after a one-query-per-lane launch too: an ordinary record of twice as many rows, and the solve may ask for the freeze launch)
-                hipLaunchKernelGGL(k_reduce_solve_fz, dim3(B), dim3(RBLK), 0, s, st, part, q1 ? icp->nblocks : icp->nblocks_nn, n, K, icp->d_boxes.as<ScanBox>(), freeze_bufs(icp, true, df),
+                hipLaunchKernelGGL(k_reduce_solve_fz, dim3(B), dim3(RBLK), 0, s, st, part, q1 ? ss.nblocks : ss.nblocks_nn, n, K, ss.d_boxes.as<ScanBox>(), freeze_bufs(icp, true, df),
                                    icp->fz_prm, (int)(k + 2 < K));
             else if (q1)
-                hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, icp->nblocks, n, k, K, icp->d_boxes.as<ScanBox>());
+                hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks, n, k, K, ss.d_boxes.as<ScanBox>());
             else
-                hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, icp->nblocks_nn, n, k, K, icp->d_boxes.as<ScanBox>());
+                hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks_nn, n, k, K, ss.d_boxes.as<ScanBox>());
         }
     } else {
-        SF_TRY(icp->X.reserve(sizeof(float) * 3 * (size_t)std::max<int64_t>(icp->plane, 1)));
-        SF_TRY(icp->corr.reserve(sizeof(float4) * (size_t)std::max<int64_t>(icp->plane, 1)));
-        float *Xx = soa(icp->X, icp->plane, 0), *Xy = soa(icp->X, icp->plane, 1), *Xz = soa(icp->X, icp->plane, 2);
-        float4 *corr = icp->corr.as<float4>();
-        const dim3 gpts((unsigned)icp->nblocks, (unsigned)B), gred((unsigned)icp->nblocks, (unsigned)B);
-        const int *nl = B == 1 ? icp->n_dev.as<int>() : nullptr; // single scan: the count comes from the device (see k_ref_init)
+        SF_TRY(ln.X.reserve(sizeof(float) * 3 * (size_t)std::max<int64_t>(ss.plane, 1)));
+        SF_TRY(ln.corr.reserve(sizeof(float4) * (size_t)std::max<int64_t>(ss.plane, 1)));
+        float *Xx = soa(ln.X, ss.plane, 0), *Xy = soa(ln.X, ss.plane, 1), *Xz = soa(ln.X, ss.plane, 2);
+        float4 *corr = ln.corr.as<float4>();
+        const dim3 gpts((unsigned)ss.nblocks, (unsigned)B), gred((unsigned)ss.nblocks, (unsigned)B);
+        const int *nl = B == 1 ? ss.n_dev.as<int>() : nullptr; // single scan: the count comes from the device (see k_ref_init)
         const bool win = m->window.kind != 0;
         const float thr = icp->prm.max_corr; // squared-vs-unsquared quirk, icp_point_to_point.cpp:70
-        const dim3 gnn((unsigned)((icp->nblocks + 7) & ~7), (unsigned)B); // see the XCD mapping in k_ref_nn
+        const dim3 gnn((unsigned)((ss.nblocks + 7) & ~7), (unsigned)B); // see the XCD mapping in k_ref_nn
         auto nn = [&](int force) {
             ProfScope ps(icp);
-            if (win) hipLaunchKernelGGL(k_ref_nn<true>, gnn, dim3(BLK), 0, s, m->grid, m->d_window.as<SfWindow>(), Xx, Xy, Xz, n, nl, st, thr, force, corr, icp->nblocks);
-            else hipLaunchKernelGGL(k_ref_nn<false>, gnn, dim3(BLK), 0, s, m->grid, (const SfWindow *)nullptr, Xx, Xy, Xz, n, nl, st, thr, force, corr, icp->nblocks);
+            if (win) hipLaunchKernelGGL(k_ref_nn<true>, gnn, dim3(BLK), 0, s, m->grid, m->d_window.as<SfWindow>(), Xx, Xy, Xz, n, nl, st, thr, force, corr, ss.nblocks);
+            else hipLaunchKernelGGL(k_ref_nn<false>, gnn, dim3(BLK), 0, s, m->grid, (const SfWindow *)nullptr, Xx, Xy, Xz, n, nl, st, thr, force, corr, ss.nblocks);
         };
         auto red = [&](int apply, int only_research) {
-            hipLaunchKernelGGL(k_ref_red, gred, dim3(BLK), 0, s, Xx, Xy, Xz, n, nl, st, corr, apply, only_research, part, icp->nblocks);
+            hipLaunchKernelGGL(k_ref_red, gred, dim3(BLK), 0, s, Xx, Xy, Xz, n, nl, st, corr, apply, only_research, part, ss.nblocks);
         };
-        auto decide = [&](int phase) { hipLaunchKernelGGL(k_ref_decide, dim3(B), dim3(RBLK), 0, s, st, part, icp->nblocks, icp->prm, phase); };
-        hipLaunchKernelGGL(k_ref_init, gpts, dim3(BLK), 0, s, src(icp, 0), src(icp, 1), src(icp, 2), n, nl, st, Xx, Xy, Xz, corr); // the cell-ordered copy when ordering is on
+        auto decide = [&](int phase) { hipLaunchKernelGGL(k_ref_decide, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks, icp->prm, phase); };
+        hipLaunchKernelGGL(k_ref_init, gpts, dim3(BLK), 0, s, queries(icp, 0), queries(icp, 1), queries(icp, 2), n, nl, st, Xx, Xy, Xz, corr); // the cell-ordered copy when ordering is on
         nn(1);
         red(0, 0);
         decide(0);
@@ -4005,17 +4025,19 @@ bool fused_reserve(sf_icp *icp, double share)
 
 bool fused_eligible(sf_icp *icp, int mode)
 {
-    const int64_t rows = mode == SF_ICP_REF_CPP ? icp->nblocks : icp->nblocks_nn;
+    SrcSet &ss = icp->src();
+    const int64_t rows = mode == SF_ICP_REF_CPP ? ss.nblocks : ss.nblocks_nn;
     // the single-launch kernels keep one point per lane (rows of 256): wide scans (qpl > 1) are not theirs
     const int64_t cap = fused_capacity(icp, mode, robust_on(icp, mode));
-    if (!(icp->fused && !icp->profiling && !icp->shard && (mode == SF_ICP_REF_CPP || icp->qpl == 1) && cap > 0 && rows * icp->batch <= cap)) return false;
+    if (!(icp->fused && !icp->profiling && !icp->shard && (mode == SF_ICP_REF_CPP || ss.qpl == 1) && cap > 0 && rows * ss.batch <= cap)) return false;
     fused_release(icp); // the previous alignment of this object has been fetched or superseded
-    return fused_reserve(icp, (double)(rows * icp->batch) / (double)cap);
+    return fused_reserve(icp, (double)(rows * ss.batch) / (double)cap);
 }
 
 template <int MODE>
 void launch_icp_fused(sf_icp *icp, dim3 grid)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
     hipStream_t s = icp->ctx->stream;
     const float thr = o3d_thr(icp);
@@ -4023,8 +4045,8 @@ void launch_icp_fused(sf_icp *icp, dim3 grid)
     if (MODE == 2 && robust_on(icp, MODE)) {
         const RobustArg rk = robust_arg(icp);
 #define SF_LAUNCH_ICPF_ROB(W, R)                                                                                                                                        \
-    hipLaunchKernelGGL((k_icp_fused_rob<W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, icp->state.as<IcpState>(), thr, \
-                       icp->prm.num_iters, icp->partials.as<double>(), icp->nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin, rk)
+    hipLaunchKernelGGL((k_icp_fused_rob<W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(), thr, \
+                       icp->prm.num_iters, ln.partials.as<double>(), ss.nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin, rk)
         if (win && icp->reuse) SF_LAUNCH_ICPF_ROB(true, true);
         else if (win) SF_LAUNCH_ICPF_ROB(true, false);
         else if (icp->reuse) SF_LAUNCH_ICPF_ROB(false, true);
@@ -4033,8 +4055,8 @@ void launch_icp_fused(sf_icp *icp, dim3 grid)
         return;
     }
 #define SF_LAUNCH_ICPF(W, R)                                                                                                                                               \
-    hipLaunchKernelGGL((k_icp_fused<MODE, W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, icp->state.as<IcpState>(), thr, \
-                       icp->prm.num_iters, icp->partials.as<double>(), icp->nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin)
+    hipLaunchKernelGGL((k_icp_fused<MODE, W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(), thr, \
+                       icp->prm.num_iters, ln.partials.as<double>(), ss.nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin)
     if (win && icp->reuse) SF_LAUNCH_ICPF(true, true);
     else if (win) SF_LAUNCH_ICPF(true, false);
     else if (icp->reuse) SF_LAUNCH_ICPF(false, true);
@@ -4044,9 +4066,10 @@ void launch_icp_fused(sf_icp *icp, dim3 grid)
 
 int launch_fused(sf_icp *icp, int mode)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
     hipStream_t s = icp->ctx->stream;
-    const int B = icp->batch;
+    const int B = ss.batch;
     const size_t need = sizeof(uint32_t) * 2 * (size_t)B;
     if (icp->bar.cap < need) {
         SF_TRY(icp->bar.reserve(need));
@@ -4058,25 +4081,25 @@ int launch_fused(sf_icp *icp, int mode)
         icp->h_pin_cap = (size_t)B;
     }
     // two slabs per scan (see k_ref_fused)
-    SF_TRY(icp->partials.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(icp->nblocks, icp->nblocks_nn) * (size_t)B * 2));
+    SF_TRY(ln.partials.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(ss.nblocks, ss.nblocks_nn) * (size_t)B * 2));
     if (mode != SF_ICP_REF_CPP) {
-        const dim3 grid_nn((unsigned)icp->nblocks_nn, (unsigned)B);
+        const dim3 grid_nn((unsigned)ss.nblocks_nn, (unsigned)B);
         if (mode == SF_ICP_O3D_P2P) launch_icp_fused<1>(icp, grid_nn);
         else launch_icp_fused<2>(icp, grid_nn);
         SF_HIP(hipGetLastError());
         icp->fused_launches += 1;
         return SF_OK;
     }
-    const dim3 grid((unsigned)icp->nblocks, (unsigned)B);
+    const dim3 grid((unsigned)ss.nblocks, (unsigned)B);
     const float thr = icp->prm.max_corr; // squared-vs-unsquared quirk, icp_point_to_point.cpp:70
     IcpParams prm = icp->prm;
-    const int *nl = icp->n_on_device ? icp->n_dev.as<int>() : nullptr;
+    const int *nl = ss.n_on_device ? ss.n_dev.as<int>() : nullptr;
     if (m->window.kind != 0)
-        hipLaunchKernelGGL(k_ref_fused<true>, grid, dim3(BLK), 0, s, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, nl, icp->state.as<IcpState>(), prm, thr,
-                           icp->partials.as<double>(), icp->nblocks, icp->bar.as<uint32_t>(), icp->h_pin);
+        hipLaunchKernelGGL(k_ref_fused<true>, grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), prm, thr,
+                           ln.partials.as<double>(), ss.nblocks, icp->bar.as<uint32_t>(), icp->h_pin);
     else
-        hipLaunchKernelGGL(k_ref_fused<false>, grid, dim3(BLK), 0, s, m->grid, m->window, src(icp, 0), src(icp, 1), src(icp, 2), (int)icp->n, nl, icp->state.as<IcpState>(), prm, thr,
-                           icp->partials.as<double>(), icp->nblocks, icp->bar.as<uint32_t>(), icp->h_pin);
+        hipLaunchKernelGGL(k_ref_fused<false>, grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), prm, thr,
+                           ln.partials.as<double>(), ss.nblocks, icp->bar.as<uint32_t>(), icp->h_pin);
     SF_HIP(hipGetLastError());
     icp->fused_launches += 1;
     return SF_OK;
@@ -4106,10 +4129,10 @@ int check_ready(sf_icp *icp, int mode)
 {
     SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
     SF_CHECK(mode >= 0 && mode <= 2, SF_ERR_INVALID, "unknown mode %d", mode);
-    SF_CHECK(icp->have_source, SF_ERR_STATE, "no source cloud set");
+    SF_CHECK(icp->src().have_source, SF_ERR_STATE, "no source cloud set");
     SF_CHECK(icp->map && icp->map->built, SF_ERR_STATE, "no target set");
     SF_CHECK(mode != SF_ICP_P2PLANE || icp->map->has_normals, SF_ERR_STATE, "point-to-plane needs map normals (sf_map_estimate_normals)");
-    SF_CHECK(!icp->n_on_device || (mode == SF_ICP_REF_CPP && !icp->shard), SF_ERR_STATE, "a source set by sf_icp_set_source_scan serves unsharded REF_CPP alignments only");
+    SF_CHECK(!icp->src().n_on_device || (mode == SF_ICP_REF_CPP && !icp->shard), SF_ERR_STATE, "a source set by sf_icp_set_source_scan serves unsharded REF_CPP alignments only");
     SF_CHECK(icp->prm.num_iters >= 0, SF_ERR_INVALID, "negative iteration count");
     return SF_OK;
 }
@@ -4144,14 +4167,14 @@ void fill_result(const sf_icp *icp, int mode, const IcpState &S, const double *i
 int states_to_host(sf_icp *icp, int count = -1)
 {
     hipStream_t s = icp->ctx->stream;
-    const size_t nb = (size_t)(count >= 0 ? count : icp->batch);
+    const size_t nb = (size_t)(count >= 0 ? count : icp->src().batch);
     if (icp->h_state.size() < nb) icp->h_state.resize(nb);
     if (icp->last_fused && icp->h_pin) {
         SF_HIP(hipStreamSynchronize(s));
         std::memcpy(icp->h_state.data(), icp->h_pin, sizeof(IcpState) * nb);
         return SF_OK;
     }
-    SF_HIP(hipMemcpyAsync(icp->h_state.data(), icp->state.p, sizeof(IcpState) * nb, hipMemcpyDeviceToHost, s));
+    SF_HIP(hipMemcpyAsync(icp->h_state.data(), icp->cur().state.p, sizeof(IcpState) * nb, hipMemcpyDeviceToHost, s));
     SF_HIP(hipStreamSynchronize(s));
     return SF_OK;
 }
@@ -4187,22 +4210,22 @@ extern "C" void sf_icp_destroy(sf_icp *icp)
     hipError_t e = hipStreamSynchronize(icp->ctx->stream);
     (void)e;
     fused_release(icp);
-    if (icp->graph_exec) { e = hipGraphExecDestroy(icp->graph_exec); (void)e; }
-    if (icp->other.graph_exec) { e = hipGraphExecDestroy(icp->other.graph_exec); (void)e; }
-    for (int l = 0; l < 2; ++l) {
-        if (icp->lane_stream[l]) { e = hipStreamSynchronize(icp->lane_stream[l]); (void)e; e = hipStreamDestroy(icp->lane_stream[l]); (void)e; }
-        if (icp->lane_done[l]) { e = hipEventDestroy(icp->lane_done[l]); (void)e; }
-        if (icp->src_used[l]) { e = hipEventDestroy(icp->src_used[l]); (void)e; }
-        if (icp->started[l]) { e = hipEventDestroy(icp->started[l]); (void)e; }
+    for (Lane &ln : icp->lanes)
+        if (ln.graph_exec) { e = hipGraphExecDestroy(ln.graph_exec); (void)e; }
+    for (Lane &ln : icp->lanes) {
+        if (ln.stream) { e = hipStreamSynchronize(ln.stream); (void)e; e = hipStreamDestroy(ln.stream); (void)e; }
+        if (ln.done) { e = hipEventDestroy(ln.done); (void)e; }
+        if (ln.started) { e = hipEventDestroy(ln.started); (void)e; }
     }
+    for (SrcSet &ss : icp->srcs)
+        if (ss.used) { e = hipEventDestroy(ss.used); (void)e; }
     if (icp->src_ready) { e = hipEventDestroy(icp->src_ready); (void)e; }
     if (icp->unmarked_ev) { e = hipEventDestroy(icp->unmarked_ev); (void)e; }
     if (icp->main_mark) { e = hipEventDestroy(icp->main_mark); (void)e; }
     for (hipEvent_t ev : icp->ev) { e = hipEventDestroy(ev); (void)e; }
     if (icp->inits_ev) { e = hipEventDestroy(icp->inits_ev); (void)e; }
     if (icp->h_inits) { e = hipHostFree(icp->h_inits); (void)e; }
-    icp->X0.release(); icp->X0r.release(); icp->qcache.release(); icp->X.release(); icp->Xq.release(); icp->qkeys.release(); icp->qkeys2.release(); icp->qidx.release(); icp->qidx2.release(); icp->corr.release(); icp->bar.release(); if (icp->h_pin) { hipError_t eh = hipHostFree(icp->h_pin); (void)eh; icp->h_pin = nullptr; } icp->state.release(); icp->d_inits.release();
-    icp->n_dev.release(); icp->nn_stats.release(); icp->d_box.release(); icp->d_boxes.release(); icp->d_box_parts.release(); icp->stage.release(); icp->partials.release(); icp->xchg_own.release(); icp->own_idx.release(); icp->own_blk.release(); icp->own_count.release(); icp->own_off.release(); icp->own_keep.release();
+    if (icp->h_pin) { e = hipHostFree(icp->h_pin); (void)e; }
     if (icp->own_map) sf_map_destroy(icp->own_map);
     if (icp->own_cloud) sf_cloud_destroy(icp->own_cloud);
     sf_ctx *ctx = icp->ctx;
@@ -4234,9 +4257,9 @@ extern "C" int sf_icp_set_initial_transformation_f64(sf_icp *icp, const double T
 
 extern "C" int sf_icp_set_initial_batch_f64(sf_icp *icp, const double *inits)
 {
-    SF_CHECK(icp && icp->batch > 0, SF_ERR_STATE, "set the source batch first");
-    icp->inits.assign((size_t)icp->batch * 16, 0.0);
-    for (int b = 0; b < icp->batch; ++b)
+    SF_CHECK(icp && icp->src().batch > 0, SF_ERR_STATE, "set the source batch first");
+    icp->inits.assign((size_t)icp->src().batch * 16, 0.0);
+    for (int b = 0; b < icp->src().batch; ++b)
         for (int i = 0; i < 16; ++i) icp->inits[(size_t)b * 16 + i] = inits ? inits[(size_t)b * 16 + i] : (i % 5 == 0 ? 1.0 : 0.0);
     return SF_OK;
 }
@@ -4250,14 +4273,15 @@ extern "C" int sf_icp_set_source_batch(sf_icp *icp, const float *xyz, int64_t n_
     const int64_t total = n_per_scan * batch;
     // host memory has no producer on the device to wait for: with an alignment in flight the upload takes the other source set
     // and the next lane's stream (SrcScope) -- the next batch is uploaded and converted beside the alignment, not behind it
-    SrcScope src(icp, true);
-    SF_TRY(src.rc);
+    SrcScope scope(icp, true);
+    SF_TRY(scope.rc);
+    SrcSet &ss = icp->src(); // (the scope may have flipped the set)
     // persistent staging buffer, no allocation and no host synchronisation per scan: a copy from pageable host
     // memory is staged by the runtime before hipMemcpyAsync returns (the caller may reuse xyz at once); pinned
     // host memory is read asynchronously, stream-ordered -- then the caller owns the usual lifetime rule
-    SF_TRY(icp->stage.reserve(sizeof(float) * 3 * (size_t)std::max<int64_t>(total, 1)));
-    if (total > 0) SF_HIP(hipMemcpyAsync(icp->stage.p, xyz, sizeof(float) * 3 * (size_t)total, hipMemcpyHostToDevice, icp->ctx->stream));
-    int rc = icp_set_source_device_aos(icp, icp->stage.as<float>(), n_per_scan, batch, src.ahead);
+    SF_TRY(ss.stage.reserve(sizeof(float) * 3 * (size_t)std::max<int64_t>(total, 1)));
+    if (total > 0) SF_HIP(hipMemcpyAsync(ss.stage.p, xyz, sizeof(float) * 3 * (size_t)total, hipMemcpyHostToDevice, icp->ctx->stream));
+    int rc = icp_set_source_device_aos(icp, ss.stage.as<float>(), n_per_scan, batch, scope.ahead);
     if (batch == 1 && keep.size() >= 16) icp->inits.assign(keep.begin(), keep.begin() + 16); // setters are order independent
     return rc;
 }
@@ -4268,8 +4292,8 @@ extern "C" int sf_icp_set_source_batch_device(sf_icp *icp, const void *d_xyz, in
     SF_CHECK(n_per_scan * batch < (int64_t)0x7fffffff, SF_ERR_OVERFLOW, "too many source points");
     SF_HIP(hipSetDevice(icp->ctx->device));
     std::vector<double> keep = icp->inits;
-    SrcScope src(icp, false); // whatever produced d_xyz is ordered on the context's stream: the conversion stays there, behind it
-    SF_TRY(src.rc);
+    SrcScope scope(icp, false); // whatever produced d_xyz is ordered on the context's stream: the conversion stays there, behind it
+    SF_TRY(scope.rc);
     int rc = icp_set_source_device_aos(icp, reinterpret_cast<const float *>(d_xyz), n_per_scan, batch);
     if (batch == 1 && keep.size() >= 16) icp->inits.assign(keep.begin(), keep.begin() + 16);
     return rc;
@@ -4288,24 +4312,25 @@ extern "C" int sf_icp_set_source_scan(sf_icp *icp, sf_cloud *raw, int stride, co
     if (n_raw < stride) stride = 1; // point_cloud_processing.hpp:58-61: a cloud shorter than the step is left untouched
     const int64_t n_cand = sf::div_up(n_raw, stride);
     SF_CHECK(n_cand < ((int64_t)1 << 31) - 4096, SF_ERR_OVERFLOW, "too many points");
-    SrcScope src(icp, false); // (the raw cloud is a product of the context's stream)
-    SF_TRY(src.rc);
+    SrcScope scope(icp, false); // (the raw cloud is a product of the context's stream)
+    SF_TRY(scope.rc);
+    SrcSet &ss = icp->src(); // (the scope may have flipped the set)
     SF_TRY(icp_alloc(icp, n_cand, 1)); // capacity: every candidate survives
-    SF_TRY(icp->n_dev.reserve(sizeof(int)));
+    SF_TRY(ss.n_dev.reserve(sizeof(int)));
     hipStream_t s = icp->ctx->stream;
     if (n_cand == 0) {
-        hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, s, icp->n_dev.as<int>(), 0);
+        hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, s, ss.n_dev.as<int>(), 0);
     } else {
         const unsigned nb = nblk(n_cand, BLK);
         SF_TRY(icp->own_blk.reserve(sizeof(uint32_t) * (size_t)nb));
         const float r2 = (float)(radius * radius);
         hipLaunchKernelGGL(k_prep_count, dim3(nb), dim3(BLK), 0, s, raw->xyz.as<float>(), n_raw, stride, n_cand, center[0], center[1], center[2], r2, icp->own_blk.as<uint32_t>());
         hipLaunchKernelGGL(k_prep_scatter, dim3(nb), dim3(BLK), 0, s, raw->xyz.as<float>(), n_raw, stride, n_cand, center[0], center[1], center[2], r2, icp->own_blk.as<uint32_t>(),
-                           soa(icp->X0, icp->plane, 0), soa(icp->X0, icp->plane, 1), soa(icp->X0, icp->plane, 2), icp->X0r.as<float4>(), icp->n_dev.as<int>());
+                           soa(ss.X0, ss.plane, 0), soa(ss.X0, ss.plane, 1), soa(ss.X0, ss.plane, 2), ss.X0r.as<float4>(), ss.n_dev.as<int>());
     }
     SF_HIP(hipGetLastError());
-    icp->n_on_device = true;
-    icp->have_source = true;
+    ss.n_on_device = true;
+    ss.have_source = true;
     icp->src_version += 1;
     return SF_OK;
 }
@@ -4314,7 +4339,7 @@ extern "C" int sf_icp_set_source_scan(sf_icp *icp, sf_cloud *raw, int stride, co
 extern "C" int sf_icp_source_count(sf_icp *icp, int64_t *n)
 {
     SF_CHECK(icp && n, SF_ERR_INVALID, "bad arguments");
-    SF_CHECK(icp->batch == 1 && !icp->h_state.empty() && icp->h_state[0].n_points >= 0, SF_ERR_STATE, "no single-scan REF_CPP alignment has been fetched");
+    SF_CHECK(icp->src().batch == 1 && !icp->h_state.empty() && icp->h_state[0].n_points >= 0, SF_ERR_STATE, "no single-scan REF_CPP alignment has been fetched");
     *n = icp->h_state[0].n_points;
     return SF_OK;
 }
@@ -4355,8 +4380,9 @@ extern "C" int sf_icp_set_query_order(sf_icp *icp, int order)
 extern "C" int sf_icp_set_nn_reuse(sf_icp *icp, int on)
 {
     SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
+    Lane &ln = icp->cur();
     icp->reuse = on != 0;
-    if (icp->graph_exec) { hipError_t e = hipGraphExecDestroy(icp->graph_exec); (void)e; icp->graph_exec = nullptr; } // the captured launches carry the cache pointers
+    if (ln.graph_exec) { hipError_t e = hipGraphExecDestroy(ln.graph_exec); (void)e; ln.graph_exec = nullptr; } // the captured launches carry the cache pointers
     return SF_OK;
 }
 
@@ -4389,10 +4415,10 @@ extern "C" int sf_icp_tile_info(sf_icp *icp, int64_t out[12])
     out[0] = icp->tile_on ? 1 : 0;
     if (!icp->tile_on) return SF_OK;
     for (int a = 0; a < 3; ++a) { out[1 + a] = icp->tiles.tc[a]; out[4 + a] = icp->tiles.nt[a]; }
-    if (icp->tile_stats.p) {
+    if (icp->cur().tile_stats.p) {
         SF_HIP(hipSetDevice(icp->ctx->device));
         unsigned long long h[TILE_STATS];
-        SF_HIP(hipMemcpyAsync(h, icp->tile_stats.p, sizeof(h), hipMemcpyDeviceToHost, icp->ctx->stream));
+        SF_HIP(hipMemcpyAsync(h, icp->cur().tile_stats.p, sizeof(h), hipMemcpyDeviceToHost, icp->ctx->stream));
         SF_HIP(hipStreamSynchronize(icp->ctx->stream));
         for (int i = 0; i < 5; ++i) out[7 + i] = (int64_t)h[i];
     }
@@ -4410,9 +4436,9 @@ extern "C" int sf_icp_defer_stats(sf_icp *icp, int64_t out[2])
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
     out[0] = out[1] = 0;
-    if (!icp->df_planned || !icp->df_stat.p) return SF_OK; // (not freeze_on() as it is NOW: sf_icp_fetch_results may have moved fz_from since)
+    if (!icp->df_planned || !icp->cur().df_stat.p) return SF_OK; // (not freeze_on() as it is NOW: sf_icp_fetch_results may have moved fz_from since)
     uint32_t h[2] = {0u, 0u};
-    SF_HIP(hipMemcpyAsync(h, icp->df_stat.p, sizeof(h), hipMemcpyDeviceToHost, icp->ctx->stream));
+    SF_HIP(hipMemcpyAsync(h, icp->cur().df_stat.p, sizeof(h), hipMemcpyDeviceToHost, icp->ctx->stream));
     SF_HIP(hipStreamSynchronize(icp->ctx->stream));
     out[0] = (int64_t)h[0]; // queries that went to the dense pass
     out[1] = (int64_t)h[1]; // waves with more failing queries than DF_WCAP: searched in place
@@ -4443,13 +4469,13 @@ void freeze_learn_schedule(sf_icp *icp)
     if (++icp->fz_fetches >= FZ_PROBE_EVERY) { icp->fz_fetches = 0; icp->fz_from = FZ_FROM_DEFAULT; return; }
     if (!freeze_on(icp, icp->last_mode)) return; // (nothing was tried: nothing learnt)
     int latest = -1, never = 0;
-    for (int b = 0; b < icp->batch; ++b) {
+    for (int b = 0; b < icp->src().batch; ++b) {
         const IcpState &S = icp->h_state[(size_t)b];
         if (S.froze_launch >= 0) latest = std::max(latest, S.froze_launch);
         else if (S.iterations >= K) never += 1;
     }
     if (latest < 0) icp->fz_from = std::max(FZ_FROM_DEFAULT, K); // nothing froze: not worth the slower launches next time
-    else if (never * 4 <= icp->batch) icp->fz_from = std::min(std::max(FZ_FROM_DEFAULT, latest), std::max(FZ_FROM_DEFAULT, K - 2));
+    else if (never * 4 <= icp->src().batch) icp->fz_from = std::min(std::max(FZ_FROM_DEFAULT, latest), std::max(FZ_FROM_DEFAULT, K - 2));
 }
 } // namespace
 
@@ -4477,10 +4503,11 @@ extern "C" int sf_icp_set_freeze_params(sf_icp *icp, float guard_scale, float gu
 extern "C" int sf_icp_freeze_stats(sf_icp *icp, int64_t out[5])
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     for (int i = 0; i < 5; ++i) out[i] = 0;
-    if (!freeze_on(icp, icp->last_mode) || icp->last_fused || !icp->fz_state.p || icp->batch <= 0) return SF_OK;
-    std::vector<FreezeState> h((size_t)icp->batch);
-    SF_HIP(hipMemcpyAsync(h.data(), icp->fz_state.p, sizeof(FreezeState) * h.size(), hipMemcpyDeviceToHost, icp->ctx->stream));
+    if (!freeze_on(icp, icp->last_mode) || icp->last_fused || !ln.fz_state.p || ss.batch <= 0) return SF_OK;
+    std::vector<FreezeState> h((size_t)ss.batch);
+    SF_HIP(hipMemcpyAsync(h.data(), ln.fz_state.p, sizeof(FreezeState) * h.size(), hipMemcpyDeviceToHost, icp->ctx->stream));
     SF_HIP(hipStreamSynchronize(icp->ctx->stream));
     for (const FreezeState &f : h) {
         out[0] += f.froze;             // freeze launches that held
@@ -4563,57 +4590,26 @@ extern "C" int sf_icp_use_graph(sf_icp *icp, int on)
 }
 
 namespace {
-void lane_flip(sf_icp *icp)
-{
-    sf_icp::Lane &o = icp->other;
-    raw_swap(icp->X, o.X); raw_swap(icp->qcache, o.qcache); raw_swap(icp->Xq, o.Xq); raw_swap(icp->qkeys, o.qkeys); raw_swap(icp->qkeys2, o.qkeys2);
-    raw_swap(icp->qidx, o.qidx); raw_swap(icp->qidx2, o.qidx2); raw_swap(icp->corr, o.corr); raw_swap(icp->state, o.state); raw_swap(icp->d_inits, o.d_inits);
-    raw_swap(icp->partials, o.partials); raw_swap(icp->fz_state, o.fz_state); raw_swap(icp->fz_part, o.fz_part); raw_swap(icp->fz_cnt, o.fz_cnt);
-    raw_swap(icp->fz_ids, o.fz_ids); raw_swap(icp->fz_all, o.fz_all); raw_swap(icp->df_cnt, o.df_cnt); raw_swap(icp->df_ids, o.df_ids); raw_swap(icp->df_part, o.df_part);
-    raw_swap(icp->df_stat, o.df_stat); raw_swap(icp->qtkey, o.qtkey); raw_swap(icp->tseg, o.tseg); raw_swap(icp->tile_stats, o.tile_stats);
-    raw_swap(icp->cov_part, o.cov_part); raw_swap(icp->cov_out, o.cov_out);
-    std::swap(icp->graph_exec, o.graph_exec);
-    std::swap(icp->graph_key, o.graph_key);
-    std::swap(icp->inits_uploaded, o.inits_uploaded);
-    std::swap(icp->d_inits_epoch, o.d_inits_epoch);
-    std::swap(icp->meta, icp->other_meta);
-    icp->lane ^= 1;
-}
-
-// what icp_alloc sizes for the lane in the members, for the lane that has just been flipped in
-int lane_reserve(sf_icp *icp)
-{
-    const int batch = std::max(icp->batch, 1);
-    SF_TRY(icp->state.reserve(sizeof(IcpState) * (size_t)batch));
-    SF_TRY(icp->d_inits.reserve(sizeof(double) * 16 * (size_t)batch));
-    SF_TRY(icp->partials.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(icp->nblocks, 1) * (size_t)batch));
-    return SF_OK;
-}
-
 // RAII around the enqueue of one alignment.  An alignment enqueued while an earlier one of this object has not been fetched yet
-// (back-to-back sf_icp_align_batch_async: the throughput pattern) takes the OTHER lane's buffers and that lane's stream; the
-// first one after a fetch -- and every alignment of a caller that fetches each result before asking for the next -- runs on the
-// context's stream with the buffers it finds, as before.  Per lane an event marks its last alignment, whatever stream it ran on.
+// (back-to-back sf_icp_align_batch_async: the throughput pattern) takes the OTHER lane -- the constructor flips `lane`, so cur()
+// is the lane of this alignment from then on -- and that lane's stream; the first one after a fetch -- and every alignment of a
+// caller that fetches each result before asking for the next -- runs on the context's stream in the lane it finds, as before.
+// Per lane an event marks its last alignment, whatever stream it ran on.
 struct LaneScope {
     sf_icp *icp;
     hipStream_t main = nullptr;
     bool piped = false;
     int rc = SF_OK;
-    LaneScope(sf_icp *i, bool allowed) : icp(i)
+    LaneScope(sf_icp *i, bool allowed) : icp(i), main(i->ctx->stream)
     {
-        main = icp->ctx->stream;
-        if (!allowed && !icp->lane_done[0]) { // the per-scan path (single launch) of an object that has never piped: no streams, no events, nothing to record
+        if (!allowed && !icp->lanes[0].done) { // the per-scan path (single launch) of an object that has never piped: no streams, no events, nothing to record
             icp->src_unmarked_use = true;
             return;
         }
         rc = ensure_lanes(icp); // (every alignment marks the end of its reading of the source set: the events must exist)
         if (rc != SF_OK) return;
-        if (!allowed) {
-            // the context's stream, the buffers at hand -- behind a source that was written on a lane's stream, if one was
-            if (icp->src_ahead) {
-                if (hipStreamWaitEvent(main, icp->src_ready, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-                icp->src_ahead = false;
-            }
+        if (!allowed) { // the context's stream, the lane at hand -- behind a source that was written on a lane's stream, if one was
+            rc = wait_src_ahead(icp, main);
             return;
         }
         // the mark: where the context's stream stood when the inputs last changed (taken before anything of this alignment is enqueued)
@@ -4629,53 +4625,58 @@ struct LaneScope {
             icp->mark_map_generation = m->generation;
             icp->mark_window = m->window;
         }
-        if (!icp->unfetched && !icp->src_ahead) { // nothing of this object in flight: the context's stream, the buffers at hand
-            if (hipEventRecord(icp->started[icp->lane], main) == hipSuccess) icp->started_rec[icp->lane] = true;
+        if (!icp->unfetched && !icp->src_ahead) { // nothing of this object in flight: the context's stream, the lane at hand
+            if (hipEventRecord(icp->cur().started, main) == hipSuccess) icp->cur().started_rec = true;
             return;
         }
-        lane_flip(icp); // take turns (a source written ahead went to this lane's stream)
+        icp->lane ^= 1; // take turns (a source written ahead went to this lane's stream)
+        Lane &ln = icp->cur();
         rc = lane_reserve(icp);
         if (rc != SF_OK) return;
-        hipStream_t ls = icp->lane_stream[icp->lane];
         // after the inputs, and after this lane's previous alignment (which may have run on the context's stream)
-        if (hipStreamWaitEvent(ls, icp->main_mark, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-        if (icp->lane_used[icp->lane] && hipStreamWaitEvent(ls, icp->lane_done[icp->lane], 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-        if (icp->src_ahead) {
-            if (hipStreamWaitEvent(ls, icp->src_ready, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-            icp->src_ahead = false;
-        }
-        icp->ctx->stream = ls;
+        if (hipStreamWaitEvent(ln.stream, icp->main_mark, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
+        if (ln.used && hipStreamWaitEvent(ln.stream, ln.done, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
+        rc = wait_src_ahead(icp, ln.stream);
+        if (rc != SF_OK) return;
+        icp->ctx->stream = ln.stream;
         piped = true;
-        if (hipEventRecord(icp->started[icp->lane], ls) == hipSuccess) icp->started_rec[icp->lane] = true;
+        if (hipEventRecord(ln.started, ln.stream) == hipSuccess) ln.started_rec = true;
     }
     ~LaneScope()
     {
         hipStream_t ran = icp->ctx->stream;
         icp->ctx->stream = main;
-        if (!icp->lane_done[icp->lane]) return; // (the lanes have never been set up: nothing to mark)
-        if (icp->src_used[icp->src_set] && hipEventRecord(icp->src_used[icp->src_set], ran) == hipSuccess) icp->src_used_rec[icp->src_set] = true; // the last reader of this source set
-        if (hipEventRecord(icp->lane_done[icp->lane], ran) != hipSuccess) return;
-        icp->lane_used[icp->lane] = true;
+        Lane &ln = icp->cur(); SrcSet &ss = icp->src();
+        if (!ln.done) return; // (the lanes have never been set up: nothing to mark)
+        if (ss.used && hipEventRecord(ss.used, ran) == hipSuccess) ss.used_rec = true; // the last reader of this source set
+        if (hipEventRecord(ln.done, ran) != hipSuccess) return;
+        ln.used = true;
         // whatever the caller enqueues next on the context's stream is ordered behind this alignment
-        if (piped) { hipError_t e = hipStreamWaitEvent(main, icp->lane_done[icp->lane], 0); (void)e; }
+        if (piped) { hipError_t e = hipStreamWaitEvent(main, ln.done, 0); (void)e; }
     }
 };
 
-// The stepping and the sharded entry points run on the context's stream in the buffers at hand, without a LaneScope.  A source that
+// cur().meta <- the alignment being enqueued: sf_icp_fetch_results and a redo describe the latest alignment as it was enqueued
+void lane_describe(sf_icp *icp, int mode, bool cov)
+{
+    sf_icp::LaneMeta &M = icp->cur().meta;
+    M.valid = true; M.cov = cov; M.batch = icp->src().batch; M.mode = mode;
+    M.inits = icp->inits; M.src_set = icp->src_set; M.src_version = icp->src_version;
+}
+
+// The stepping and the sharded entry points run on the context's stream in the lane at hand, without a LaneScope.  A source that
 // SrcScope wrote ahead of an unfetched alignment (on a lane's stream, icp_alloc(outputs = false)) is theirs to adopt at the start of
 // an alignment: the context's stream waits for the upload, and everything an alignment writes per scan -- states, initial poses,
 // partial rows, the exchange records -- is sized for the source now at hand.  They leave no event on the source set they read: the
 // next source written ahead waits for the context's stream instead (src_unmarked_use).
 int step_adopt_source(sf_icp *icp)
 {
-    if (icp->src_ahead) {
-        SF_HIP(hipStreamWaitEvent(icp->ctx->stream, icp->src_ready, 0));
-        icp->src_ahead = false;
-    }
-    const auto e0 = icp->state.epoch;
+    SF_TRY(wait_src_ahead(icp, icp->ctx->stream));
+    Lane &ln = icp->cur();
+    const auto e0 = ln.state.epoch;
     SF_TRY(lane_reserve(icp));
-    if (icp->state.epoch != e0) icp->meta.valid = false; // (as icp_alloc: the states of the last alignment went with the old allocation)
-    SF_TRY(icp->xchg_own.reserve(sizeof(double) * REC_STRIDE * (size_t)std::max(icp->batch, 1)));
+    if (ln.state.epoch != e0) ln.meta.valid = false; // (as icp_alloc: the states of the last alignment went with the old allocation)
+    SF_TRY(icp->xchg_own.reserve(sizeof(double) * REC_STRIDE * (size_t)std::max(icp->src().batch, 1)));
     icp->src_unmarked_use = true;
     return SF_OK;
 }
@@ -4686,25 +4687,21 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     SF_TRY(check_ready(icp, mode));
     SF_CHECK(!icp->shard, SF_ERR_STATE, "a sharded alignment needs the exchange between its halves: use sf_icp_step_begin / sf_icp_step_end");
     SF_HIP(hipSetDevice(icp->ctx->device));
+    const SrcSet &ss = icp->src(); // (an alignment never flips the source set)
     icp->last_mode = mode;
     icp->last_fused = fused_eligible(icp, mode);
     icp->df_planned = !icp->last_fused && defer_planned(icp, mode);
     SF_TRY(order_lut_prepare(icp));
     // the launch list takes a lane (see sf_icp::Lane); the single launch, profiled runs and a count left on the device stay on the context's stream
     const bool beside = icp->unfetched; // an alignment of this object is still unfetched: this one may run beside it
-    LaneScope lanes(icp, icp->pipeline != 0 && !icp->last_fused && !icp->profiling && !icp->n_on_device);
+    LaneScope lanes(icp, icp->pipeline != 0 && !icp->last_fused && !icp->profiling && !ss.n_on_device);
     SF_TRY(lanes.rc);
+    Lane &ln = icp->cur(); // (the scope may have flipped the lane)
     if (!lanes.piped) SF_TRY(lane_reserve(icp)); // (a source written ahead of an alignment in flight left the output buffers alone: icp_alloc)
     icp->unfetched = true;
-    icp->prev_ok = lanes.piped && beside && icp->other_meta.valid; // (not piped: this alignment runs in the buffers of the one before it)
-    icp->prev_cov_ok = icp->prev_ok && icp->other_meta.cov;
-    icp->meta.valid = true;
-    icp->meta.cov = icp->cov_on != 0;
-    icp->meta.batch = icp->batch;
-    icp->meta.mode = mode;
-    icp->meta.inits = icp->inits;
-    icp->meta.src_set = icp->src_set;
-    icp->meta.src_version = icp->src_version;
+    icp->prev_ok = lanes.piped && beside && icp->prev().meta.valid; // (not piped: this alignment runs in the lane of the one before it)
+    icp->prev_cov_ok = icp->prev_ok && icp->prev().meta.cov;
+    lane_describe(icp, mode, icp->cov_on != 0);
     hipStream_t s = icp->ctx->stream;
     if (icp->cov_on) SF_TRY(cov_alloc(icp)); // (before any capture, and before the graph key is formed)
     SF_TRY(launch_state_init(icp));
@@ -4722,54 +4719,54 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
         hipLaunchKernelGGL(k_set_window, dim3(1), dim3(1), 0, s, icp->map->d_window.as<SfWindow>(), icp->map->window);
     }
     SF_TRY(order_queries(icp, mode)); // plain launches ahead of the (replayed) iteration graph
-    if (mode != SF_ICP_REF_CPP) SF_TRY(reuse_reset(icp, icp->n * icp->batch));
+    if (mode != SF_ICP_REF_CPP) SF_TRY(reuse_reset(icp, ss.n * ss.batch));
     if (freeze_on(icp, mode)) SF_TRY(freeze_alloc(icp));
     // O3D_P2P / P2PLANE take the window by value (it moves with the pose: plain launches then); REF_CPP reads it from device memory
     if (icp->use_graph && !icp->profiling && (icp->map->window.kind == 0 || mode == SF_ICP_REF_CPP)) {
         if (mode == SF_ICP_REF_CPP) { // buffers must exist before capture (and before the key is formed)
-            SF_TRY(icp->X.reserve(sizeof(float) * 3 * (size_t)std::max<int64_t>(icp->plane, 1)));
-            SF_TRY(icp->corr.reserve(sizeof(float4) * (size_t)std::max<int64_t>(icp->plane, 1)));
+            SF_TRY(ln.X.reserve(sizeof(float) * 3 * (size_t)std::max<int64_t>(ss.plane, 1)));
+            SF_TRY(ln.corr.reserve(sizeof(float4) * (size_t)std::max<int64_t>(ss.plane, 1)));
         }
         const sf_icp::GraphKey key = graph_key_now(icp, mode);
-        const bool hit = icp->graph_exec && key == icp->graph_key;
+        const bool hit = ln.graph_exec && key == ln.graph_key;
         if (!hit) {
-            if (icp->graph_exec) { hipError_t e = hipGraphExecDestroy(icp->graph_exec); (void)e; icp->graph_exec = nullptr; }
+            if (ln.graph_exec) { hipError_t e = hipGraphExecDestroy(ln.graph_exec); (void)e; ln.graph_exec = nullptr; }
             hipGraph_t graph = nullptr;
             SF_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             int rc = enqueue_align(icp, mode);
             hipError_t e = hipStreamEndCapture(s, &graph);
             if (rc != SF_OK) return rc;
             SF_CHECK(e == hipSuccess, SF_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-            e = hipGraphInstantiate(&icp->graph_exec, graph, nullptr, nullptr, 0);
+            e = hipGraphInstantiate(&ln.graph_exec, graph, nullptr, nullptr, 0);
             hipError_t e2 = hipGraphDestroy(graph);
             (void)e2;
             SF_CHECK(e == hipSuccess, SF_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-            icp->graph_key = key;
+            ln.graph_key = key;
             icp->graph_captures += 1;
         }
         icp->graph_replays += 1;
-        SF_HIP(hipGraphLaunch(icp->graph_exec, s));
+        SF_HIP(hipGraphLaunch(ln.graph_exec, s));
         return SF_OK;
     }
     return enqueue_align(icp, mode);
 }
 
 namespace {
-// The alignment that is redone is the one being fetched, as it was enqueued (icp->meta): its source, its priors, its mode.  A source
+// The alignment that is redone is the one being fetched, as it was enqueued (cur().meta): its source, its priors, its mode.  A source
 // and priors set since belong to the NEXT alignment.  With the lanes on that source went into the other source set (SrcScope), so
-// the set the alignment read is still whole: it is flipped in for the redo and out again afterwards, and the upload written ahead
+// the set the alignment read is still whole: src_set is flipped to it for the redo and back again afterwards, and the upload written ahead
 // keeps its mark (src_ahead) for the alignment that will read it.  A source that replaced the alignment's own in place (no lanes)
 // leaves nothing to redo from: an error, not another batch's poses.
 int redo_after_barrier_timeout(sf_icp *icp)
 {
-    const sf_icp::LaneMeta was = icp->meta;
+    const sf_icp::LaneMeta was = icp->cur().meta;
     const bool flip = was.valid && was.src_set != icp->src_set;
     SF_CHECK(!was.valid || flip || was.src_version == icp->src_version, SF_ERR_STATE,
              "a grid barrier timed out and the alignment cannot be redone: its source was replaced before the fetch");
     const bool ahead = icp->src_ahead;
     std::vector<double> next_inits;
     if (was.valid) {
-        if (flip) src_flip(icp);
+        if (flip) icp->src_set ^= 1;
         icp->src_ahead = false; // (the redo reads nothing of the upload written ahead, and runs on the context's stream)
         next_inits.swap(icp->inits);
         icp->inits = was.inits;
@@ -4778,7 +4775,7 @@ int redo_after_barrier_timeout(sf_icp *icp)
     if (rc == SF_OK) rc = states_to_host(icp);
     if (rc == SF_OK) {
         icp->unfetched = false; // (the states are on the host)
-        for (int b = 0; b < icp->batch && rc == SF_OK; ++b)
+        for (int b = 0; b < icp->src().batch && rc == SF_OK; ++b) // (the set the redo read)
             if (icp->h_state[(size_t)b].flags & SF_ICP_FLAG_BARRIER_TIMEOUT) {
                 sf::set_error("alignment redone through the launch list still carries a barrier flag");
                 rc = SF_ERR_HIP;
@@ -4786,7 +4783,7 @@ int redo_after_barrier_timeout(sf_icp *icp)
     }
     if (was.valid) { // what the next alignment will see: the source and the priors set for it
         icp->inits.swap(next_inits);
-        if (flip) src_flip(icp);
+        if (flip) icp->src_set ^= 1;
         icp->src_ahead = ahead;
     }
     return rc;
@@ -4796,18 +4793,20 @@ int redo_after_barrier_timeout(sf_icp *icp)
 extern "C" int sf_icp_fetch_results(sf_icp *icp, sf_icp_result *out)
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
-    SF_CHECK(icp->batch > 0, SF_ERR_STATE, "nothing to fetch");
+    // (ln and ss still name the lane and set at hand after check_barrier_flags: its redo enqueues with `unfetched` and `src_ahead` false, so LaneScope keeps the lane, and flips src_set back before it returns)
+    const Lane &ln = icp->cur(); const SrcSet &ss = icp->src();
+    SF_CHECK(ss.batch > 0, SF_ERR_STATE, "nothing to fetch");
     // the latest alignment as it was enqueued: a source or priors set since (for the NEXT alignment) do not describe it
-    const bool described = icp->meta.valid && icp->meta.batch > 0 && !icp->shard;
-    const int nb = described ? icp->meta.batch : icp->batch;
+    const bool described = ln.meta.valid && ln.meta.batch > 0 && !icp->shard;
+    const int nb = described ? ln.meta.batch : ss.batch;
     SF_TRY(states_to_host(icp, nb));
     icp->unfetched = false;
     fused_release(icp); // the grid has drained
     if (icp->profiling) prof_collect(icp);
     SF_TRY(check_barrier_flags(icp, nb));
     for (int b = 0; b < nb; ++b)
-        fill_result(icp, described ? icp->meta.mode : icp->last_mode, icp->h_state[(size_t)b], described ? &icp->meta.inits[(size_t)b * 16] : &icp->inits[(size_t)b * 16], out + b);
-    if (nb == icp->batch) freeze_learn_schedule(icp);
+        fill_result(icp, described ? ln.meta.mode : icp->last_mode, icp->h_state[(size_t)b], described ? &ln.meta.inits[(size_t)b * 16] : &icp->inits[(size_t)b * 16], out + b);
+    if (nb == ss.batch) freeze_learn_schedule(icp);
     return SF_OK;
 }
 
@@ -4818,17 +4817,17 @@ extern "C" int sf_icp_fetch_results(sf_icp *icp, sf_icp_result *out)
 extern "C" int sf_icp_fetch_previous(sf_icp *icp, sf_icp_result *out)
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
-    SF_CHECK(icp->prev_ok && icp->other_meta.valid && icp->other_meta.batch > 0, SF_ERR_STATE,
+    Lane &pl = icp->prev();
+    const sf_icp::LaneMeta &M = pl.meta;
+    SF_CHECK(icp->prev_ok && M.valid && M.batch > 0, SF_ERR_STATE,
              "no earlier alignment to fetch: the latest alignment did not run beside the one before it (fetched in between, pipeline off, single launch) or it was fetched already");
-    const int ol = icp->lane ^ 1;
-    const sf_icp::LaneMeta &M = icp->other_meta;
-    SF_CHECK(icp->lane_used[ol] && icp->lane_done[ol] && icp->lane_stream[ol] && icp->other.state.p, SF_ERR_STATE, "the other lane holds no alignment");
+    SF_CHECK(pl.used && pl.done && pl.stream && pl.state.p, SF_ERR_STATE, "the other lane holds no alignment");
     SF_HIP(hipSetDevice(icp->ctx->device));
-    SF_HIP(hipEventSynchronize(icp->lane_done[ol]));
+    SF_HIP(hipEventSynchronize(pl.done));
     icp->h_prev.resize((size_t)M.batch);
     // on the other lane's own stream: neither the context's stream (it waits for the latest alignment) nor the null stream is touched
-    SF_HIP(hipMemcpyAsync(icp->h_prev.data(), icp->other.state.p, sizeof(IcpState) * (size_t)M.batch, hipMemcpyDeviceToHost, icp->lane_stream[ol]));
-    SF_HIP(hipStreamSynchronize(icp->lane_stream[ol]));
+    SF_HIP(hipMemcpyAsync(icp->h_prev.data(), pl.state.p, sizeof(IcpState) * (size_t)M.batch, hipMemcpyDeviceToHost, pl.stream));
+    SF_HIP(hipStreamSynchronize(pl.stream));
     for (int b = 0; b < M.batch; ++b) fill_result(icp, M.mode, icp->h_prev[(size_t)b], &M.inits[(size_t)b * 16], out + b);
     icp->prev_ok = false;
     return SF_OK;
@@ -4857,30 +4856,31 @@ extern "C" int sf_icp_set_degeneracy_thresholds(sf_icp *icp, double trans, doubl
 extern "C" int sf_icp_fetch_covariance(sf_icp *icp, sf_icp_covariance *out)
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
-    SF_CHECK(icp->meta.valid && icp->meta.batch > 0 && !icp->shard, SF_ERR_STATE, "no alignment to fetch a covariance of");
-    SF_CHECK(icp->meta.cov, SF_ERR_STATE, "the latest alignment ran with the covariance switch off (sf_icp_set_covariance)");
+    const Lane &ln = icp->cur();
+    SF_CHECK(ln.meta.valid && ln.meta.batch > 0 && !icp->shard, SF_ERR_STATE, "no alignment to fetch a covariance of");
+    SF_CHECK(ln.meta.cov, SF_ERR_STATE, "the latest alignment ran with the covariance switch off (sf_icp_set_covariance)");
     SF_CHECK(!icp->unfetched, SF_ERR_STATE, "fetch the alignment's results first (sf_icp_fetch_results)");
-    SF_CHECK(icp->cov_out.p, SF_ERR_STATE, "no covariance has been computed");
+    SF_CHECK(ln.cov_out.p, SF_ERR_STATE, "no covariance has been computed");
     SF_HIP(hipSetDevice(icp->ctx->device));
     hipStream_t s = icp->ctx->stream; // (ordered behind the alignment, whichever lane it took)
-    SF_HIP(hipMemcpyAsync(out, icp->cov_out.p, sizeof(sf_icp_covariance) * (size_t)icp->meta.batch, hipMemcpyDeviceToHost, s));
+    SF_HIP(hipMemcpyAsync(out, ln.cov_out.p, sizeof(sf_icp_covariance) * (size_t)ln.meta.batch, hipMemcpyDeviceToHost, s));
     SF_HIP(hipStreamSynchronize(s));
     return SF_OK;
 }
 
-// twin of sf_icp_fetch_previous: the other lane's buffers, the other lane's stream, the latest alignment goes on running
+// twin of sf_icp_fetch_previous: prev()'s buffers on prev()'s stream, the latest alignment goes on running
 extern "C" int sf_icp_fetch_covariance_previous(sf_icp *icp, sf_icp_covariance *out)
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
-    SF_CHECK(icp->other_meta.valid && icp->other_meta.batch > 0 && (icp->prev_ok || icp->prev_cov_ok), SF_ERR_STATE,
+    Lane &pl = icp->prev();
+    SF_CHECK(pl.meta.valid && pl.meta.batch > 0 && (icp->prev_ok || icp->prev_cov_ok), SF_ERR_STATE,
              "no earlier alignment to fetch a covariance of: the latest alignment did not run beside the one before it, or it was fetched already");
-    SF_CHECK(icp->other_meta.cov && icp->prev_cov_ok, SF_ERR_STATE, "the earlier alignment ran with the covariance switch off, or its covariance was fetched already");
-    const int ol = icp->lane ^ 1;
-    SF_CHECK(icp->lane_used[ol] && icp->lane_done[ol] && icp->lane_stream[ol] && icp->other.cov_out.p, SF_ERR_STATE, "the other lane holds no covariance");
+    SF_CHECK(pl.meta.cov && icp->prev_cov_ok, SF_ERR_STATE, "the earlier alignment ran with the covariance switch off, or its covariance was fetched already");
+    SF_CHECK(pl.used && pl.done && pl.stream && pl.cov_out.p, SF_ERR_STATE, "the other lane holds no covariance");
     SF_HIP(hipSetDevice(icp->ctx->device));
-    SF_HIP(hipEventSynchronize(icp->lane_done[ol]));
-    SF_HIP(hipMemcpyAsync(out, icp->other.cov_out.p, sizeof(sf_icp_covariance) * (size_t)icp->other_meta.batch, hipMemcpyDeviceToHost, icp->lane_stream[ol]));
-    SF_HIP(hipStreamSynchronize(icp->lane_stream[ol]));
+    SF_HIP(hipEventSynchronize(pl.done));
+    SF_HIP(hipMemcpyAsync(out, pl.cov_out.p, sizeof(sf_icp_covariance) * (size_t)pl.meta.batch, hipMemcpyDeviceToHost, pl.stream));
+    SF_HIP(hipStreamSynchronize(pl.stream));
     icp->prev_cov_ok = false;
     return SF_OK;
 }
@@ -4891,7 +4891,7 @@ extern "C" int sf_icp_align_batch(sf_icp *icp, int mode, sf_icp_result *out)
     SF_TRY(sf_icp_align_batch_async(icp, mode));
     int rc = sf_icp_fetch_results(icp, out);
     if (rc == SF_OK && icp->debug)
-        for (int b = 0; b < icp->batch; ++b)
+        for (int b = 0; b < icp->src().batch; ++b)
             fprintf(stdout, "[ICP INFO] scan %d: iterations %d, error %g, correspondences %d, converged %d\n", b, out[b].iterations, (double)out[b].error,
                     out[b].n_corr, out[b].converged);
     return rc;
@@ -4900,8 +4900,8 @@ extern "C" int sf_icp_align_batch(sf_icp *icp, int mode, sf_icp_result *out)
 extern "C" int sf_icp_align(sf_icp *icp, int mode, sf_icp_result *out)
 {
     SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
-    SF_CHECK(icp->have_source, SF_ERR_STATE, "no source cloud set");
-    SF_CHECK(icp->batch == 1, SF_ERR_STATE, "sf_icp_align needs a single source scan (use sf_icp_align_batch)");
+    SF_CHECK(icp->src().have_source, SF_ERR_STATE, "no source cloud set");
+    SF_CHECK(icp->src().batch == 1, SF_ERR_STATE, "sf_icp_align needs a single source scan (use sf_icp_align_batch)");
     return sf_icp_align_batch(icp, mode, out);
 }
 
@@ -4933,7 +4933,7 @@ extern "C" int sf_icp_set_exchange_buffer(sf_icp *icp, void *d_buf, int64_t nbyt
 extern "C" void *sf_icp_exchange_ptr(sf_icp *icp, int64_t *nbytes)
 {
     if (!icp) return nullptr;
-    const int64_t need = (int64_t)sizeof(double) * REC_STRIDE * std::max(icp->batch, 1);
+    const int64_t need = (int64_t)sizeof(double) * REC_STRIDE * std::max(icp->src().batch, 1);
     if (nbytes) *nbytes = need;
     if (icp->xchg && icp->xchg_bytes >= need) return icp->xchg;
     return icp->xchg_own.p;
@@ -4946,16 +4946,17 @@ namespace {
 // One host synchronisation (the counts size the sort and the launch grid).
 int shard_build(sf_icp *icp, bool resume)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     ProfScope ps(icp, SF_PROF_SHARD_BUILD);
-    const int B = icp->batch;
-    const int n = (int)icp->n;
-    const int nbf = icp->nblocks; // workgroups covering a whole scan
+    const int B = ss.batch;
+    const int n = (int)ss.n;
+    const int nbf = ss.nblocks; // workgroups covering a whole scan
     hipStream_t s = icp->ctx->stream;
-    IcpState *st = icp->state.as<IcpState>();
+    IcpState *st = ln.state.as<IcpState>();
     SF_TRY(icp->own_blk.reserve(sizeof(uint32_t) * (size_t)nbf * (size_t)B));
     SF_TRY(icp->own_count.reserve(sizeof(uint32_t) * (size_t)B));
     SF_TRY(icp->own_off.reserve(sizeof(uint32_t) * (size_t)(B + 1)));
-    const float *X = soa(icp->X0, icp->plane, 0), *Y = soa(icp->X0, icp->plane, 1), *Z = soa(icp->X0, icp->plane, 2);
+    const float *X = soa(ss.X0, ss.plane, 0), *Y = soa(ss.X0, ss.plane, 1), *Z = soa(ss.X0, ss.plane, 2);
     const dim3 grid((unsigned)nbf, (unsigned)B);
     if (resume) hipLaunchKernelGGL(k_own_resume, dim3(nblk(B, 64)), dim3(64), 0, s, st, B);
     SF_TRY(icp->own_keep.reserve(sizeof(unsigned long long) * (size_t)nbf * (size_t)B * (BLK / 64)));
@@ -4971,11 +4972,11 @@ int shard_build(sf_icp *icp, bool resume)
     }
     const int64_t own = (int64_t)icp->h_own[(size_t)B];
     icp->own_total = own;
-    icp->own_nblocks = (int)std::max<int64_t>(1, sf::div_up((int64_t)maxc, BLK * icp->qpl));
+    icp->own_nblocks = (int)std::max<int64_t>(1, sf::div_up((int64_t)maxc, BLK * ss.qpl));
     SF_HIP(hipMemcpyAsync(icp->own_off.p, icp->h_own.data(), sizeof(uint32_t) * (size_t)(B + 1), hipMemcpyHostToDevice, s));
     const size_t cap = (size_t)std::max<int64_t>(own, 1);
     SF_TRY(icp->own_idx.reserve(sizeof(uint32_t) * cap));
-    SF_TRY(icp->Xq.reserve(sizeof(float) * 3 * cap));
+    SF_TRY(ln.Xq.reserve(sizeof(float) * 3 * cap));
     if (own > 0) {
         hipLaunchKernelGGL(k_own_scatter, grid, dim3(BLK), 0, s, n, st, icp->own_keep.as<unsigned long long>(), icp->own_blk.as<uint32_t>(), nbf, icp->own_off.as<uint32_t>(),
                            icp->own_idx.as<uint32_t>());
@@ -4999,19 +5000,12 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     SF_CHECK(first >= 0 && first <= 2, SF_ERR_INVALID, "first must be 0, 1 or 2");
     SF_CHECK(!icp->cov_on, SF_ERR_STATE, COV_DECLINE_MSG);
     SF_CHECK(first != 2 || icp->shard, SF_ERR_STATE, "resume (first = 2) is a sharded-path operation");
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = false;
     if (first) SF_TRY(step_adopt_source(icp)); // (sf_icp_align_group and the all-reduce form of sf_icp_align_sharded_async start here too)
-    if (first == 1) { // sf_icp_fetch_results describes the latest alignment as it was enqueued: this one
-        icp->meta.valid = true;
-        icp->meta.cov = false;
-        icp->meta.batch = icp->batch;
-        icp->meta.mode = mode;
-        icp->meta.inits = icp->inits;
-        icp->meta.src_set = icp->src_set;
-        icp->meta.src_version = icp->src_version;
-    }
+    if (first == 1) lane_describe(icp, mode, false);
     if (first) icp->df_planned = defer_planned(icp, mode);
     if (first) SF_TRY(order_lut_prepare(icp));
     if (first == 1) SF_TRY(launch_state_init(icp));
@@ -5019,27 +5013,27 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
         if (first) SF_TRY(shard_build(icp, first == 2));
     } else if (first) {
         SF_TRY(order_queries(icp, mode));
-        SF_TRY(reuse_reset(icp, icp->n * icp->batch));
+        SF_TRY(reuse_reset(icp, ss.n * ss.batch));
     }
     if (first) SF_TRY(freeze_start_pass(icp, mode));
     double *x = reinterpret_cast<double *>(sf_icp_exchange_ptr(icp, nullptr));
     hipStream_t s = icp->ctx->stream;
     // wide scans: the first launches of a pass with one query per lane, as enqueue_align (rows of 256: twice as many)
-    const bool q1 = mode == SF_ICP_P2PLANE && icp->qpl > 1 && icp->fz_step < VERIFY_FROM_SEARCH;
-    const int nb = icp->shard ? (q1 ? icp->own_nblocks * icp->qpl : icp->own_nblocks) : (q1 ? icp->nblocks : icp->nblocks_nn);
-    const int qpl_now = q1 ? 1 : icp->qpl;
+    const bool q1 = mode == SF_ICP_P2PLANE && ss.qpl > 1 && icp->fz_step < VERIFY_FROM_SEARCH;
+    const int nb = icp->shard ? (q1 ? icp->own_nblocks * ss.qpl : icp->own_nblocks) : (q1 ? ss.nblocks : ss.nblocks_nn);
+    const int qpl_now = q1 ? 1 : ss.qpl;
     const uint32_t *off = icp->shard ? icp->own_off.as<uint32_t>() : nullptr;
     if (mode == SF_ICP_O3D_P2P) {
         launch_nn_red<1>(icp, icp->shard);
         ProfScope ps(icp, SF_PROF_REDUCE);
-        hipLaunchKernelGGL(k_reduce_only<1>, dim3(icp->batch), dim3(SBLK), 0, s, icp->state.as<IcpState>(), icp->partials.as<double>(), nb, x, off, icp->qpl, freeze_bufs(icp, false));
+        hipLaunchKernelGGL(k_reduce_only<1>, dim3(ss.batch), dim3(SBLK), 0, s, ln.state.as<IcpState>(), ln.partials.as<double>(), nb, x, off, ss.qpl, freeze_bufs(icp, false));
     } else {
         const bool df = !q1 && defer_now(icp, mode, icp->fz_step);
         if (freeze_nn_now(icp, mode)) launch_nn_red_fz(icp, icp->shard, icp->fz_step > icp->fz_from);
         else if (df) launch_nn_red_df(icp);
         else launch_nn_red<2>(icp, icp->shard, q1);
         ProfScope ps(icp, SF_PROF_REDUCE);
-        hipLaunchKernelGGL(k_reduce_only<2>, dim3(icp->batch), dim3(SBLK), 0, s, icp->state.as<IcpState>(), icp->partials.as<double>(), nb, x, off, qpl_now,
+        hipLaunchKernelGGL(k_reduce_only<2>, dim3(ss.batch), dim3(SBLK), 0, s, ln.state.as<IcpState>(), ln.partials.as<double>(), nb, x, off, qpl_now,
                            freeze_bufs(icp, freeze_nn_now(icp, mode), df));
     }
     SF_HIP(hipGetLastError());
@@ -5049,17 +5043,18 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
 extern "C" int sf_icp_step_end(sf_icp *icp, int mode, int last)
 {
     SF_TRY(check_ready(icp, mode));
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     (void)last;
     const double *x = reinterpret_cast<const double *>(sf_icp_exchange_ptr(icp, nullptr));
     hipStream_t s = icp->ctx->stream;
     const int K = icp->prm.num_iters;
     ProfScope ps(icp, SF_PROF_SOLVE);
     if (mode == SF_ICP_O3D_P2P)
-        hipLaunchKernelGGL(k_solve_only<1>, dim3(nblk(icp->batch, 64)), dim3(64), 0, s, icp->state.as<IcpState>(), x, (int)icp->n, K, icp->batch, icp->d_boxes.as<ScanBox>(),
+        hipLaunchKernelGGL(k_solve_only<1>, dim3(nblk(ss.batch, 64)), dim3(64), 0, s, ln.state.as<IcpState>(), x, (int)ss.n, K, ss.batch, ss.d_boxes.as<ScanBox>(),
                            icp->shard ? icp->own_margin : 0.0f, (FreezeState *)nullptr, icp->fz_prm, 0);
     else
-        hipLaunchKernelGGL(k_solve_only<2>, dim3(nblk(icp->batch, 64)), dim3(64), 0, s, icp->state.as<IcpState>(), x, (int)icp->n, K, icp->batch, icp->d_boxes.as<ScanBox>(),
-                           icp->shard ? icp->own_margin : 0.0f, freeze_solve_now(icp, mode) ? icp->fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm,
+        hipLaunchKernelGGL(k_solve_only<2>, dim3(nblk(ss.batch, 64)), dim3(64), 0, s, ln.state.as<IcpState>(), x, (int)ss.n, K, ss.batch, ss.d_boxes.as<ScanBox>(),
+                           icp->shard ? icp->own_margin : 0.0f, freeze_solve_now(icp, mode) ? ln.fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm,
                            (int)(icp->fz_step + 2 < K));
     icp->fz_step += 1;
     SF_HIP(hipGetLastError());
@@ -5116,7 +5111,7 @@ int sharded_steps(const sf_icp *icp, int mode) { return mode == SF_ICP_O3D_P2P ?
 
 bool any_stale(const sf_icp *icp)
 {
-    for (int b = 0; b < icp->batch; ++b)
+    for (int b = 0; b < icp->src().batch; ++b)
         if (icp->h_state[(size_t)b].flags & SF_ICP_FLAG_SHARD_STALE) return true;
     return false;
 }
@@ -5127,6 +5122,7 @@ namespace {
 // one iteration of the sharded loop over a P2P communicator: NN + slab rows, reduce + publish, gather + solve
 int shard_step_p2p(sf_icp *icp, int mode, int first, const sf::P2pView &view)
 {
+    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = false;
@@ -5135,23 +5131,23 @@ int shard_step_p2p(sf_icp *icp, int mode, int first, const sf::P2pView &view)
     if (first) SF_TRY(shard_build(icp, first == 2));
     if (first) SF_TRY(freeze_start_pass(icp, mode));
     hipStream_t s = icp->ctx->stream;
-    IcpState *st = icp->state.as<IcpState>();
-    const bool q1 = mode == SF_ICP_P2PLANE && icp->qpl > 1 && icp->fz_step < VERIFY_FROM_SEARCH; // as enqueue_align: one query per lane while nearly every query searches
-    const int nb = q1 ? icp->own_nblocks * icp->qpl : icp->own_nblocks, B = icp->batch, K = icp->prm.num_iters, qpl_now = q1 ? 1 : icp->qpl;
+    IcpState *st = ln.state.as<IcpState>();
+    const bool q1 = mode == SF_ICP_P2PLANE && ss.qpl > 1 && icp->fz_step < VERIFY_FROM_SEARCH; // as enqueue_align: one query per lane while nearly every query searches
+    const int nb = q1 ? icp->own_nblocks * ss.qpl : icp->own_nblocks, B = ss.batch, K = icp->prm.num_iters, qpl_now = q1 ? 1 : ss.qpl;
     const bool fz_nn = freeze_nn_now(icp, mode), fz_solve = freeze_solve_now(icp, mode);
     if (mode == SF_ICP_O3D_P2P) launch_nn_red<1>(icp, true);
     else if (fz_nn) launch_nn_red_fz(icp, true, icp->fz_step > icp->fz_from);
     else launch_nn_red<2>(icp, true, q1);
     {
         ProfScope ps(icp, SF_PROF_REDUCE);
-        if (mode == SF_ICP_O3D_P2P) hipLaunchKernelGGL(k_reduce_publish<1>, dim3(B), dim3(SBLK), 0, s, st, icp->partials.as<double>(), nb, icp->own_off.as<uint32_t>(), icp->qpl, view, freeze_bufs(icp, false));
-        else hipLaunchKernelGGL(k_reduce_publish<2>, dim3(B), dim3(SBLK), 0, s, st, icp->partials.as<double>(), nb, icp->own_off.as<uint32_t>(), qpl_now, view, freeze_bufs(icp, fz_nn));
+        if (mode == SF_ICP_O3D_P2P) hipLaunchKernelGGL(k_reduce_publish<1>, dim3(B), dim3(SBLK), 0, s, st, ln.partials.as<double>(), nb, icp->own_off.as<uint32_t>(), ss.qpl, view, freeze_bufs(icp, false));
+        else hipLaunchKernelGGL(k_reduce_publish<2>, dim3(B), dim3(SBLK), 0, s, st, ln.partials.as<double>(), nb, icp->own_off.as<uint32_t>(), qpl_now, view, freeze_bufs(icp, fz_nn));
     }
     {
         ProfScope ps(icp, SF_PROF_COLLECTIVE); // the wait for the peers' records AND the solve
-        if (mode == SF_ICP_O3D_P2P) hipLaunchKernelGGL(k_gather_solve<1>, dim3(B), dim3(64), 0, s, st, (int)icp->n, K, icp->d_boxes.as<ScanBox>(), icp->own_margin, view, (FreezeState *)nullptr, icp->fz_prm, 0);
-        else hipLaunchKernelGGL(k_gather_solve<2>, dim3(B), dim3(64), 0, s, st, (int)icp->n, K, icp->d_boxes.as<ScanBox>(), icp->own_margin, view,
-                                fz_solve ? icp->fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm, (int)(icp->fz_step + 2 < K));
+        if (mode == SF_ICP_O3D_P2P) hipLaunchKernelGGL(k_gather_solve<1>, dim3(B), dim3(64), 0, s, st, (int)ss.n, K, ss.d_boxes.as<ScanBox>(), icp->own_margin, view, (FreezeState *)nullptr, icp->fz_prm, 0);
+        else hipLaunchKernelGGL(k_gather_solve<2>, dim3(B), dim3(64), 0, s, st, (int)ss.n, K, ss.d_boxes.as<ScanBox>(), icp->own_margin, view,
+                                fz_solve ? ln.fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm, (int)(icp->fz_step + 2 < K));
     }
     icp->fz_step += 1;
     SF_HIP(hipGetLastError());
@@ -5172,7 +5168,7 @@ extern "C" int sf_icp_align_sharded_async(sf_icp *icp, int mode, sf_comm *comm, 
     int rc = SF_OK;
     for (int k = 0; k < steps && rc == SF_OK; ++k) {
         sf::P2pView view;
-        const int p2p = sf::comm_p2p_begin(comm, (int64_t)REC_STRIDE * icp->batch, &view);
+        const int p2p = sf::comm_p2p_begin(comm, (int64_t)REC_STRIDE * icp->src().batch, &view);
         if (p2p < 0) { rc = p2p; break; }
         if (p2p == 1) { // P2P: the reduce kernel publishes, the solve kernel gathers (two kernels per iteration, no all-reduce of its own)
             rc = shard_step_p2p(icp, mode, k == 0 ? first : 0, view);
@@ -5181,7 +5177,7 @@ extern "C" int sf_icp_align_sharded_async(sf_icp *icp, int mode, sf_comm *comm, 
         rc = sf_icp_step_begin(icp, mode, k == 0 ? first : 0);
         if (rc == SF_OK) {
             ProfScope ps(icp, SF_PROF_COLLECTIVE);
-            rc = sf::comm_allreduce_f64(comm, sf_icp_exchange_ptr(icp, nullptr), (int64_t)REC_STRIDE * icp->batch);
+            rc = sf::comm_allreduce_f64(comm, sf_icp_exchange_ptr(icp, nullptr), (int64_t)REC_STRIDE * icp->src().batch);
         }
         if (rc == SF_OK) rc = sf_icp_step_end(icp, mode, k == steps - 1);
     }
@@ -5206,7 +5202,7 @@ extern "C" int sf_icp_align_sharded(sf_icp *icp, int mode, sf_comm *comm, sf_icp
             SF_TRY(fetch_states(icp));
             SF_TRY(sf_comm_status(comm)); // a collective that timed out or was aborted left the records unsummed: no result
             if (!any_stale(icp)) {
-                for (int b = 0; b < icp->batch; ++b) fill_result(icp, icp->last_mode, icp->h_state[(size_t)b], &icp->inits[(size_t)b * 16], out + b);
+                for (int b = 0; b < icp->src().batch; ++b) fill_result(icp, icp->last_mode, icp->h_state[(size_t)b], &icp->inits[(size_t)b * 16], out + b);
                 if (resumes) *resumes = n_resume;
                 return SF_OK;
             }
@@ -5231,12 +5227,12 @@ extern "C" int sf_icp_align_group(sf_icp **members, int n, int mode, sf_icp_resu
         SF_TRY(check_ready(members[m], mode));
         SF_CHECK(members[m]->shard, SF_ERR_STATE, "member %d: sf_icp_set_shard first", m);
         SF_CHECK(!members[m]->cov_on, SF_ERR_STATE, COV_DECLINE_MSG);
-        SF_CHECK(members[m]->ctx == members[0]->ctx && members[m]->batch == members[0]->batch && members[m]->n == members[0]->n &&
+        SF_CHECK(members[m]->ctx == members[0]->ctx && members[m]->src().batch == members[0]->src().batch && members[m]->src().n == members[0]->src().n &&
                      members[m]->prm.num_iters == members[0]->prm.num_iters,
                  SF_ERR_INVALID, "member %d does not match member 0 (context, batch, points per scan, iterations)", m);
     }
     sf_icp *lead = members[0];
-    const int steps = sharded_steps(lead, mode), count = REC_STRIDE * lead->batch;
+    const int steps = sharded_steps(lead, mode), count = REC_STRIDE * lead->src().batch;
     hipStream_t s = lead->ctx->stream;
     int first = 1, n_resume = 0;
     for (int attempt = 0; attempt <= steps + 1; ++attempt) {
@@ -5251,12 +5247,12 @@ extern "C" int sf_icp_align_group(sf_icp **members, int n, int mode, sf_icp_resu
         SF_HIP(hipGetLastError());
         for (int m = 0; m < n; ++m) SF_TRY(fetch_states(members[m]));
         for (int m = 1; m < n; ++m) // the slabs must agree bit for bit: same records in, same solve
-            for (int b = 0; b < lead->batch; ++b)
+            for (int b = 0; b < lead->src().batch; ++b)
                 SF_CHECK(std::memcmp(members[m]->h_state[(size_t)b].T, lead->h_state[(size_t)b].T, sizeof(double) * 16) == 0 &&
                              members[m]->h_state[(size_t)b].flags == lead->h_state[(size_t)b].flags,
                          SF_ERR_STATE, "slab %d diverged from slab 0 on scan %d", m, b);
         if (!any_stale(lead)) {
-            for (int b = 0; b < lead->batch; ++b) fill_result(lead, lead->last_mode, lead->h_state[(size_t)b], &lead->inits[(size_t)b * 16], out + b);
+            for (int b = 0; b < lead->src().batch; ++b) fill_result(lead, lead->last_mode, lead->h_state[(size_t)b], &lead->inits[(size_t)b * 16], out + b);
             if (resumes) *resumes = n_resume;
             return SF_OK;
         }
@@ -5271,9 +5267,9 @@ extern "C" int sf_icp_align_group(sf_icp **members, int n, int mode, sf_icp_resu
 // record before the collective is not kept; this is the owned-candidate count of the compact arrays)
 extern "C" int sf_icp_owned_counts(sf_icp *icp, int64_t *counts, int cap)
 {
-    SF_CHECK(icp && counts && cap >= icp->batch, SF_ERR_INVALID, "bad arguments");
-    SF_CHECK(icp->shard && icp->h_own.size() == (size_t)icp->batch + 1, SF_ERR_STATE, "no sharded alignment has run");
-    for (int b = 0; b < icp->batch; ++b) counts[b] = (int64_t)icp->h_own[(size_t)b + 1] - (int64_t)icp->h_own[(size_t)b];
+    SF_CHECK(icp && counts && cap >= icp->src().batch, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(icp->shard && icp->h_own.size() == (size_t)icp->src().batch + 1, SF_ERR_STATE, "no sharded alignment has run");
+    for (int b = 0; b < icp->src().batch; ++b) counts[b] = (int64_t)icp->h_own[(size_t)b + 1] - (int64_t)icp->h_own[(size_t)b];
     return SF_OK;
 }
 

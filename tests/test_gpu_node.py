@@ -352,7 +352,7 @@ def test_a_redone_alignment_is_the_one_that_was_enqueued(api, ctx, synth, small_
     where the fetch must still look at the barrier flags of the three scans it fetches.
 
     What makes it pass: redo_after_barrier_timeout (csrc/sf_icp.hip) flips the source set the fetched alignment read back in
-    (icp->meta.src_set, recorded by sf_icp_align_batch_async), restores its priors and mode from icp->meta for the redo, and puts
+    (cur().meta.src_set, recorded by sf_icp_align_batch_async), restores its priors and mode from cur().meta for the redo, and puts
     the next batch's source, priors and src_ahead back afterwards; sf_icp_fetch_results checks the barrier flags of the scans it
     fetches whatever the batch now at hand.  Before, the redo aligned whatever source and priors were at hand: S1 returned as S0."""
     m = small_world["map"]

@@ -192,7 +192,7 @@ def test_a_stepped_alignment_behind_a_source_set_ahead(api, ctx, synth, world):
     waits for src_ready, and lane_reserve + the xchg_own reserve size the states, partial rows and exchange records for five
     scans.  Without it the step reads a source still uploading and writes five scans' states and records into buffers sized for
     three.  That fetch_results returns the stepped alignment's five scans (and not three, described by the asynchronous one) is the
-    description sf_icp_step_begin(first = 1) now leaves in icp->meta."""
+    description sf_icp_step_begin(first = 1) now leaves in cur().meta."""
     iters = 12
     first = world["scans"][:3, :100_000].copy()
     second = np.concatenate([world["scans"], world["scans"][:1, ::-1]])        # five scans of 140 000 points
