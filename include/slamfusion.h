@@ -224,6 +224,22 @@ int sf_map_download_normals(sf_map *m, float *normals, int32_t *n_neighbors, int
 /* raw exact 1-NN (a9 without the threshold): idx in ORIGINAL point order, d2 squared
  * float32 summed x,y,z like FLANN L2_Simple; idx = -1 if nothing within max_d2. */
 int sf_map_nn(sf_map *m, const float *queries, int64_t n, float max_d2, int32_t *idx, float *d2);
+#define SF_KNN_MAX 64
+/* exact k nearest neighbours of each query among the indexed points the window accepts (as sf_map_nn).
+ * Row i of idx / d2 (k entries each): the min(k, m_i) smallest candidates in ascending order of
+ * (d2, position in the index), d2 = FLANN L2_Simple in float32 like sf_map_nn, accepted iff d2 < max_d2 (strict);
+ * idx in ORIGINAL point order; the unused tail of a row is idx = -1, d2 = +inf.  count[i] = min(k, m_i) (may be NULL).
+ * A non-finite query, an empty map, or max_d2 <= 0 or NaN gives count 0 (no search).  SF_ERR_INVALID for k < 1 or k > SF_KNN_MAX. */
+int sf_map_knn(sf_map *m, const float *queries, int64_t n, int k, float max_d2, int32_t *idx, float *d2, int32_t *count);
+/* extension x2, the k-NN / hybrid form (Open3D KDTreeSearchParamKNN / Hybrid): PCA normal (and covariance) of every map point
+ * from its k nearest map points, itself included, within max_radius (<= 0 or inf: no limit).  See DESIGN §13 for the exact rule.
+ * The map remembers (k, max_radius, with_covariance) in place of the radius: with sf_map_set_normals_carry on, sf_map_patch is
+ * followed by this estimate in full on every path (sf_map_normals_carry_info: {0, 0, n, n}). */
+int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, int with_covariance);
+/* measurement (tools/knn_bench.py): with the switch on, sf_map_nn, sf_map_knn and sf_map_estimate_normals[_cov|_knn] record device
+ * events around their kernel launches (not the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */
+int sf_map_profile_launches(sf_map *m, int on);
+int sf_map_last_launch_ms(sf_map *m, float *ms);
 
 /* ------------------------------------------------------------------ ICP */
 /* a13: ICPResult — icp_point_to_point.h:28-39 (+ float64 and diagnostics) */

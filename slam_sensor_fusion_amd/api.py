@@ -430,6 +430,12 @@ class Map:
     def estimate_normals(self, radius, covariance=False):
         _check(self.lib.sf_map_estimate_normals_cov(self.h, C.c_float(radius), C.c_int(int(covariance))))
 
+    def estimate_normals_knn(self, k, max_radius=np.inf, covariance=False):
+        """sf_map_estimate_normals_knn: PCA normals (and covariances) from each map point's k nearest map points, itself included,
+        within max_radius (inf or <= 0: no limit) -- Open3D's KDTreeSearchParamKNN / Hybrid."""
+        r = float(max_radius)
+        _check(self.lib.sf_map_estimate_normals_knn(self.h, C.c_int(int(k)), C.c_float(r if np.isfinite(r) else 0.0), C.c_int(int(covariance))))
+
     def set_normals_carry(self, on=True):
         """sf_map_set_normals_carry: `patch` keeps the estimated normals (and covariances) -- carried with the entries that stay,
         re-estimated where the merge changed a neighbourhood; bit-equal to patch + estimate_normals with the last arguments."""
@@ -467,6 +473,28 @@ class Map:
         d2 = np.empty(len(q), np.float32)
         _check(self.lib.sf_map_nn(self.h, _p(q), C.c_int64(len(q)), C.c_float(min(max_d2, 3.0e38)), _p(idx), _p(d2)))
         return idx, d2
+
+    def knn(self, queries, k, max_d2=np.inf):
+        """sf_map_knn: the exact k nearest indexed points of each query (inside the window, d2 < max_d2) -> (idx [n, k] int32 in
+        original point order, d2 [n, k] float32, count [n] int32); rows ascend in (d2, index position), tails are -1 / inf."""
+        q = _f32(queries).reshape(-1, 3)
+        k = int(k)
+        rows = max(k, 0)
+        idx = np.empty((len(q), rows), np.int32)
+        d2 = np.empty((len(q), rows), np.float32)
+        cnt = np.empty(len(q), np.int32)
+        _check(self.lib.sf_map_knn(self.h, _p(q), C.c_int64(len(q)), C.c_int(k), C.c_float(max_d2), _p(idx), _p(d2), _p(cnt)))
+        return idx, d2, cnt
+
+    def profile_launches(self, on=True):
+        """sf_map_profile_launches: device events around the kernel launches of nn / knn / estimate_normals*."""
+        _check(self.lib.sf_map_profile_launches(self.h, C.c_int(int(bool(on)))))
+        return self
+
+    def last_launch_ms(self):
+        ms = C.c_float()
+        _check(self.lib.sf_map_last_launch_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def close(self):
         if self.h:

@@ -187,9 +187,14 @@ struct sf_map {
     sf::DevBuf nrm4_alt, cov6_alt, carry_tmp, carry_list;
     bool normals_carry = false;
     bool nrm_estimated = false; // the normals come from sf_map_estimate_normals_cov with the arguments below (not sf_map_set_normals)
-    float nrm_radius = 0;
+    float nrm_radius = 0;       // ... its radius, or the max_radius of the k-NN form
+    int nrm_knn_k = 0;          // > 0: the estimate is sf_map_estimate_normals_knn's with this k (re-run in full behind a patch, not carried)
     bool nrm_with_cov = false;
     int64_t carry_info[4] = {-1, 0, 0, 0}; // sf_map_normals_carry_info
+    // sf_map_profile_launches: device events around the kernel launches of sf_map_nn / sf_map_knn / sf_map_estimate_normals*
+    bool profile = false;
+    hipEvent_t prof_ev[2] = {nullptr, nullptr};
+    float last_launch_ms = -1.0f;
     int64_t n = 0;
     bool built = false, has_normals = false, has_cov = false;
     uint64_t generation = 0; // process-unique stamp of the index contents (build / normals): captured hipGraphs key on it

@@ -9,6 +9,7 @@
 //   nrm4[n]       float4  normal xyz + neighbour count (sorted order), optional
 #include "sf_common.hpp"
 #include "sf_nn.hpp"
+#include "sf_knn.hpp"
 
 #include "sf_sort.hpp"
 #include <cmath>
@@ -19,6 +20,27 @@ namespace {
 inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)sf::div_up(n > 0 ? n : 1, b); }
 
 struct GridGeom { float org[3]; float inv_h; int dim[3]; uint64_t ncell; };
+
+// sf_map_profile_launches: events around the launches of a query / estimate call, read after the call's own synchronise
+inline void prof_begin(sf_map *m)
+{
+    if (!m->profile) return;
+    for (int i = 0; i < 2; ++i) // (each on its own: one that could not be created is tried again, never recorded on)
+        if (!m->prof_ev[i] && hipEventCreate(&m->prof_ev[i]) != hipSuccess) { m->prof_ev[i] = nullptr; m->profile = false; return; }
+    hipError_t e = hipEventRecord(m->prof_ev[0], m->ctx->stream);
+    (void)e;
+}
+inline void prof_end(sf_map *m)
+{
+    if (!m->profile) return;
+    hipError_t e = hipEventRecord(m->prof_ev[1], m->ctx->stream);
+    (void)e;
+}
+inline void prof_read(sf_map *m)
+{
+    float ms = -1.0f;
+    if (m->profile && hipEventElapsedTime(&ms, m->prof_ev[0], m->prof_ev[1]) == hipSuccess) m->last_launch_ms = ms;
+}
 
 // K = uint32_t while the grid has fewer than 2^32 cells, uint64_t beyond (large sparse extents: a dense table over
 // 1 km x 1 km x 100 m at 0.25 m is 6.4e9 cells = 25.6 GB of the 288 GB)
@@ -164,6 +186,8 @@ extern "C" void sf_map_destroy(sf_map *m)
     m->pts4.release(); m->nrm4.release(); m->cov6.release(); m->d_window.release(); m->cell_start.release(); m->keys.release(); m->vals.release();
     m->keys2.release(); m->vals2.release(); m->pts4_alt.release(); m->patch_tmp.release();
     m->nrm4_alt.release(); m->cov6_alt.release(); m->carry_tmp.release(); m->carry_list.release();
+    for (hipEvent_t ev : m->prof_ev)
+        if (ev) { hipError_t e2 = hipEventDestroy(ev); (void)e2; }
     sf_ctx *ctx = m->ctx;
     delete m;
     sf::ctx_release(ctx);
@@ -181,6 +205,7 @@ extern "C" int sf_map_build(sf_map *m, sf_cloud *cloud, float cell)
     m->built = false;
     m->has_normals = false;
     m->nrm_estimated = false; // (sf_map_patch remembers the estimate it carries before it comes here)
+    m->nrm_knn_k = 0;
     m->n = 0;
     m->window.kind = 0;
     const float *xyz = cloud->xyz.as<float>();
@@ -479,14 +504,26 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     const uint64_t old_cells = (uint64_t)old.dim[0] * (uint64_t)old.dim[1] * (uint64_t)old.dim[2];
     const int64_t n_old = rec.n_old, ng = rec.n_groups, n_out = cloud->n;
     // the estimate to carry (sf_map_set_normals_carry): normals that sf_map_estimate_normals_cov wrote, with its arguments
-    const bool carry = m->normals_carry && m->has_normals && m->nrm_estimated;
+    // a k-NN estimate (sf_map_estimate_normals_knn) is not carried entry by entry -- a point added or removed can change a
+    // neighbourhood arbitrarily far away -- but run again in full behind the patch, on every path
+    const int knn_k = (m->normals_carry && m->has_normals && m->nrm_estimated) ? m->nrm_knn_k : 0;
+    const bool knn_cov = knn_k > 0 && m->has_cov && m->nrm_with_cov;
+    const bool carry = m->normals_carry && m->has_normals && m->nrm_estimated && knn_k == 0;
     const float carry_radius = m->nrm_radius;
     const bool carry_cov = carry && m->has_cov && m->nrm_with_cov;
+    auto knn_again = [&]() -> int {
+        SF_TRY(sf_map_estimate_normals_knn(m, knn_k, carry_radius, knn_cov ? 1 : 0));
+        m->carry_info[0] = 0;
+        m->carry_info[1] = 0;
+        m->carry_info[2] = m->grid.n;
+        return SF_OK;
+    };
     m->carry_info[0] = -1; m->carry_info[1] = m->carry_info[2] = 0; m->carry_info[3] = m->n;
     auto rebuild = [&](int why) -> int { // *patched: 0 / negative = the build ran, and why
         if (patched) *patched = why;
         SF_TRY(sf_map_build(m, cloud, cell));
         m->carry_info[3] = m->n;
+        if (knn_k > 0) return knn_again();
         if (!carry) return SF_OK;
         SF_TRY(sf_map_estimate_normals_cov(m, carry_radius, carry_cov ? 1 : 0)); // nothing of the old estimate survives a build: in full, as remembered
         m->carry_info[0] = 0;
@@ -595,6 +632,7 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     m->built = true;
     m->has_normals = false;
     m->nrm_estimated = false;
+    m->nrm_knn_k = 0;
     m->window.kind = 0;
     SfGrid &G = m->grid;
     for (int d = 0; d < 3; ++d) G.dim[d] = g.dim[d];
@@ -625,6 +663,7 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
         m->carry_info[1] = 2 * ng - rec.n_fresh; // every centroid, and the old point of every voxel that had one
         m->carry_info[2] = n_dirty;
     }
+    if (knn_k > 0) SF_TRY(knn_again());
     if (patched) *patched = 1;
     return SF_OK;
 }
@@ -744,14 +783,84 @@ extern "C" int sf_map_nn(sf_map *m, const float *queries, int64_t n, float max_d
     SF_TRY(di.reserve(sizeof(int32_t) * (size_t)n));
     SF_TRY(dd.reserve(sizeof(float) * (size_t)n));
     SF_HIP(hipMemcpyAsync(dq.p, queries, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    prof_begin(m);
     if (m->window.kind)
         hipLaunchKernelGGL(k_map_nn_t<true>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, max_d2, di.as<int32_t>(), dd.as<float>());
     else
         hipLaunchKernelGGL(k_map_nn_t<false>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, max_d2, di.as<int32_t>(), dd.as<float>());
+    prof_end(m);
     SF_HIP(hipGetLastError());
     SF_HIP(hipMemcpyAsync(idx, di.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipMemcpyAsync(d2, dd.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
+    prof_read(m);
+    return SF_OK;
+}
+
+// ------------------------------------------------------------------ exact k-NN (sf_knn.hpp)
+namespace {
+// a wave walks its 64 consecutive queries one after another, all lanes on the same query; result rows are written by lanes 0 .. k-1
+template <bool WINDOW>
+__global__ __launch_bounds__(256) void k_map_knn_t(SfGrid g, SfWindow w, const float *__restrict__ q, int64_t n, int k, float thr, int32_t *__restrict__ idx, float *__restrict__ d2,
+                                                  int32_t *__restrict__ count)
+{
+    __shared__ sf::WaveKNN ws[256 / 64];
+    // the window from LDS: as a kernel argument its 35 dwords stay in SGPRs across the whole walk, which is wave-uniform and
+    // lives in SGPRs itself, and the register file spills
+    __shared__ SfWindow sw;
+    if (WINDOW) {
+        if (threadIdx.x == 0) sw = w;
+        __syncthreads();
+    }
+    const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+    const int64_t base = ((int64_t)blockIdx.x * 4 + wv) * 64;
+    if (base >= n) return; // (the whole wave: no workgroup barrier below)
+    const int64_t i = base + lane;
+    const bool valid = i < n;
+    const float mx = valid ? q[3 * i] : 0.0f, my = valid ? q[3 * i + 1] : 0.0f, mz = valid ? q[3 * i + 2] : 0.0f;
+    const int nq = (int)min((int64_t)64, n - base);
+    for (int t = 0; t < nq; ++t) {
+        const float qx = __shfl(mx, t), qy = __shfl(my, t), qz = __shfl(mz, t);
+        unsigned long long key;
+        const int cnt = sf::knn_search<WINDOW>(g, WINDOW ? sw : w, qx, qy, qz, k, thr, &ws[wv], key);
+        if (lane < k) {
+            const bool has = lane < cnt;
+            int32_t id = -1;
+            if (has) id = (int32_t)__float_as_uint(g.pts[(uint32_t)key].w);
+            idx[(size_t)(base + t) * (size_t)k + lane] = id;
+            d2[(size_t)(base + t) * (size_t)k + lane] = has ? __uint_as_float((uint32_t)(key >> 32)) : INFINITY;
+        }
+        if (lane == 0) count[base + t] = cnt;
+    }
+}
+} // namespace
+
+extern "C" int sf_map_knn(sf_map *m, const float *queries, int64_t n, int k, float max_d2, int32_t *idx, float *d2, int32_t *count)
+{
+    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
+    SF_CHECK(k >= 1 && k <= SF_KNN_MAX, SF_ERR_INVALID, "k must be 1 .. %d (got %d)", SF_KNN_MAX, k);
+    SF_CHECK(n >= 0 && (n == 0 || (queries && idx && d2)), SF_ERR_INVALID, "bad arguments");
+    if (n == 0) return SF_OK;
+    sf_ctx *ctx = m->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    sf::DevBuf dq, di, dd, dc;
+    SF_TRY(dq.reserve(sizeof(float) * 3 * (size_t)n));
+    SF_TRY(di.reserve(sizeof(int32_t) * (size_t)n * (size_t)k));
+    SF_TRY(dd.reserve(sizeof(float) * (size_t)n * (size_t)k));
+    SF_TRY(dc.reserve(sizeof(int32_t) * (size_t)n));
+    SF_HIP(hipMemcpyAsync(dq.p, queries, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    prof_begin(m);
+    if (m->window.kind)
+        hipLaunchKernelGGL(k_map_knn_t<true>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, k, max_d2, di.as<int32_t>(), dd.as<float>(), dc.as<int32_t>());
+    else
+        hipLaunchKernelGGL(k_map_knn_t<false>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, k, max_d2, di.as<int32_t>(), dd.as<float>(), dc.as<int32_t>());
+    prof_end(m);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(idx, di.p, sizeof(int32_t) * (size_t)n * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(d2, dd.p, sizeof(float) * (size_t)n * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    if (count) SF_HIP(hipMemcpyAsync(count, dc.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    prof_read(m);
     return SF_OK;
 }
 
@@ -857,6 +966,63 @@ __global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, int R, flo
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= g.n) return;
     normals_point(g, r2, R, j, nrm4, cov6);
+}
+
+// ---- k-NN / hybrid normals: the neighbourhood is the k-NN list of the point's own coordinates (sf_knn.hpp), the
+// float64 sums run over the list positions in the pairwise tree of wave_tree_sum (absent positions +0.0), so they depend on the
+// list alone.  A wave walks its 64 consecutive points one after another; each lane keeps the count and the six sums of "its"
+// point in registers and the Jacobi solve then runs once, lane per point (not once per wave with 63 lanes redundant).
+__device__ __forceinline__ void knn_normal_finish(int cnt, const double C[6], int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+{
+    double nv[3] = {0, 0, 1};
+    if (cnt >= 3) {
+        const double M[9] = {C[0], C[1], C[2], C[1], C[3], C[4], C[2], C[4], C[5]};
+        smallest_eigvec(M, nv);
+    }
+    nrm4[j] = make_float4((float)nv[0], (float)nv[1], (float)nv[2], __int_as_float(cnt));
+    if (cov6) {
+#pragma unroll
+        for (int d = 0; d < 6; ++d) cov6[6 * (size_t)j + d] = cnt >= 3 ? C[d] / (double)cnt : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_normals_knn(SfGrid g, SfWindow w, int k, float thr, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+{
+    __shared__ sf::WaveKNN ws[256 / 64];
+    const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+    const int64_t base = ((int64_t)blockIdx.x * 4 + wv) * 64;
+    if (base >= g.n) return; // (the whole wave: no workgroup barrier below)
+    const int64_t i = base + lane;
+    const float4 mine = i < g.n ? g.pts[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const int nq = (int)min((int64_t)64, g.n - base);
+    double myC[6] = {0, 0, 0, 0, 0, 0};
+    int mycnt = 0;
+    for (int t = 0; t < nq; ++t) {
+        const float qx = __shfl(mine.x, t), qy = __shfl(mine.y, t), qz = __shfl(mine.z, t);
+        unsigned long long key;
+        const int cnt = sf::knn_search<false>(g, w, qx, qy, qz, k, thr, &ws[wv], key);
+        const bool has = lane < cnt;
+        const float4 p = sf::load_point(g, (uint32_t)key, has);
+        double C[6] = {0, 0, 0, 0, 0, 0};
+        if (cnt >= 3) {
+            const double sx = sf::wave_tree_sum(has ? (double)p.x : 0.0), sy = sf::wave_tree_sum(has ? (double)p.y : 0.0), sz = sf::wave_tree_sum(has ? (double)p.z : 0.0);
+            const double mx = sx / cnt, my = sy / cnt, mz = sz / cnt;
+            const double ax = has ? (double)p.x - mx : 0.0, ay = has ? (double)p.y - my : 0.0, az = has ? (double)p.z - mz : 0.0;
+            C[0] = sf::wave_tree_sum(has ? __dmul_rn(ax, ax) : 0.0);
+            C[1] = sf::wave_tree_sum(has ? __dmul_rn(ax, ay) : 0.0);
+            C[2] = sf::wave_tree_sum(has ? __dmul_rn(ax, az) : 0.0);
+            C[3] = sf::wave_tree_sum(has ? __dmul_rn(ay, ay) : 0.0);
+            C[4] = sf::wave_tree_sum(has ? __dmul_rn(ay, az) : 0.0);
+            C[5] = sf::wave_tree_sum(has ? __dmul_rn(az, az) : 0.0);
+        }
+        if (lane == t) {
+            mycnt = cnt;
+#pragma unroll
+            for (int d = 0; d < 6; ++d) myC[d] = C[d];
+        }
+    }
+    if (i >= g.n) return;
+    knn_normal_finish(mycnt, myC, i, nrm4, cov6);
 }
 
 // ---- the estimate carried over sf_map_patch: only where a neighbourhood changed
@@ -1005,18 +1171,68 @@ extern "C" int sf_map_estimate_normals_cov(sf_map *m, float radius, int with_cov
     m->has_cov = false;
     if (with_covariance) SF_TRY(m->cov6.reserve(sizeof(double) * 6 * (size_t)std::max<int64_t>(m->n, 1)));
     const int R = normals_reach(radius, m->grid.h);
+    prof_begin(m);
     if (m->grid.n > 0)
         hipLaunchKernelGGL(k_normals, dim3(nblk(m->grid.n)), dim3(256), 0, ctx->stream, m->grid, (double)radius * (double)radius, R, m->nrm4.as<float4>(),
                            with_covariance ? m->cov6.as<double>() : nullptr);
+    prof_end(m);
     SF_HIP(hipGetLastError());
     SF_HIP(hipStreamSynchronize(ctx->stream));
+    prof_read(m);
     m->grid.nrm = m->nrm4.as<float4>();
     m->has_normals = true;
     m->has_cov = with_covariance != 0;
     m->nrm_estimated = true; // what sf_map_patch carries (sf_map_set_normals_carry)
+    m->nrm_knn_k = 0;
     m->nrm_radius = radius;
     m->nrm_with_cov = with_covariance != 0;
     m->generation = sf::next_generation();
+    return SF_OK;
+}
+
+extern "C" int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, int with_covariance)
+{
+    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
+    SF_CHECK(k >= 1 && k <= SF_KNN_MAX, SF_ERR_INVALID, "k must be 1 .. %d (got %d)", SF_KNN_MAX, k);
+    SF_CHECK(!std::isnan(max_radius), SF_ERR_INVALID, "max_radius must be a number (<= 0 or inf: no limit)");
+    sf_ctx *ctx = m->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    SF_TRY(m->nrm4.reserve(sizeof(float4) * (size_t)std::max<int64_t>(m->n, 1)));
+    m->has_cov = false;
+    if (with_covariance) SF_TRY(m->cov6.reserve(sizeof(double) * 6 * (size_t)std::max<int64_t>(m->n, 1)));
+    const float thr = (max_radius > 0 && std::isfinite(max_radius)) ? (float)(max_radius * max_radius) : INFINITY;
+    SfWindow none{};
+    prof_begin(m);
+    if (m->grid.n > 0)
+        hipLaunchKernelGGL(k_normals_knn, dim3(nblk(m->grid.n)), dim3(256), 0, ctx->stream, m->grid, none, k, thr, m->nrm4.as<float4>(), with_covariance ? m->cov6.as<double>() : nullptr);
+    prof_end(m);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    prof_read(m);
+    m->grid.nrm = m->nrm4.as<float4>();
+    m->has_normals = true;
+    m->has_cov = with_covariance != 0;
+    m->nrm_estimated = true; // what sf_map_patch re-estimates (sf_map_set_normals_carry): in full, by this call
+    m->nrm_knn_k = k;
+    m->nrm_radius = max_radius;
+    m->nrm_with_cov = with_covariance != 0;
+    m->generation = sf::next_generation();
+    return SF_OK;
+}
+
+extern "C" int sf_map_profile_launches(sf_map *m, int on)
+{
+    SF_CHECK(m, SF_ERR_INVALID, "bad arguments");
+    m->profile = on != 0;
+    m->last_launch_ms = -1.0f;
+    return SF_OK;
+}
+
+extern "C" int sf_map_last_launch_ms(sf_map *m, float *ms)
+{
+    SF_CHECK(m && ms, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(m->profile && m->last_launch_ms >= 0.0f, SF_ERR_STATE, "nothing timed (sf_map_profile_launches, then a query or an estimate)");
+    *ms = m->last_launch_ms;
     return SF_OK;
 }
 
@@ -1071,6 +1287,7 @@ extern "C" int sf_map_set_normals(sf_map *m, const float *normals, int64_t n)
     m->has_normals = true;
     m->has_cov = false;
     m->nrm_estimated = false; // normals of the caller's: nothing to re-estimate them with, sf_map_patch drops them
+    m->nrm_knn_k = 0;
     m->generation = sf::next_generation();
     return SF_OK;
 }

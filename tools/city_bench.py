@@ -19,7 +19,10 @@ keeps P2PLANE from freezing, so its fair throughput baseline is scans_per_s_no_f
 smallest normalised eigenvalue of the marginal translation / rotation information and the flags, and scans/s with the switch
 off and on (same object, same settings).  --tunnel replaces the city by synth.make_tunnel (walls along x, ends out of range,
 40 m rays): the degenerate scene, where the translation flag is expected on every scan.
-   python tools/city_bench.py [--map-points 10000000] [--batch 64] [--rings 64 128] [--prior 0.06:0.3 0.3:1.5] [--dynamic-boxes 40] [--robust tukey:0.1] [--covariance [--tunnel]]"""
+--normals-knn K estimates the map normals from each point's K nearest map points (sf_map_estimate_normals_knn) instead of the
+0.25 m radius: every figure is then for the k-NN normals, and "normals" holds the share of map points with fewer than 3
+neighbours under both forms and the pose errors of the same scans registered against the radius normals.
+   python tools/city_bench.py [--map-points 10000000] [--batch 64] [--rings 64 128] [--prior 0.06:0.3 0.3:1.5] [--dynamic-boxes 40] [--robust tukey:0.1] [--covariance [--tunnel]] [--normals-knn 20]"""
 import argparse
 import json
 import os
@@ -62,6 +65,7 @@ def main():
     ap.add_argument("--dynamic-boxes", type=int, default=0, help="car-sized boxes in the ray-cast world that the map does not hold")
     ap.add_argument("--robust", default=None, help="KIND:K -- also register under this robust kernel (huber, cauchy, tukey, gm; K in metres)")
     ap.add_argument("--covariance", action="store_true", help="also register with sf_icp_set_covariance on: eigenvalues, flags, scans/s off vs on")
+    ap.add_argument("--normals-knn", type=int, default=0, metavar="K", help="map normals from the K nearest map points instead of the 0.25 m radius; reports both")
     ap.add_argument("--tunnel", action="store_true", help="the degenerate scene (synth.make_tunnel) instead of the city")
     args = ap.parse_args()
     mode = "p2plane"
@@ -77,6 +81,14 @@ def main():
     n_map = len(cloud)
     mp = api.Map(ctx, cloud, 0.25)
     mp.estimate_normals(0.25)
+    normals_info = None
+    if args.normals_knn > 0:
+        cnt_r = mp.download_normals()[1]
+        mp.estimate_normals_knn(args.normals_knn)
+        cnt_k = mp.download_normals()[1]
+        normals_info = dict(k=args.normals_knn, radius_m=0.25, share_below_3_radius=float((cnt_r < 3).mean()), share_below_3_knn=float((cnt_k < 3).mean()),
+                            share_below_6_radius=float((cnt_r < 6).mean()), neighbours_radius_median=float(np.median(cnt_r)), neighbours_radius_p99=float(np.percentile(cnt_r, 99)))
+        del cnt_r, cnt_k
     cell, dims = mp.cell_size()
     cars = synth.make_cars(boxes, [(0.0, 0.0)], args.dynamic_boxes, radius=(3.0, 20.0)) if args.dynamic_boxes > 0 else np.zeros((0, 6))
     world = np.r_[boxes, cars]
@@ -149,6 +161,16 @@ def main():
                                          flags=[int(c["flags"]) for c in covs], sigma_hat_m=[round(float(np.sqrt(c["sigma2_hat"])), 4) for c in covs],
                                          weakest_trans_dir_of_scan_0=[round(float(v), 4) for v in covs[0]["trans_dir"][0]])
                 icp.set_covariance(False)
+            if normals_info is not None:                             # the same scans against the radius normals
+                mp.estimate_normals(0.25)
+                icp.set_target(mp)
+                icp.set_source_batch(scans)
+                icp.set_initial_batch(inits)
+                rad = pose_errors(icp.align_batch(mode), truths)
+                mp.estimate_normals_knn(args.normals_knn)
+                out["normals"] = dict(normals_info, median_translation_err_m_knn=out["median_translation_err_m"], median_translation_err_m_radius=rad["median_translation_err_m"],
+                                      median_rotation_err_deg_knn=out["median_rotation_err_deg"], median_rotation_err_deg_radius=rad["median_rotation_err_deg"],
+                                      p95_translation_err_m_knn=out["p95_translation_err_m"], p95_translation_err_m_radius=rad["p95_translation_err_m"])
             icp.close()
             print(json.dumps(dict(workload="ring scans (%d x 2032 rays) vs a %.0f m synthetic %s, %d samples -> %d map points (voxel 0.1 m), %d scans in flight x %d points, "
                                            "%d %s iterations, prior error %.2f m / %.1f deg (1 sigma per axis)" % (rings, args.extent, "tunnel" if args.tunnel else "city", args.map_points, n_map, args.batch, n, args.iters,
