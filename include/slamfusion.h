@@ -240,6 +240,25 @@ int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, int with_cov
  * events around their kernel launches (not the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */
 int sf_map_profile_launches(sf_map *m, int on);
 int sf_map_last_launch_ms(sf_map *m, float *ms);
+/* Neighbour table: per indexed point one 32-byte entry -- the sorted positions of its up to 7 nearest other points
+ * (within just under one cell, among the 27 cells around its own) and a radius inside which there is no further point.  The
+ * launch list of O3D_P2P / P2PLANE alignments (neighbour reuse on, no window, unsharded, no robust kernel) consults it when a
+ * cached neighbour no longer certifies: the answer is the full search's, bit for bit, or the lane searches as before.
+ * sf_map_build_neighbour_table builds it now (kept until sf_map_build / sf_map_patch move the points; a normals pass keeps it).
+ * sf_map_set_neighbour_table: 0 never consulted, 2 always (an alignment builds a missing one first), 1 (default) auto: a table
+ * at hand is consulted; a missing one is built only for a batch of at least 700 000 queries against a map that has not been
+ * rebuilt or patched since it first served an alignment -- the owner of a growing map builds it when that is worthwhile.
+ * sf_map_neighbour_table_info: out = {present, entries, bytes, device time of the last build in whole ms (rounded up; -1 unless
+ * sf_map_profile_launches was on)}. */
+int sf_map_build_neighbour_table(sf_map *m);
+int sf_map_set_neighbour_table(sf_map *m, int mode);
+int sf_map_neighbour_table_info(sf_map *m, int64_t out[4]);
+/* the table as it lies on the device (parity tests): [n][8] uint32 -- seven sorted positions (0xffffffff: none), the radius's float bits */
+int sf_map_download_neighbour_table(sf_map *m, uint32_t *table, int64_t cap_entries, int64_t *n);
+/* test entry of the table look-up alone: query i starts from the indexed point at SORTED position seed_pos[i] (as
+ * sf_map_download_index lists them; negative or out of range: no seed).  served[i] = 1: idx / d2 are sf_map_nn's answer, bit for
+ * bit; served[i] = 0: undecided (idx = -1, d2 = +inf).  Needs a table and no window. */
+int sf_map_nn_seeded(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *served);
 
 /* ------------------------------------------------------------------ ICP */
 /* a13: ICPResult — icp_point_to_point.h:28-39 (+ float64 and diagnostics) */
@@ -425,6 +444,14 @@ int sf_icp_set_defer_search(sf_icp *icp, int on);
  * searched in place} -- zeros when the schedule did not run or the switch is off.  Whether it ran is recorded when the
  * alignment is enqueued: a later sf_icp_fetch_results that re-learns the freeze schedule does not change the answer. */
 int sf_icp_defer_stats(sf_icp *icp, int64_t out[2]);
+/* The first launch index (>= 1; default 2, the third launch) of an alignment from which lanes consult the map's neighbour
+ * table (sf_map_set_neighbour_table); negative: never.  Earlier launches move the pose too far for the table to serve many. */
+int sf_icp_set_neighbour_research(sf_icp *icp, int from_launch);
+/* of the last alignment enqueued, in profiled runs (sf_icp_profile_enable): {queries the table served, queries it was tried for
+ * and did not serve, waves that still searched}.  A wave of the deferring launch that holds more failing queries than the cap
+ * looks its unserved queries up a second time and counts them twice.  SF_ERR_STATE when profiling is off or its counters are
+ * full (1024 launches since sf_icp_profile_enable; enabling again resets them). */
+int sf_icp_neighbour_stats(sf_icp *icp, int64_t out[3]);
 /* Robust M-estimator kernel of SF_ICP_P2PLANE (REF_CPP and O3D_P2P ignore it, as Open3D's point-to-point estimator takes no
  * kernel).  With r = (y - p) . n the float64 point-to-plane residual of a pair (y the transformed source point, p / n the
  * neighbour and its normal) and the scale k > 0 in metres, every pair enters the normal equations with the weight w(r):

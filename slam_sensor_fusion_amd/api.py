@@ -486,6 +486,44 @@ class Map:
         _check(self.lib.sf_map_knn(self.h, _p(q), C.c_int64(len(q)), C.c_int(k), C.c_float(max_d2), _p(idx), _p(d2), _p(cnt)))
         return idx, d2, cnt
 
+    def build_neighbour_table(self):
+        """sf_map_build_neighbour_table: per indexed point its up to 7 nearest other points and a radius free of any further
+        point (include/slamfusion.h); kept until build / patch move the points."""
+        _check(self.lib.sf_map_build_neighbour_table(self.h))
+        return self
+
+    def set_neighbour_table(self, mode="auto"):
+        """sf_map_set_neighbour_table: "never", "auto" (default) or "always"."""
+        _check(self.lib.sf_map_set_neighbour_table(self.h, C.c_int({"never": 0, "auto": 1, "always": 2}[mode])))
+        return self
+
+    def neighbour_table_info(self):
+        """sf_map_neighbour_table_info -> dict(present, entries, bytes, build_ms); build_ms is -1 unless profile_launches was on."""
+        a = (C.c_int64 * 4)()
+        _check(self.lib.sf_map_neighbour_table_info(self.h, a))
+        return {"present": bool(a[0]), "entries": a[1], "bytes": a[2], "build_ms": a[3]}
+
+    def download_neighbour_table(self):
+        """The table as it lies on the device: (ids [n, 7] uint32 sorted positions, 0xffffffff = none; r [n] float32)."""
+        info = self.neighbour_table_info()
+        raw = np.zeros((max(info["entries"], 1), 8), np.uint32)
+        n = C.c_int64()
+        _check(self.lib.sf_map_download_neighbour_table(self.h, _p(raw), C.c_int64(len(raw)), C.byref(n)))
+        raw = raw[:n.value]
+        return raw[:, :7].copy(), raw[:, 7].copy().view(np.float32)
+
+    def nn_seeded(self, queries, seed_pos, max_d2=np.inf):
+        """sf_map_nn_seeded: the table look-up alone, from the indexed point at SORTED position seed_pos[i] (-1: none) ->
+        (idx, d2, served); served rows equal nn() bit for bit, the others are -1 / inf."""
+        q = _f32(queries).reshape(-1, 3)
+        s = np.ascontiguousarray(seed_pos, dtype=np.int32).reshape(-1)
+        assert len(s) == len(q)
+        idx = np.empty(len(q), np.int32)
+        d2 = np.empty(len(q), np.float32)
+        served = np.empty(len(q), np.uint8)
+        _check(self.lib.sf_map_nn_seeded(self.h, _p(q), C.c_int64(len(q)), _p(s), C.c_float(min(max_d2, 3.0e38)), _p(idx), _p(d2), _p(served)))
+        return idx, d2, served.astype(bool)
+
     def profile_launches(self, on=True):
         """sf_map_profile_launches: device events around the kernel launches of nn / knn / estimate_normals*."""
         _check(self.lib.sf_map_profile_launches(self.h, C.c_int(int(bool(on)))))
@@ -695,6 +733,16 @@ class Icp:
         """Deferred search of the frozen-pairs schedule (sf_icp_set_defer_search, default on): the stragglers of the last verifying
         launch before the first chance to freeze go to a dense pass instead of being searched in place."""
         _check(self.lib.sf_icp_set_defer_search(self.h, C.c_int(int(bool(on)))))
+
+    def set_neighbour_research(self, from_launch=2):
+        """sf_icp_set_neighbour_research: the first launch index (>= 1) that consults the map's neighbour table; negative: never."""
+        _check(self.lib.sf_icp_set_neighbour_research(self.h, C.c_int(int(from_launch))))
+
+    def neighbour_stats(self):
+        """Of the last alignment, profiled runs only (sf_icp_neighbour_stats)."""
+        a = (C.c_int64 * 3)()
+        _check(self.lib.sf_icp_neighbour_stats(self.h, a))
+        return {"served": a[0], "not_served": a[1], "waves_searched": a[2]}
 
     def defer_stats(self):
         """Of the last batched alignment (sf_icp_defer_stats): queries that went to the dense pass, waves that hit the cap."""

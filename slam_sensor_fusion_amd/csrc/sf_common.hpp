@@ -169,6 +169,10 @@ struct SfGrid {
     const float4 *pts;          // sorted by cell: x, y, z, bitcast(original index)
     const float4 *nrm;          // sorted normals (w = neighbour count) or nullptr
     int64_t n;
+    // the neighbour table (sf_map_build_neighbour_table) as ONE alignment uses it: sf_map::grid itself always carries
+    // nullptr, the launch list of an alignment that consults the table passes a copy with these two set (sf_icp.hip)
+    const uint4 *nbr;           // [n][2]: ids[7] (sorted positions, 0xffffffff: none) + radius, or nullptr
+    int nbr_from;               // first launch index of an alignment that consults it
 };
 
 struct sf_map {
@@ -195,6 +199,17 @@ struct sf_map {
     bool profile = false;
     hipEvent_t prof_ev[2] = {nullptr, nullptr};
     float last_launch_ms = -1.0f;
+    // the neighbour table: per indexed point its up to 7 nearest other points and a radius inside which there is no other
+    // (sf_map_build_neighbour_table).  nbr_stamp is the stamp of the points it describes (pts_stamp when valid, 0: none);
+    // everything that moves pts4 takes a new pts_stamp and so drops the table -- a normals pass does not.
+    sf::DevBuf nbr;
+    uint64_t pts_stamp = 0, nbr_stamp = 0;
+    int nbr_mode = 1;          // sf_map_set_neighbour_table: 0 never, 1 auto, 2 always
+    float nbr_build_ms = -1.0f;
+    hipEvent_t nbr_ev[2] = {nullptr, nullptr}; // around the last build, when sf_map_profile_launches is on
+    bool nbr_timed = false;    // ... recorded and not read yet
+    bool served = false;       // an alignment has been enqueued against this map ...
+    bool moved_after_serving = false; // ... and the index was rebuilt or patched after that (auto: no table for a growing map)
     int64_t n = 0;
     bool built = false, has_normals = false, has_cov = false;
     uint64_t generation = 0; // process-unique stamp of the index contents (build / normals): captured hipGraphs key on it
@@ -214,6 +229,11 @@ int ensure_scratch(sf_ctx *ctx, size_t bytes);
 // dst (device) <- src (any host memory), stream-ordered on the context's stream; src may be freed on return
 int upload_staged(sf_ctx *ctx, void *dst, const void *src, size_t bytes);
 uint64_t next_generation();
+// sf_map.hip: the index's points moved (build / patch): a new stamp, the neighbour table no longer describes them
+void map_points_moved(sf_map *m);
+// builds the neighbour table if it is missing (on the context's stream; never inside a capture)
+int map_neighbour_table_ensure(sf_map *m);
+inline bool map_neighbour_table_present(const sf_map *m) { return m->nbr.p != nullptr && m->nbr_stamp != 0 && m->nbr_stamp == m->pts_stamp; }
 inline void cloud_touch(sf_cloud *c) { c->stamp = next_generation(); c->merge.valid = false; }
 // children keep their context alive: any destruction order is safe
 void ctx_retain(sf_ctx *ctx);

@@ -493,7 +493,11 @@ constexpr int VERIFY_FROM_SEARCH = 4; // wide scans: from the fifth launch of an
 #ifndef NN_RED_WAVES
 #define NN_RED_WAVES 4
 #endif
+#ifndef SF_NBR_FROM
+#define SF_NBR_FROM 2 // measured against 1: profiles/LADDER.md round 7
+#endif
 constexpr int NN_STATS_SHARDS = 256; // counters of one profiled launch
+constexpr int NN_STATS_PER = 4;      // per shard: queries that searched, waves that searched, queries the neighbour table served, queries it was tried for and did not serve
 
 struct LanePair {
     double sx, sy, sz; // the transformed scan point (float64)
@@ -644,11 +648,31 @@ __device__ __forceinline__ LanePair make_pair(const QueryIn &q, const sf::NNHit 
     return P;
 }
 
+// One lane's look into the neighbour table (sf_nn.hpp: nn_research_table) for a query whose certificate failed with a cached
+// neighbour at hand (seed.j >= 0).  Served: hit / tn are the pair the search would have found and the cache entry is written
+// as the search path writes it -- E from the table's runner-up bound; the winner's normal is fetched only when the winner is
+// not the cached point.  Not served: nothing is touched.
+template <int MODE>
+__device__ __forceinline__ bool table_serve(const SfGrid &g, const QueryIn &q, float thr, float m_now, const sf::NNHit &seed, float4 *__restrict__ qcache, int64_t cache_n,
+                                            sf::NNHit &hit, float4 &tn)
+{
+    sf::NNHit th;
+    if (!sf::nn_research_table(g, q.qx, q.qy, q.qz, thr, seed, th)) return false;
+    const bool same = th.j == seed.j;
+    hit = th;
+    if (MODE == 2) tn = same ? make_float4(q.c2.x, q.c2.y, q.c2.z, 0.0f) : (th.j >= 0 ? g.nrm[th.j] : make_float4(0.f, 0.f, 0.f, 0.f));
+    const float en = fmaxf(sqrtf(th.lb2) * 0.9999f + m_now * 0.999998f - 1.0e-6f, 1.0e-30f);
+    if (!same) qcache[q.o] = make_float4(th.px, th.py, th.pz, __int_as_float(th.j));
+    if (MODE == 2) qcache[(size_t)cache_n + q.o] = make_float4(tn.x, tn.y, tn.z, en);
+    else reinterpret_cast<float *>(qcache + (size_t)cache_n)[q.o] = en;
+    return true;
+}
+
 template <int MODE, bool WINDOW, bool SHARD>
 __device__ __forceinline__ LanePair nn_pair(const SfGrid &g, const SfWindow &w, const float *__restrict__ X0x, const float *__restrict__ X0y, const float *__restrict__ X0z,
                                             int n, int b, const IcpState *S, float thr, float xlo, float xhi, const uint32_t *__restrict__ own_off,
                                             float4 *__restrict__ qcache, int64_t cache_n, int slot, int n_live, sf::WaveNN *ws, uint32_t *__restrict__ stats,
-                                            sf::PhaseClock *pc = nullptr)
+                                            sf::PhaseClock *pc = nullptr, bool try_table = true)
 {
     // once the scan's entries have been written (every lane writes its entry in the first launch after a (re)start,
     // searched or not, so the cache is never reset) the cache streams are requested together with the scan point: one
@@ -662,11 +686,33 @@ __device__ __forceinline__ LanePair nn_pair(const SfGrid &g, const SfWindow &w, 
     sf::NNHit hit;
     float4 tn;
     sf::NNHit seed;
-    const bool need = reuse_certificate(q.valid, qx, qy, qz, thr, m_now, q.e, q.c1, q.c2, hit, tn, seed);
+    bool need = reuse_certificate(q.valid, qx, qy, qz, thr, m_now, q.e, q.c1, q.c2, hit, tn, seed);
+    // The neighbour table (sf_nn.hpp: nn_research_table), from launch g.nbr_from of the alignment on: a lane whose
+    // certificate failed looks among its cached neighbour and that point's own nearest map points first.  Served: the pair
+    // and the cache entry are what the search would have left (E from the table's runner-up bound), and the lane needs no
+    // search.  Everything of this block is dead before the search branch.
+    if constexpr (!WINDOW && !SHARD) {
+        if (try_table && g.nbr != nullptr && S->n_research >= g.nbr_from) {
+            const bool tried = need && seed.j >= 0;
+            bool served = false;
+            if (tried) {
+                served = table_serve<MODE>(g, q, thr, m_now, seed, qcache, cache_n, hit, tn);
+                need = !served;
+            }
+            if (stats) { // profiling only
+                const unsigned long long tm = __ballot(tried), sm = __ballot(served);
+                if ((threadIdx.x & 63) == 0 && tm) {
+                    uint32_t *sh = stats + NN_STATS_PER * ((blockIdx.x + blockIdx.y * gridDim.x) & (NN_STATS_SHARDS - 1));
+                    atomicAdd(&sh[2], (uint32_t)__popcll(sm));
+                    atomicAdd(&sh[3], (uint32_t)__popcll(tm & ~sm));
+                }
+            }
+        }
+    }
     // every lane takes part in the search (lanes without a query still execute other lanes' tasks)
     const unsigned long long need_mask = __ballot(need);
     if (stats && (threadIdx.x & 63) == 0 && need_mask) { // profiling only (integer counters: order independent); sharded: one address would serialise 100 k waves
-        uint32_t *sh = stats + 2 * ((blockIdx.x + blockIdx.y * gridDim.x) & (NN_STATS_SHARDS - 1));
+        uint32_t *sh = stats + NN_STATS_PER * ((blockIdx.x + blockIdx.y * gridDim.x) & (NN_STATS_SHARDS - 1));
         atomicAdd(&sh[0], (uint32_t)__popcll(need_mask));
         atomicAdd(&sh[1], 1u);
     }
@@ -1965,6 +2011,23 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_df(SfGrid g, SfWin
             sf::NNHit hit, seed;
             float4 tn;
             need[u] = reuse_certificate(q.valid, q.qx, q.qy, q.qz, thr, m_now, q.e, q.c1, q.c2, hit, tn, seed);
+            // the neighbour table first: only what it cannot serve is listed (or searched in place)
+            if (g.nbr != nullptr && S->n_research >= g.nbr_from) {
+                const bool tried = need[u] && seed.j >= 0;
+                bool served = false;
+                if (tried) {
+                    served = table_serve<MODE>(g, q, thr, m_now, seed, qcache, cache_n, hit, tn);
+                    need[u] = !served;
+                }
+                if (stats) { // profiling only
+                    const unsigned long long tm = __ballot(tried), sm = __ballot(served);
+                    if (lane == 0 && tm) {
+                        uint32_t *sh = stats + NN_STATS_PER * ((blockIdx.x + blockIdx.y * gridDim.x) & (NN_STATS_SHARDS - 1));
+                        atomicAdd(&sh[2], (uint32_t)__popcll(sm));
+                        atomicAdd(&sh[3], (uint32_t)__popcll(tm & ~sm));
+                    }
+                }
+            }
             P[u] = make_pair(q, hit, tn); // (a failing query: no pair, a zero contribution)
         }
         uint32_t failing = 0;
@@ -1985,6 +2048,8 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_df(SfGrid g, SfWin
         }
     }
     if (!fast) {
+        // (a capped wave: its queries go through nn_pair from the start.  One the table served above certifies from the entry it
+        // wrote; one it did not serve is looked up again with the same outcome -- and counted again by the profiling counters)
         asm volatile("" ::: "memory"); // nothing loaded above stays live across the searches below
 #pragma unroll
         for (int u = 0; u < Q; ++u) {
@@ -2071,7 +2136,8 @@ __global__ __launch_bounds__(BLK, 2) void k_nn_deferred(SfGrid g, SfWindow w, co
             const uint32_t i = q0 + (uint32_t)threadIdx.x;
             if (q0 + (uint32_t)(wv * 64) < total) { // (whole waves; dealing a round out in equal shares to the four waves measured the same, 172 against 173 us)
                 const int slot = i < total ? (int)list[i] : n; // n: no query
-                const LanePair A1 = nn_pair<MODE, false, false>(g, w, X0x, X0y, X0z, n, b, S, thr, 0.0f, 0.0f, nullptr, qcache, cache_n, slot, n, &nn_ws[wv], stats);
+                // (no second look into the neighbour table: a listed query is one it did not serve in k_nn_red_df)
+                const LanePair A1 = nn_pair<MODE, false, false>(g, w, X0x, X0y, X0z, n, b, S, thr, 0.0f, 0.0f, nullptr, qcache, cache_n, slot, n, &nn_ws[wv], stats, nullptr, false);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     double v[16];
@@ -3038,13 +3104,16 @@ struct sf_icp {
         int64_t n = -1;
         const void *map = nullptr;
         uint64_t map_generation = 0, epochs = 0;
+        uint64_t nbr_stamp = 0; // the neighbour table this alignment consults (0: none), its address and the first launch that does
+        const void *nbr = nullptr;
+        int nbr_from = 0;
         float max_corr = 0, accept = 0, eps = 0;
         double robust_k = 0;
         double cov_prm[5] = {0, 0, 0, 0, 0};
         bool operator==(const GraphKey &o) const
         {
             return mode == o.mode && iters == o.iters && batch == o.batch && window == o.window && ordered == o.ordered && reuse == o.reuse && n == o.n && map == o.map &&
-                   map_generation == o.map_generation && epochs == o.epochs && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
+                   map_generation == o.map_generation && epochs == o.epochs && nbr_stamp == o.nbr_stamp && nbr == o.nbr && nbr_from == o.nbr_from && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
                    robust_kind == o.robust_kind && robust_k == o.robust_k && cov_on == o.cov_on && std::memcmp(cov_prm, o.cov_prm, sizeof(cov_prm)) == 0;
         }
     };
@@ -3153,6 +3222,10 @@ struct sf_icp {
     bool fz_from_auto = true;       // learnt from the last fetched alignment (sf_icp_fetch_results); sf_icp_set_freeze_params fixes it
     int fz_fetches = 0;             // fetched alignments since fz_from was last reset to its default (every FZ_PROBE_EVERY-th starts over)
     int fz_step = 0;                // stepping paths: launches since the pass began
+    int nbr_from = SF_NBR_FROM;     // sf_icp_set_neighbour_research: first launch index that consults the map's neighbour table (negative: off)
+    bool nbr_active = false;        // the alignment being enqueued consults it (nbr_prepare)
+    int64_t nbr_stats_first = 0;    // nn_stats slot of the last alignment's first launch (sf_icp_neighbour_stats)
+    uint64_t mark_nbr_stamp = 0;
     int defer = 1;                  // sf_icp_set_defer_search: the verifying launches of the frozen-pairs schedule list their stragglers for a dense pass (k_nn_red_df)
     bool df_planned = false;        // the last alignment's launch list held a deferring launch (fz_from as it stood THEN: a fetch may re-learn it)
     int64_t nn_stats_used = 0;
@@ -3591,6 +3664,7 @@ sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
     k.n = (mode == SF_ICP_REF_CPP && ss.batch == 1) ? -ss.n_cap : ss.n; // REF_CPP, one scan: any count of the same capacity replays
     k.map = (const void *)icp->map;
     k.map_generation = icp->map->generation;
+    if (icp->nbr_active) { k.nbr_stamp = icp->map->nbr_stamp; k.nbr = icp->map->nbr.p; k.nbr_from = icp->nbr_from; }
     k.robust_kind = robust_on(icp, mode) ? icp->robust_kind : SF_ROBUST_NONE; k.robust_k = robust_on(icp, mode) ? icp->robust_k : 0.0; // (passed by value to the robust kernels)
     k.cov_on = icp->cov_on;
     if (icp->cov_on) { const double cp[5] = {icp->cov_arg.sensor_sigma, icp->cov_arg.thr_t, icp->cov_arg.thr_r, icp->cov_arg.infl_t, icp->cov_arg.infl_r}; std::memcpy(k.cov_prm, cp, sizeof(cp)); }
@@ -3600,6 +3674,40 @@ sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
     k.epochs = (uint64_t)ss.plane;
     for (const sf::DevBuf *b : bufs) k.epochs = (k.epochs * 1000003ull + b->epoch) * 1000003ull + (uint64_t)(uintptr_t)b->p; // (the address too: the two source sets take turns under one lane's graph)
     return k;
+}
+
+// the map's grid as this alignment's launches see it: with the neighbour table when the alignment consults it
+SfGrid grid_for(const sf_icp *icp)
+{
+    SfGrid g = icp->map->grid;
+    g.nbr = icp->nbr_active ? icp->map->nbr.as<uint4>() : nullptr;
+    g.nbr_from = icp->nbr_from;
+    return g;
+}
+
+// Whether the alignment about to be enqueued consults the map's neighbour table, and -- before any lane forks and outside
+// any capture -- the build of a table that is wanted and missing.  The table is consulted on the launch list of O3D_P2P /
+// P2PLANE with the neighbour reuse on, whole map, unsharded, plain pairs.  sf_map_set_neighbour_table: never; always (built
+// when missing); auto: a table at hand is used, a missing one is built only for a batch of the automatic frozen-pairs size
+// against a map that has not been rebuilt or patched since it first served an alignment (a growing map never pays a
+// build per growth step).  Configuration alone decides: nothing here counts calls or remembers earlier alignments.
+int nbr_prepare(sf_icp *icp, int mode)
+{
+    sf_map *m = icp->map;
+    const SrcSet &ss = icp->src();
+    icp->nbr_active = false;
+    const bool path = !icp->last_fused && (mode == SF_ICP_P2PLANE || mode == SF_ICP_O3D_P2P) && icp->reuse && m->window.kind == 0 && !icp->shard && !robust_on(icp, mode) &&
+                      icp->nbr_from >= 1 && m->nbr_mode != 0 && m->grid.n > 0 && (mode != SF_ICP_P2PLANE || m->grid.nrm != nullptr);
+    if (path) {
+        bool present = sf::map_neighbour_table_present(m);
+        if (!present && (m->nbr_mode == 2 || (ss.n * ss.batch >= FREEZE_AUTO_MIN_QUERIES && !m->moved_after_serving))) {
+            SF_TRY(sf::map_neighbour_table_ensure(m));
+            present = true;
+        }
+        icp->nbr_active = present;
+    }
+    m->served = true;
+    return SF_OK;
 }
 
 float o3d_thr(const sf_icp *icp) { return (float)((double)icp->prm.max_corr * (double)icp->prm.max_corr); }
@@ -3620,7 +3728,7 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
     hipStream_t s = icp->ctx->stream;
     ProfScope ps(icp);
     uint32_t *stats = nullptr;
-    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + 2 * NN_STATS_SHARDS * icp->nn_stats_used++;
+    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
     const bool win = m->window.kind != 0;
     if (MODE == 2 && robust_on(icp, MODE)) {
         const RobustArg rk = robust_arg(icp);
@@ -3636,7 +3744,7 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
         return;
     }
 #define SF_LAUNCH_NNRED_Q(W, S, QQ)                                                                                                                              \
-    hipLaunchKernelGGL((k_nn_red<MODE, W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb, \
+    hipLaunchKernelGGL((k_nn_red<MODE, W, S, QQ>), grid, blk, 0, s, grid_for(icp), m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb, \
                        icp->own_off.as<uint32_t>(), icp->reuse ? ln.qcache.as<float4>() : nullptr, icp->cache_n, stats)
 #define SF_LAUNCH_NNRED(W, S)                                  \
     do {                                                       \
@@ -3745,7 +3853,7 @@ void launch_nn_deferred(sf_icp *icp, uint32_t *stats)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    hipLaunchKernelGGL((k_nn_deferred<SF_WIDE_QPL>), dim3((unsigned)FZ_FEW, (unsigned)ss.batch), dim3(BLK), 0, icp->ctx->stream, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2),
+    hipLaunchKernelGGL((k_nn_deferred<SF_WIDE_QPL>), dim3((unsigned)FZ_FEW, (unsigned)ss.batch), dim3(BLK), 0, icp->ctx->stream, grid_for(icp), m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2),
                        (int)ss.n, ln.state.as<IcpState>(), o3d_thr(icp), ss.nblocks_nn, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
 }
 
@@ -3758,8 +3866,8 @@ void launch_nn_red_df(sf_icp *icp)
     const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), blk(BLK);
     ProfScope ps(icp);
     uint32_t *stats = nullptr;
-    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + 2 * NN_STATS_SHARDS * icp->nn_stats_used++;
-    hipLaunchKernelGGL((k_nn_red_df<SF_WIDE_QPL>), grid, blk, 0, icp->ctx->stream, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(),
+    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
+    hipLaunchKernelGGL((k_nn_red_df<SF_WIDE_QPL>), grid, blk, 0, icp->ctx->stream, grid_for(icp), m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(),
                        o3d_thr(icp), ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
     launch_nn_deferred(icp, stats);
 }
@@ -3783,7 +3891,7 @@ void launch_nn_red_fz(sf_icp *icp, bool sharded, bool few)
     A.qcache = ln.qcache.as<float4>();
     A.cache_n = icp->cache_n;
     A.stats = nullptr;
-    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) A.stats = icp->nn_stats.as<uint32_t>() + 2 * NN_STATS_SHARDS * icp->nn_stats_used++;
+    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) A.stats = icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
     A.fz = ln.fz_state.as<FreezeState>();
     A.mom_part = ln.fz_part.as<double>();
     A.act_cnt = ln.fz_cnt.as<uint32_t>();
@@ -3791,11 +3899,11 @@ void launch_nn_red_fz(sf_icp *icp, bool sharded, bool few)
     A.act_all = ln.fz_all.as<uint32_t>();
     hipStream_t s = icp->ctx->stream;
     if (few) {
-        if (sharded) hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, true>), grid_few, blk, 0, s, m->grid, m->window, A);
-        else hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, false>), grid_few, blk, 0, s, m->grid, m->window, A);
+        if (sharded) hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, true>), grid_few, blk, 0, s, grid_for(icp), m->window, A);
+        else hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, false>), grid_few, blk, 0, s, grid_for(icp), m->window, A);
     } else {
-        if (sharded) hipLaunchKernelGGL((k_nn_red_fz<SF_WIDE_QPL, true>), grid_full, blk, 0, s, m->grid, m->window, A);
-        else hipLaunchKernelGGL((k_nn_red_fz<SF_WIDE_QPL, false>), grid_full, blk, 0, s, m->grid, m->window, A);
+        if (sharded) hipLaunchKernelGGL((k_nn_red_fz<SF_WIDE_QPL, true>), grid_full, blk, 0, s, grid_for(icp), m->window, A);
+        else hipLaunchKernelGGL((k_nn_red_fz<SF_WIDE_QPL, false>), grid_full, blk, 0, s, grid_for(icp), m->window, A);
     }
 }
 
@@ -4432,6 +4540,32 @@ extern "C" int sf_icp_set_defer_search(sf_icp *icp, int on)
     return SF_OK;
 }
 
+extern "C" int sf_icp_set_neighbour_research(sf_icp *icp, int from_launch)
+{
+    SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
+    SF_CHECK(from_launch != 0, SF_ERR_INVALID, "from_launch must be at least 1 (the first launch has no cached neighbours), or negative for off");
+    icp->nbr_from = from_launch < 0 ? -1 : from_launch;
+    return SF_OK;
+}
+
+// {queries the table served, queries it was tried for and did not serve, waves that still searched} over the launches of
+// the last alignment enqueued with sf_icp_align_batch_async; counted in profiled runs only (sf_icp_profile_enable)
+extern "C" int sf_icp_neighbour_stats(sf_icp *icp, int64_t out[3])
+{
+    SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(icp->profiling && icp->nn_stats.p, SF_ERR_STATE, "the neighbour statistics are counted in profiled runs (sf_icp_profile_enable)");
+    SF_CHECK(icp->nn_stats_used < sf_icp::NN_STATS_CAP, SF_ERR_STATE, "the profiling counters are full (%lld launches since sf_icp_profile_enable): enable profiling again to reset them", (long long)sf_icp::NN_STATS_CAP);
+    SF_HIP(hipStreamSynchronize(icp->ctx->stream));
+    out[0] = out[1] = out[2] = 0;
+    const int64_t first = icp->nbr_stats_first, used = icp->nn_stats_used;
+    if (used <= first) return SF_OK;
+    const size_t per = (size_t)NN_STATS_PER * NN_STATS_SHARDS;
+    std::vector<uint32_t> st(per * (size_t)(used - first), 0u);
+    SF_HIP(hipMemcpy(st.data(), icp->nn_stats.as<uint32_t>() + per * (size_t)first, sizeof(uint32_t) * st.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < st.size(); i += NN_STATS_PER) { out[0] += st[i + 2]; out[1] += st[i + 3]; out[2] += st[i + 1]; }
+    return SF_OK;
+}
+
 extern "C" int sf_icp_defer_stats(sf_icp *icp, int64_t out[2])
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
@@ -4615,7 +4749,7 @@ struct LaneScope {
         // the mark: where the context's stream stood when the inputs last changed (taken before anything of this alignment is enqueued)
         const sf_map *m = icp->map;
         // (the initial poses are not part of it: they travel in the kernel arguments or through the lane's own copy, on the lane's stream)
-        const bool same = icp->mark_valid && icp->mark_src_version == icp->src_version && icp->mark_map == (const void *)m && icp->mark_map_generation == m->generation &&
+        const bool same = icp->mark_valid && icp->mark_src_version == icp->src_version && icp->mark_map == (const void *)m && icp->mark_map_generation == m->generation && icp->mark_nbr_stamp == m->nbr_stamp &&
                           std::memcmp(&icp->mark_window, &m->window, sizeof(SfWindow)) == 0;
         if (!same) {
             if (hipEventRecord(icp->main_mark, main) != hipSuccess) { rc = SF_ERR_HIP; return; }
@@ -4623,6 +4757,7 @@ struct LaneScope {
             icp->mark_src_version = icp->src_version;
             icp->mark_map = (const void *)m;
             icp->mark_map_generation = m->generation;
+            icp->mark_nbr_stamp = m->nbr_stamp;
             icp->mark_window = m->window;
         }
         if (!icp->unfetched && !icp->src_ahead) { // nothing of this object in flight: the context's stream, the lane at hand
@@ -4692,6 +4827,8 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     icp->last_fused = fused_eligible(icp, mode);
     icp->df_planned = !icp->last_fused && defer_planned(icp, mode);
     SF_TRY(order_lut_prepare(icp));
+    SF_TRY(nbr_prepare(icp, mode));
+    icp->nbr_stats_first = icp->nn_stats_used;
     // the launch list takes a lane (see sf_icp::Lane); the single launch, profiled runs and a count left on the device stay on the context's stream
     const bool beside = icp->unfetched; // an alignment of this object is still unfetched: this one may run beside it
     LaneScope lanes(icp, icp->pipeline != 0 && !icp->last_fused && !icp->profiling && !ss.n_on_device);
@@ -5004,6 +5141,8 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = false;
+    icp->nbr_active = false; // (the stepping paths search as always)
+    icp->map->served = true;
     if (first) SF_TRY(step_adopt_source(icp)); // (sf_icp_align_group and the all-reduce form of sf_icp_align_sharded_async start here too)
     if (first == 1) lane_describe(icp, mode, false);
     if (first) icp->df_planned = defer_planned(icp, mode);
@@ -5072,14 +5211,14 @@ extern "C" int sf_icp_profile_read_launches(sf_icp *icp, float *ms, uint32_t *se
     if (n) *n = have;
     if (!ms && !searched_queries && !searched_waves) return SF_OK;
     SF_CHECK(cap >= have, SF_ERR_INVALID, "buffer too small: %lld < %lld", (long long)cap, (long long)have);
-    const size_t per = (size_t)2 * NN_STATS_SHARDS;
+    const size_t per = (size_t)NN_STATS_PER * NN_STATS_SHARDS;
     std::vector<uint32_t> st(per * (size_t)std::max<int64_t>(icp->nn_stats_used, 1), 0u);
     if (icp->nn_stats_used > 0) SF_HIP(hipMemcpy(st.data(), icp->nn_stats.p, sizeof(uint32_t) * per * (size_t)icp->nn_stats_used, hipMemcpyDeviceToHost));
     for (int64_t k = 0; k < have; ++k) {
         if (ms) ms[k] = icp->prof_each[(size_t)k];
         uint64_t q = 0, w = 0;
         if (k < icp->nn_stats_used && icp->last_mode != SF_ICP_REF_CPP)
-            for (int sh = 0; sh < NN_STATS_SHARDS; ++sh) { q += st[per * (size_t)k + 2 * sh]; w += st[per * (size_t)k + 2 * sh + 1]; }
+            for (int sh = 0; sh < NN_STATS_SHARDS; ++sh) { q += st[per * (size_t)k + NN_STATS_PER * sh]; w += st[per * (size_t)k + NN_STATS_PER * sh + 1]; }
         if (searched_queries) searched_queries[k] = (uint32_t)q;
         if (searched_waves) searched_waves[k] = (uint32_t)w;
     }
@@ -5126,6 +5265,8 @@ int shard_step_p2p(sf_icp *icp, int mode, int first, const sf::P2pView &view)
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = false;
+    icp->nbr_active = false;
+    icp->map->served = true;
     if (first) SF_TRY(order_lut_prepare(icp));
     if (first == 1) SF_TRY(launch_state_init(icp));
     if (first) SF_TRY(shard_build(icp, first == 2));
@@ -5285,8 +5426,8 @@ extern "C" int sf_icp_profile_enable(sf_icp *icp, int on)
     for (auto &v : icp->prof_phase) v.clear();
     icp->nn_stats_used = 0;
     if (on) {
-        SF_TRY(icp->nn_stats.reserve(sizeof(uint32_t) * 2 * NN_STATS_SHARDS * sf_icp::NN_STATS_CAP));
-        SF_HIP(hipMemsetAsync(icp->nn_stats.p, 0, sizeof(uint32_t) * 2 * NN_STATS_SHARDS * sf_icp::NN_STATS_CAP, icp->ctx->stream));
+        SF_TRY(icp->nn_stats.reserve(sizeof(uint32_t) * NN_STATS_PER * NN_STATS_SHARDS * sf_icp::NN_STATS_CAP));
+        SF_HIP(hipMemsetAsync(icp->nn_stats.p, 0, sizeof(uint32_t) * NN_STATS_PER * NN_STATS_SHARDS * sf_icp::NN_STATS_CAP, icp->ctx->stream));
     }
     return SF_OK;
 }

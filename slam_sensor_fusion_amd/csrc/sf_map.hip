@@ -188,6 +188,9 @@ extern "C" void sf_map_destroy(sf_map *m)
     m->nrm4_alt.release(); m->cov6_alt.release(); m->carry_tmp.release(); m->carry_list.release();
     for (hipEvent_t ev : m->prof_ev)
         if (ev) { hipError_t e2 = hipEventDestroy(ev); (void)e2; }
+    for (hipEvent_t ev : m->nbr_ev)
+        if (ev) { hipError_t e2 = hipEventDestroy(ev); (void)e2; }
+    m->nbr.release();
     sf_ctx *ctx = m->ctx;
     delete m;
     sf::ctx_release(ctx);
@@ -308,6 +311,7 @@ extern "C" int sf_map_build(sf_map *m, sf_cloud *cloud, float cell)
     m->built = true;
     m->has_cov = false;
     m->generation = sf::next_generation();
+    sf::map_points_moved(m);
     m->h_exact = h;
     for (int d = 0; d < 3; ++d) { m->src_mn[d] = n_valid > 0 ? mm.mn[d] : 0.0f; m->src_mx[d] = n_valid > 0 ? mm.mx[d] : 0.0f; }
     m->src_stamp = cloud->stamp;
@@ -643,6 +647,7 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     G.n = n_out;
     m->has_cov = false;
     m->generation = sf::next_generation();
+    sf::map_points_moved(m);
     for (int d = 0; d < 3; ++d) { m->src_mn[d] = new_mn[d]; m->src_mx[d] = new_mx[d]; }
     m->src_stamp = cloud->stamp;
     m->carry_info[3] = m->n;
@@ -794,6 +799,191 @@ extern "C" int sf_map_nn(sf_map *m, const float *queries, int64_t n, float max_d
     SF_HIP(hipMemcpyAsync(d2, dd.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
     prof_read(m);
+    return SF_OK;
+}
+
+// ------------------------------------------------------------------ the neighbour table
+// Per indexed point p one 32-byte entry: the sorted positions of the up to 7 OTHER points with the smallest key
+// hit_key(l2_simple(p, x), position) among the points of the 27 cells around p's cell with d2 < cap^2, 0xffffffff where
+// there is none, and a radius r that bounds from below the distance from p to every point that is neither p nor listed.
+// cap = safe_gap(h, gap_eps) * 0.999, the search's own convention: everything outside the 27-cell block is at least a cell
+// (less the rounding of the grid coordinates) away.  Seven listed: r = sqrt(d2 of the 7th) * 0.9999; fewer: r = cap.
+// One lane per point; the seven keys stay sorted in registers by an unrolled insertion.  The entry depends on the index
+// alone: the key order is total, whatever order the cells are walked in.
+namespace {
+__global__ __launch_bounds__(256) void k_neighbour_table(SfGrid g, uint4 *__restrict__ tab)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= g.n) return;
+    const float4 p = g.pts[j];
+    const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
+    const int cx = (int)fminf(fmaxf(floorf((p.x - g.org[0]) * g.inv_h), 0.0f), (float)(nx - 1));
+    const int cy = (int)fminf(fmaxf(floorf((p.y - g.org[1]) * g.inv_h), 0.0f), (float)(ny - 1));
+    const int cz = (int)fminf(fmaxf(floorf((p.z - g.org[2]) * g.inv_h), 0.0f), (float)(nz - 1));
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, nx - 1);
+    const int y0 = max(cy - 1, 0), y1 = min(cy + 1, ny - 1);
+    const int z0 = max(cz - 1, 0), z1 = min(cz + 1, nz - 1);
+    const float cap = sf::safe_gap(g.h, g.gap_eps) * 0.999f;
+    const float cap2 = cap * cap;
+    unsigned long long key[sf::NBR_K];
+#pragma unroll
+    for (int i = 0; i < sf::NBR_K; ++i) key[i] = ~0ull;
+    for (int z = z0; z <= z1; ++z)
+        for (int y = y0; y <= y1; ++y) {
+            const size_t row = ((size_t)z * ny + y) * nx;
+            const uint32_t a = g.cell_start[row + x0], b = g.cell_start[row + x1 + 1];
+            for (uint32_t k = a; k < b; ++k) {
+                const float4 q = g.pts[k];
+                const float d2 = sf::l2_simple(p.x, p.y, p.z, q.x, q.y, q.z);
+                if (k == (uint32_t)j || !(d2 < cap2)) continue;
+                unsigned long long v = sf::hit_key(d2, (int)k);
+                if (v >= key[sf::NBR_K - 1]) continue;
+#pragma unroll
+                for (int i = 0; i < sf::NBR_K; ++i) { // v sinks to its place, the larger keys move down one, the largest falls out
+                    const unsigned long long lo = v < key[i] ? v : key[i], hi = v < key[i] ? key[i] : v;
+                    key[i] = lo;
+                    v = hi;
+                }
+            }
+        }
+    const bool full = key[sf::NBR_K - 1] != ~0ull;
+    const float r = full ? sqrtf(__uint_as_float((uint32_t)(key[sf::NBR_K - 1] >> 32))) * 0.9999f : cap;
+    // (an absent slot's key is all ones: its low half is the "none" id)
+    tab[2 * (size_t)j] = make_uint4((uint32_t)key[0], (uint32_t)key[1], (uint32_t)key[2], (uint32_t)key[3]);
+    tab[2 * (size_t)j + 1] = make_uint4((uint32_t)key[4], (uint32_t)key[5], (uint32_t)key[6], __float_as_uint(r));
+}
+
+// the re-search of sf_nn.hpp on its own, one query per lane: sf_map_nn_seeded
+__global__ __launch_bounds__(256) void k_map_nn_seeded(SfGrid g, const float *__restrict__ q, int64_t n, const int32_t *__restrict__ seed_pos, float thr, int32_t *__restrict__ idx,
+                                                       float *__restrict__ d2, uint8_t *__restrict__ served)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
+    const int32_t s = seed_pos[i];
+    bool ok = false;
+    sf::NNHit hit{0.0f, -1, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (s >= 0 && (int64_t)s < g.n && isfinite(qx) && isfinite(qy) && isfinite(qz)) {
+        const float4 p = g.pts[s];
+        const sf::NNHit seed{sf::l2_simple(qx, qy, qz, p.x, p.y, p.z), s, p.x, p.y, p.z, 0.0f};
+        ok = sf::nn_research_table(g, qx, qy, qz, thr, seed, hit);
+    }
+    const bool has = ok && hit.j >= 0;
+    idx[i] = has ? (int32_t)__float_as_uint(g.pts[hit.j].w) : -1;
+    d2[i] = has ? hit.d2 : INFINITY;
+    served[i] = ok ? 1 : 0;
+}
+} // namespace
+
+namespace sf {
+void map_points_moved(sf_map *m)
+{
+    m->pts_stamp = next_generation();
+    m->nbr_stamp = 0; // the table (its allocation is kept) describes other points
+    if (m->served) m->moved_after_serving = true;
+}
+
+int map_neighbour_table_ensure(sf_map *m)
+{
+    if (map_neighbour_table_present(m)) return SF_OK;
+    sf_ctx *ctx = m->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    SF_TRY(m->nbr.reserve(sizeof(uint4) * 2 * (size_t)std::max<int64_t>(m->grid.n, 1)));
+    m->nbr_timed = false;
+    if (m->profile) {
+        bool ok = true;
+        for (int i = 0; i < 2; ++i)
+            if (!m->nbr_ev[i] && hipEventCreate(&m->nbr_ev[i]) != hipSuccess) { m->nbr_ev[i] = nullptr; ok = false; }
+        m->nbr_timed = ok && hipEventRecord(m->nbr_ev[0], ctx->stream) == hipSuccess;
+    }
+    SfGrid g = m->grid;
+    g.nbr = nullptr;
+    if (g.n > 0) hipLaunchKernelGGL(k_neighbour_table, dim3(nblk(g.n)), dim3(256), 0, ctx->stream, g, m->nbr.as<uint4>());
+    SF_HIP(hipGetLastError());
+    if (m->nbr_timed) m->nbr_timed = hipEventRecord(m->nbr_ev[1], ctx->stream) == hipSuccess;
+    m->nbr_build_ms = -1.0f;
+    m->nbr_stamp = m->pts_stamp;
+    return SF_OK;
+}
+} // namespace sf
+
+extern "C" int sf_map_build_neighbour_table(sf_map *m)
+{
+    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
+    SF_TRY(sf::map_neighbour_table_ensure(m));
+    SF_HIP(hipStreamSynchronize(m->ctx->stream));
+    return SF_OK;
+}
+
+extern "C" int sf_map_set_neighbour_table(sf_map *m, int mode)
+{
+    SF_CHECK(m, SF_ERR_INVALID, "map is NULL");
+    SF_CHECK(mode >= 0 && mode <= 2, SF_ERR_INVALID, "mode must be 0 (never), 1 (auto) or 2 (always)");
+    m->nbr_mode = mode;
+    return SF_OK;
+}
+
+// out: present (0 / 1), entries, bytes, the last build's device time in whole ms (rounded up; -1: not timed -- builds are timed
+// while sf_map_profile_launches is on)
+extern "C" int sf_map_neighbour_table_info(sf_map *m, int64_t out[4])
+{
+    SF_CHECK(m && out, SF_ERR_INVALID, "bad arguments");
+    const bool present = m->built && sf::map_neighbour_table_present(m);
+    if (m->nbr_timed) { // (timed builds only: sf_map_profile_launches)
+        SF_HIP(hipStreamSynchronize(m->ctx->stream));
+        float ms = -1.0f;
+        if (hipEventElapsedTime(&ms, m->nbr_ev[0], m->nbr_ev[1]) == hipSuccess) m->nbr_build_ms = ms;
+        m->nbr_timed = false;
+    }
+    out[0] = present ? 1 : 0;
+    out[1] = present ? m->grid.n : 0;
+    out[2] = present ? (int64_t)(sizeof(uint4) * 2) * m->grid.n : 0;
+    out[3] = m->nbr_build_ms >= 0.0f ? (int64_t)std::ceil((double)m->nbr_build_ms) : -1; // whole milliseconds, rounded up; -1: not timed
+    return SF_OK;
+}
+
+// the table as it lies in HBM, for the parity tests: [n][8] uint32 (seven sorted positions, the radius's float bits)
+extern "C" int sf_map_download_neighbour_table(sf_map *m, uint32_t *table, int64_t cap_entries, int64_t *n)
+{
+    SF_CHECK(m && m->built && n, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(sf::map_neighbour_table_present(m), SF_ERR_STATE, "no neighbour table (sf_map_build_neighbour_table)");
+    *n = m->grid.n;
+    if (!table || m->grid.n == 0) return SF_OK;
+    SF_CHECK(cap_entries >= m->grid.n, SF_ERR_INVALID, "buffer too small");
+    SF_HIP(hipSetDevice(m->ctx->device));
+    SF_HIP(hipMemcpyAsync(table, m->nbr.p, sizeof(uint32_t) * 8 * (size_t)m->grid.n, hipMemcpyDeviceToHost, m->ctx->stream));
+    SF_HIP(hipStreamSynchronize(m->ctx->stream));
+    return SF_OK;
+}
+
+// Test entry of the table re-search: query i starts from the indexed point at SORTED position seed_pos[i] (-1, or anything
+// outside the index: no seed).  served[i] = 1: idx / d2 are sf_map_nn's answer for the query, bit for bit (original ids,
+// -1 / +inf when nothing lies within max_d2); served[i] = 0: the table could not decide it (idx = -1, d2 = +inf).
+extern "C" int sf_map_nn_seeded(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *served)
+{
+    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
+    SF_CHECK(n >= 0 && (n == 0 || (queries && seed_pos && idx && d2 && served)), SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(sf::map_neighbour_table_present(m), SF_ERR_STATE, "no neighbour table (sf_map_build_neighbour_table)");
+    SF_CHECK(m->window.kind == 0, SF_ERR_STATE, "the neighbour table knows no window");
+    if (n == 0) return SF_OK;
+    sf_ctx *ctx = m->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    sf::DevBuf dq, ds, di, dd, dv;
+    SF_TRY(dq.reserve(sizeof(float) * 3 * (size_t)n));
+    SF_TRY(ds.reserve(sizeof(int32_t) * (size_t)n));
+    SF_TRY(di.reserve(sizeof(int32_t) * (size_t)n));
+    SF_TRY(dd.reserve(sizeof(float) * (size_t)n));
+    SF_TRY(dv.reserve((size_t)n));
+    SF_HIP(hipMemcpyAsync(dq.p, queries, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    SF_HIP(hipMemcpyAsync(ds.p, seed_pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    SfGrid g = m->grid;
+    g.nbr = m->nbr.as<uint4>();
+    hipLaunchKernelGGL(k_map_nn_seeded, dim3(nblk(n)), dim3(256), 0, ctx->stream, g, dq.as<float>(), n, ds.as<int32_t>(), max_d2, di.as<int32_t>(), dd.as<float>(), dv.as<uint8_t>());
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(idx, di.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(d2, dd.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(served, dv.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;
 }
 

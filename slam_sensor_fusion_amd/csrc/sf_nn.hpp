@@ -155,6 +155,8 @@ __device__ __forceinline__ float4 load_point(const SfGrid &g, uint32_t j, bool v
     const u4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, valid ? (int)(j * 16u) : -1, 0, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
+#else
+__device__ __forceinline__ float4 load_point(const SfGrid &g, uint32_t j, bool valid) { return g.pts[valid ? j : 0u]; }
 #endif
 
 template <bool WINDOW, bool TRACK = false>
@@ -849,6 +851,86 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
         unres = __ballot(more);
     }
     return hit;
+}
+
+// ------------------------------------------------------------------ re-search from the map's own neighbour table
+// The map does not move: a query whose cached neighbour p no longer certifies almost always ends at p again or at one
+// of p's own nearest map points.  Entry jc of the table (sf_map_build_neighbour_table) lists the up to 7 map points
+// nearest to p and a radius r with |x - p| >= r for every map point x that is neither p nor listed.  The candidates are p
+// and the listed points; the winner is the lexicographic minimum of (d2, j) among them, as in every search form.
+// Served iff (|q - p| + |q - best|) * 1.0001 + 2e-6 < r.  Then for every x outside the candidate set
+// |x - q| >= |x - p| - |q - p| >= r - |q - p| > |q - best| (triangle inequality), so the full search cannot prefer x, ties
+// included: the result is nn_search_wave's, bit for bit.  Margins: q, p, x are float32 values and l2_simple of two of them
+// is within 4 ulp of the real squared distance, its square root within 2.5e-7 relative; 1e-4 relative + 2e-6 absolute on
+// the left covers both distances of the sum and the one comparison of float32 d2 values the search itself would make.
+// The runner-up bound of a served query: the second smallest candidate distance and r - |q - p|, both rounded down -- and
+// the best candidate's own distance too when it is not under the threshold (no neighbour: the bound then covers every point).
+// Early end: with five or more listed, the rule is first tried on p and the first four with r4 = |x4 - p| * 0.9999 in place of r
+// (everything else is at least that far from p, by the key order of the list); it serves the same queries -- r4 <= r and the
+// winner is proven among the five -- with a bound from r4.
+// Pure: no LDS, no wave cooperation; the lane either takes the result or searches as before with its seed unchanged.
+constexpr uint32_t NBR_NONE = 0xffffffffu;
+constexpr int NBR_K = 7;
+
+__device__ __forceinline__ void nbr_fold(const float4 &p, uint32_t id, float qx, float qy, float qz, unsigned long long &best, float4 &bp, float &second)
+{
+    const float d2 = l2_simple(qx, qy, qz, p.x, p.y, p.z);
+    const unsigned long long key = hit_key(d2, (int)id);
+    const bool valid = id != NBR_NONE;
+    const bool take = valid && key < best;
+    // whichever of (the best so far, this candidate) loses is a runner-up
+    const float lose = take ? __uint_as_float((uint32_t)(best >> 32)) : (valid ? d2 : 3.0e38f);
+    second = fminf(second, lose);
+    if (take) { best = key; bp = p; }
+}
+
+// seed: the cached neighbour (seed.j >= 0) with its current squared distance, as reuse_certificate leaves it
+__device__ __forceinline__ bool nn_research_table(const SfGrid &g, float qx, float qy, float qz, float thr, const NNHit &seed, NNHit &out)
+{
+    const uint4 e0 = g.nbr[2 * (size_t)seed.j], e1 = g.nbr[2 * (size_t)seed.j + 1];
+    const float r = __uint_as_float(e1.w);
+    unsigned long long best = hit_key(seed.d2, seed.j);
+    float4 bp = make_float4(seed.px, seed.py, seed.pz, 0.0f);
+    float second = 3.0e38f;
+    const float dp = sqrtf(seed.d2);
+    float rr = r;
+    bool rest = e1.x != NBR_NONE; // (key order: no fifth, no sixth or seventh)
+    { // two batches (4 + 3): at most four candidates' coordinates live at a time
+        const float4 p0 = load_point(g, e0.x, e0.x != NBR_NONE), p1 = load_point(g, e0.y, e0.y != NBR_NONE), p2 = load_point(g, e0.z, e0.z != NBR_NONE),
+                     p3 = load_point(g, e0.w, e0.w != NBR_NONE);
+        nbr_fold(p0, e0.x, qx, qy, qz, best, bp, second);
+        nbr_fold(p1, e0.y, qx, qy, qz, best, bp, second);
+        nbr_fold(p2, e0.z, qx, qy, qz, best, bp, second);
+        nbr_fold(p3, e0.w, qx, qy, qz, best, bp, second);
+        if (rest) {
+            // the list is in key order, so the fourth point's distance from p bounds the fifth to seventh and everything
+            // unlisted exactly as r bounds the unlisted: when the rule holds with it, the second batch cannot change the
+            // winner and is not loaded (most lanes: 6 gathers instead of 9; the look-up is bound by gathers per lane)
+            const float r4 = sqrtf(l2_simple(seed.px, seed.py, seed.pz, p3.x, p3.y, p3.z)) * 0.9999f;
+            if ((dp + sqrtf(__uint_as_float((uint32_t)(best >> 32)))) * 1.0001f + 2.0e-6f < r4) { rr = r4; rest = false; }
+        }
+    }
+    if (rest) {
+        const float4 p4 = load_point(g, e1.x, true), p5 = load_point(g, e1.y, e1.y != NBR_NONE), p6 = load_point(g, e1.z, e1.z != NBR_NONE);
+        nbr_fold(p4, e1.x, qx, qy, qz, best, bp, second);
+        nbr_fold(p5, e1.y, qx, qy, qz, best, bp, second);
+        nbr_fold(p6, e1.z, qx, qy, qz, best, bp, second);
+    }
+    const float d2b = __uint_as_float((uint32_t)(best >> 32));
+    if (!((dp + sqrtf(d2b)) * 1.0001f + 2.0e-6f < rr)) return false;
+    float lb = fmaxf(fminf(sqrtf(second) * 0.9999f, rr - dp * 1.0001f - 1.0e-6f), 0.0f);
+    // nothing under the threshold: the entry will say "no neighbour", and for such an entry the bound speaks of EVERY map
+    // point (reuse_certificate: "still nothing within the acceptance radius") -- the best candidate itself comes under it, as
+    // the would-be best of a search that found nothing enters its runner-up bound
+    if (!(d2b < thr)) lb = fminf(lb, sqrtf(d2b) * 0.9999f);
+    const float l2 = lb * lb;
+    out.lb2 = l2 > 0.0f ? __uint_as_float(__float_as_uint(l2) - 1u) : 0.0f; // one step below the rounded square
+    if (d2b < thr) {
+        out.d2 = d2b; out.j = (int)(uint32_t)best; out.px = bp.x; out.py = bp.y; out.pz = bp.z;
+    } else { // nothing within the acceptance radius: what a search that found nothing returns
+        out.d2 = search_start(thr); out.j = -1; out.px = out.py = out.pz = 0.0f;
+    }
+    return true;
 }
 
 } // namespace sf
