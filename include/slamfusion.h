@@ -236,8 +236,43 @@ int sf_map_knn(sf_map *m, const float *queries, int64_t n, int k, float max_d2, 
  * The map remembers (k, max_radius, with_covariance) in place of the radius: with sf_map_set_normals_carry on, sf_map_patch is
  * followed by this estimate in full on every path (sf_map_normals_carry_info: {0, 0, n, n}). */
 int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, int with_covariance);
-/* measurement (tools/knn_bench.py): with the switch on, sf_map_nn, sf_map_knn and sf_map_estimate_normals[_cov|_knn] record device
- * events around their kernel launches (not the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */
+/* Outlier removal (extension, no reference code): pcl::StatisticalOutlierRemoval / pcl::RadiusOutlierRemoval,
+ * Open3D remove_statistical_outlier / remove_radius_outlier.  The window is ignored, as the normals passes ignore it; the map's
+ * index, normals and neighbour table are not modified.
+ * Statistical.  The list of point i is its sf_map_knn list (own float32 coordinates, max_d2 = +inf, no window) of K entries:
+ *   SF_SOR_PCL: k OTHER points, K = k + 1, k in 1 .. 63;  SF_SOR_O3D: k points, itself among them, K = k, k in 1 .. 64;
+ *   any other flavour or k is SF_ERR_INVALID.  cnt = min(K, n_valid).
+ *   d_i = (sum over the list positions of sqrt((double)d2), pairwise tree over positions 0 .. 63, absent ones +0.0) divided by
+ *   cnt - 1 (PCL: position 0 is the point itself or a coincident one; 0 when cnt < 2) or by cnt (O3D); NaN for a point that is
+ *   not indexed (non-finite).  mean = sum(d) / n_valid, stddev = sqrt(sum((d - mean)^2) / (n_valid - 1)) (0 when n_valid < 2),
+ *   both float64 sums over the points in ORIGINAL order in the pairwise tree over the array padded with +0.0 to a power of two
+ *   (points not indexed contribute +0.0); threshold = mean + std_ratio * stddev.
+ *   Keep iff d_i <= threshold (PCL) / d_i < threshold (O3D), compared in float64; points not indexed are not kept.
+ *   d_i, the statistics and the flags depend on the cloud alone: not on the cell, the launch or the run.
+ *   Divergences from both libraries: the variance is the two-pass form for either flavour (they use sum and sum of squares),
+ *   and a cloud with fewer than K points divides by what it has instead of marking every point invalid.
+ * Radius.  radius > 0 and finite, min_neighbors >= 0, else SF_ERR_INVALID.  r2 = (float)(radius * radius); count_i = the number
+ *   of indexed points p with d2(x_i, p) < r2 under the float32, unfused, strict rule of sf_map_nn / sf_map_knn, the point itself
+ *   included (so min(count_i, 64) is the count of sf_map_knn(x_i, 64, r2)); keep iff count_i > min_neighbors, i.e. that many
+ *   neighbours besides itself, as both libraries have it.  Points not indexed get count 0 and are not kept.
+ * keep [n] (1 / 0), mean_dist [n] / n_neighbors [n] and stats are in ORIGINAL point order; any of them may be NULL.
+ * SF_ERR_STATE for a map that is not built.  With sf_map_profile_launches on, the map calls record the device time from their
+ * first to their last kernel (the statistical form reads its two sums back in between) for sf_map_last_launch_ms. */
+#define SF_SOR_PCL 0
+#define SF_SOR_O3D 1
+typedef struct { int64_t n_points, n_valid, n_kept; double mean, stddev, threshold; } sf_outlier_stats; /* radius: the doubles are 0 */
+int sf_map_statistical_outliers(sf_map *m, int k, double std_ratio, int flavour,
+                                uint8_t *keep, double *mean_dist, sf_outlier_stats *stats);   /* original point order; any may be NULL */
+int sf_map_radius_outliers(sf_map *m, double radius, int min_neighbors,
+                           uint8_t *keep, int32_t *n_neighbors, sf_outlier_stats *stats);
+/* The same filters applied to a cloud: it is indexed with a temporary map (`cell` as in sf_map_build, 0 = automatic), flagged by
+ * the device code of the map calls and compacted in place like a crop -- the order is kept, sf_cloud_last_indices reports the
+ * survivors, the flags never leave the device.  An empty cloud is SF_OK with zero stats. */
+int sf_cloud_remove_statistical_outliers(sf_cloud *c, int k, double std_ratio, int flavour, float cell, sf_outlier_stats *stats);
+int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int min_neighbors, float cell, sf_outlier_stats *stats);
+/* measurement (tools/knn_bench.py, tools/outlier_bench.py): with the switch on, sf_map_nn, sf_map_knn, sf_map_estimate_normals[_cov|_knn]
+ * and sf_map_*_outliers record device events around their kernel launches (not the copies); sf_map_last_launch_ms reads the latest
+ * (SF_ERR_STATE if there is none). */
 int sf_map_profile_launches(sf_map *m, int on);
 int sf_map_last_launch_ms(sf_map *m, float *ms);
 /* Neighbour table: per indexed point one 32-byte entry -- the sorted positions of its up to 7 nearest other points

@@ -59,6 +59,22 @@ class IcpCovariance(C.Structure):
                     rot_info=a(self.rot_info, 3), rot_dir=a(self.rot_dir, 3, 3), n_corr=int(self.n_corr), flags=int(self.flags))
 
 
+SOR_FLAVOURS = {"pcl": 0, "o3d": 1}  # SF_SOR_*
+
+
+def _sor_flavour(flavour):
+    return SOR_FLAVOURS[flavour] if flavour in SOR_FLAVOURS else int(flavour)
+
+
+class OutlierStats(C.Structure):
+    """sf_outlier_stats: what an outlier filter saw (the radius filter leaves the three doubles 0)."""
+    _fields_ = [("n_points", C.c_int64), ("n_valid", C.c_int64), ("n_kept", C.c_int64), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
+
+    def as_dict(self):
+        return dict(n_points=int(self.n_points), n_valid=int(self.n_valid), n_kept=int(self.n_kept), mean=float(self.mean), stddev=float(self.stddev),
+                    threshold=float(self.threshold))
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
@@ -291,6 +307,21 @@ class Cloud:
         _check(self.lib.sf_cloud_transform(self.h, _p(T)))
         return self
 
+    def remove_statistical_outliers(self, nb_neighbors=20, std_ratio=2.0, flavour="pcl", cell=0.0):
+        """sf_cloud_remove_statistical_outliers (pcl::StatisticalOutlierRemoval / Open3D remove_statistical_outlier): in place, order
+        kept, `last_indices` reports the survivors -> stats dict.  `cell`: the cell of the temporary index (0 = automatic)."""
+        st = OutlierStats()
+        _check(self.lib.sf_cloud_remove_statistical_outliers(self.h, C.c_int(int(nb_neighbors)), C.c_double(std_ratio), C.c_int(_sor_flavour(flavour)), C.c_float(cell),
+                                                             C.byref(st)))
+        return st.as_dict()
+
+    def remove_radius_outliers(self, radius, min_neighbors, cell=0.0):
+        """sf_cloud_remove_radius_outliers (pcl::RadiusOutlierRemoval / Open3D remove_radius_outlier): keeps the points with more than
+        `min_neighbors` other points within `radius` -> stats dict."""
+        st = OutlierStats()
+        _check(self.lib.sf_cloud_remove_radius_outliers(self.h, C.c_double(radius), C.c_int(int(min_neighbors)), C.c_float(cell), C.byref(st)))
+        return st.as_dict()
+
     def last_indices(self):
         n = C.c_int64()
         cap = 1 << 20
@@ -485,6 +516,27 @@ class Map:
         cnt = np.empty(len(q), np.int32)
         _check(self.lib.sf_map_knn(self.h, _p(q), C.c_int64(len(q)), C.c_int(k), C.c_float(max_d2), _p(idx), _p(d2), _p(cnt)))
         return idx, d2, cnt
+
+    def statistical_outliers(self, k, std_ratio=2.0, flavour="pcl"):
+        """sf_map_statistical_outliers: -> (keep bool [n], mean_dist float64 [n], stats dict), original point order.  flavour "pcl":
+        k other points, keep iff d <= mean + std_ratio * stddev (pcl::StatisticalOutlierRemoval); "o3d": k points with the point
+        itself among them, keep iff d < threshold (remove_statistical_outlier).  Points that are not indexed: False / NaN."""
+        n = len(self)
+        keep = np.zeros(n, np.uint8)
+        dist = np.empty(n, np.float64)
+        st = OutlierStats()
+        _check(self.lib.sf_map_statistical_outliers(self.h, C.c_int(int(k)), C.c_double(std_ratio), C.c_int(_sor_flavour(flavour)), _p(keep), _p(dist), C.byref(st)))
+        return keep.astype(bool), dist, st.as_dict()
+
+    def radius_outliers(self, radius, min_neighbors):
+        """sf_map_radius_outliers: -> (keep bool [n], n_neighbors int32 [n], stats dict), original point order.  n_neighbors counts the
+        indexed points with float32 d2 < float32(radius^2), the point itself included; keep iff n_neighbors > min_neighbors."""
+        n = len(self)
+        keep = np.zeros(n, np.uint8)
+        cnt = np.empty(n, np.int32)
+        st = OutlierStats()
+        _check(self.lib.sf_map_radius_outliers(self.h, C.c_double(radius), C.c_int(int(min_neighbors)), _p(keep), _p(cnt), C.byref(st)))
+        return keep.astype(bool), cnt, st.as_dict()
 
     def build_neighbour_table(self):
         """sf_map_build_neighbour_table: per indexed point its up to 7 nearest other points and a radius free of any further

@@ -210,6 +210,9 @@ struct sf_map {
     bool nbr_timed = false;    // ... recorded and not read yet
     bool served = false;       // an alignment has been enqueued against this map ...
     bool moved_after_serving = false; // ... and the index was rebuilt or patched after that (auto: no table for a growing map)
+    // sf_map_*_outliers (and the sf_cloud_remove_*_outliers that run them on a temporary map), all in ORIGINAL point order:
+    // keep flags uint8[n]; mean distances double[n] or neighbour counts int32[n]; the partial sums of the tree reduction
+    sf::DevBuf out_flags, out_val, out_red;
     int64_t n = 0;
     bool built = false, has_normals = false, has_cov = false;
     uint64_t generation = 0; // process-unique stamp of the index contents (build / normals): captured hipGraphs key on it

@@ -191,6 +191,7 @@ extern "C" void sf_map_destroy(sf_map *m)
     for (hipEvent_t ev : m->nbr_ev)
         if (ev) { hipError_t e2 = hipEventDestroy(ev); (void)e2; }
     m->nbr.release();
+    m->out_flags.release(); m->out_val.release(); m->out_red.release();
     sf_ctx *ctx = m->ctx;
     delete m;
     sf::ctx_release(ctx);
@@ -1408,6 +1409,355 @@ extern "C" int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, i
     m->nrm_with_cov = with_covariance != 0;
     m->generation = sf::next_generation();
     return SF_OK;
+}
+
+// ------------------------------------------------------------------ outlier removal (extension, no reference code)
+namespace {
+
+// the mean neighbour distance of every indexed point, the shape of k_normals_knn: a wave walks its 64 consecutive points, all lanes
+// on one query; list position p is lane p and contributes sqrt((double)d2) of its key's upper word (absent: +0.0), no point is
+// loaded; lane t keeps the result of point t and the wave writes its 64 results at the end, in original point order
+__global__ __launch_bounds__(256) void k_knn_mean_dist(SfGrid g, int K, int pcl, double *__restrict__ mean_dist)
+{
+    __shared__ sf::WaveKNN ws[256 / 64];
+    const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+    const int64_t base = ((int64_t)blockIdx.x * 4 + wv) * 64;
+    if (base >= g.n) return; // (the whole wave: no workgroup barrier below)
+    const int64_t i = base + lane;
+    const float4 mine = i < g.n ? g.pts[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const int nq = (int)min((int64_t)64, g.n - base);
+    const SfWindow none{}; // (never read: knn_search<false>)
+    double myd = 0.0;
+    for (int t = 0; t < nq; ++t) {
+        const float qx = __shfl(mine.x, t), qy = __shfl(mine.y, t), qz = __shfl(mine.z, t);
+        unsigned long long key;
+        const int cnt = sf::knn_search<false>(g, none, qx, qy, qz, K, INFINITY, &ws[wv], key);
+        const double sum = sf::wave_tree_sum(lane < cnt ? sqrt((double)__uint_as_float((uint32_t)(key >> 32))) : 0.0);
+        const int div = pcl ? cnt - 1 : cnt; // PCL: position 0 is the point itself (or a coincident one), a zero that is not a neighbour
+        const double d = div > 0 ? sum / (double)div : 0.0;
+        if (lane == t) myd = d;
+    }
+    if (i < g.n) mean_dist[__float_as_uint(mine.w)] = myd;
+}
+
+__global__ void k_fill_f64(double *__restrict__ p, int64_t n, double v)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// One level of the float64 pairwise tree: workgroup b sums leaves [256 b, 256 b + 256) -- wave_tree_sum over the 64 leaves of each
+// wave, the four wave sums pairwise -- which is the subtree over those leaves of the full tree v[0::2] + v[1::2] ... over the
+// array padded with +0.0 to a power of two; applied again to its own output until one value is left.  A NaN leaf (a point that is
+// not indexed) and a leaf past the end are +0.0.  sq: the leaf is (v - mean)^2, the product formed by its own multiply.
+__global__ __launch_bounds__(256) void k_tree_sum(const double *__restrict__ v, int64_t n, int sq, double mean, double *__restrict__ out)
+{
+    __shared__ double wsum[256 / 64];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double x = 0.0;
+    if (i < n) {
+        const double d = v[i];
+        if (d == d) x = sq ? __dmul_rn(__dsub_rn(d, mean), __dsub_rn(d, mean)) : d;
+    }
+    x = sf::wave_tree_sum(x);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = __dadd_rn(__dadd_rn(wsum[0], wsum[1]), __dadd_rn(wsum[2], wsum[3]));
+}
+
+// The kept count: every wave adds its ballot's popcount to one of KEPT_SLOTS integer counters, 128 bytes apart, and k_sum_kept adds
+// those up into the word behind them.  Atomics on one address are served one after another where that cache line lives, so one
+// counter for all waves would put n / 64 of them in a single queue; consecutive waves go to different lines instead and each
+// line's queue is KEPT_SLOTS times shorter.  Integer sums: order independent.
+constexpr int KEPT_SLOTS = 256, KEPT_STRIDE = 16, KEPT_WORDS = (KEPT_SLOTS + 1) * KEPT_STRIDE; // in 8-byte words
+__device__ __forceinline__ void add_kept(bool keep, unsigned long long *__restrict__ kept)
+{
+    const unsigned long long b = __ballot(keep);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(kept + (size_t)((blockIdx.x * 4u + (threadIdx.x >> 6)) & (KEPT_SLOTS - 1)) * KEPT_STRIDE, (unsigned long long)__popcll(b));
+}
+__global__ __launch_bounds__(KEPT_SLOTS) void k_sum_kept(unsigned long long *__restrict__ kept)
+{
+    __shared__ unsigned long long wsum[KEPT_SLOTS / 64];
+    unsigned long long v = kept[(size_t)threadIdx.x * KEPT_STRIDE];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) kept[(size_t)KEPT_SLOTS * KEPT_STRIDE] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// keep iff d <= thr (PCL) / d < thr (strict: O3D) in float64; NaN (not indexed) is not kept.
+__global__ __launch_bounds__(256) void k_flag_mean_dist(const double *__restrict__ mean_dist, int64_t n, double thr, int strict, uint8_t *__restrict__ flags,
+                                                         unsigned long long *__restrict__ kept)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool keep = false;
+    if (i < n) {
+        const double d = mean_dist[i];
+        keep = strict ? d < thr : d <= thr;
+        flags[i] = keep ? 1 : 0;
+    }
+    add_kept(keep, kept);
+}
+
+// count_j = the number of indexed points q with l2_simple(p_j, q) < r2 (float32, unfused, strict; p_j itself included), one lane per
+// indexed point, walking the block of cells within R of its own cell row by row, each row one contiguous cell_start run.
+//
+// Nothing the rule accepts is lost.  Write G(x) = fl(fl(x - org) * inv_h) for the grid coordinate every point is binned by
+// (k_cell_keys; the cell is floor(G) clamped to the grid), u = 2^-24, and let q be accepted for p.
+// (a) Per axis |p - q| < r (1 + 2u), r = sqrt(r2): rounding is monotone, so the float sum of non-negative terms is at least each
+//     term, fl(d2) >= fl(fl(dx)^2) >= dx^2 (1 - u)^3, and fl(d2) < r2.  (A square that underflows belongs to |dx| < 2^-62 m.)
+// (b) G(x) = (x - org) inv_h (1 + e1)(1 + e2), |e| <= u, and (x - org) inv_h < dim (1 + u) for every indexed point, so
+//     |G(p) - G(q)| <= |p - q| inv_h + S with S = 2^-22 maxdim (1 + 3u) cells: S h is below gap_eps = 1.5 * 2^-22 maxdim h, the
+//     slack SfGrid carries for exactly this.
+// (c) Reach: floor(a) - floor(b) <= ceil(D) whenever a - b <= D, and the clamp only brings cells closer, so q's cell is within
+//     R = ceil((r (1 + 1e-6) + gap_eps) inv_h) of p's on every axis (the host computes it in float64; 1e-6 covers (a) and its own
+//     roundings).  normals_reach's ceil(radius / h - 1e-9) is one short when r is a whole number of cells and p, q straddle it.
+// (d) Row skip and x-trim, the rule of knn_search with tau = r2: a point binned in cell c != cq has G on the far side of the face
+//     between, so by (b) its true axis distance from p is at least safe_gap(cell_gap * h, gap_eps), up to the relative roundings of
+//     forming it (a few u).  A row or an end cell is left out only when the sum g2 of those squared gaps has g2 * 0.998 >= r2;
+//     then dy^2 + dz^2 (+ dx^2) >= g2 (1 - 8u) and fl(d2) >= that (1 - 5u) >= r2 / 0.998 * (1 - 13u) > r2: rejected by the rule itself.
+// No early exit at count > min_neighbors: the counts are an output.
+__global__ __launch_bounds__(256) void k_radius_count(SfGrid g, float r2, int R, int min_neighbors, int32_t *__restrict__ n_neighbors, uint8_t *__restrict__ flags,
+                                                       unsigned long long *__restrict__ kept)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool keep = false;
+    if (j < g.n) {
+        const float4 p = g.pts[j];
+        const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
+        const float gx = (p.x - g.org[0]) * g.inv_h, gy = (p.y - g.org[1]) * g.inv_h, gz = (p.z - g.org[2]) * g.inv_h;
+        const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
+        const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
+        const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
+        const int x0 = max(cx - R, 0), x1 = min(cx + R, nx - 1);
+        const int y0 = max(cy - R, 0), y1 = min(cy + R, ny - 1);
+        const int z0 = max(cz - R, 0), z1 = min(cz + R, nz - 1);
+        const float h = g.h, ge = g.gap_eps;
+        int cnt = 0;
+        for (int z = z0; z <= z1; ++z) {
+            const float rz = sf::safe_gap(sf::cell_gap(gz, z, cz) * h, ge);
+            if (!(rz * rz * 0.998f < r2)) continue;
+            for (int y = y0; y <= y1; ++y) {
+                const float ry = sf::safe_gap(sf::cell_gap(gy, y, cy) * h, ge);
+                const float g2 = ry * ry + rz * rz;
+                if (!(g2 * 0.998f < r2)) continue;
+                int xa = x0, xb = x1; // the x-run less the end cells whose gap excludes them (the point's own column never is)
+                while (xa < cx) {
+                    const float gl = sf::safe_gap(sf::cell_gap(gx, xa, cx) * h, ge);
+                    if ((g2 + gl * gl) * 0.998f < r2) break;
+                    ++xa;
+                }
+                while (xb > cx) {
+                    const float gr = sf::safe_gap(sf::cell_gap(gx, xb, cx) * h, ge);
+                    if ((g2 + gr * gr) * 0.998f < r2) break;
+                    --xb;
+                }
+                const size_t row = ((size_t)z * ny + y) * nx;
+                const uint32_t a = g.cell_start[row + xa], b = g.cell_start[row + xb + 1];
+                for (uint32_t k = a; k < b; k += 4) { // four loads in flight (scan4 of sf_nn.hpp)
+                    const float4 q0 = sf::load_point(g, k, true), q1 = sf::load_point(g, k + 1, k + 1 < b), q2 = sf::load_point(g, k + 2, k + 2 < b),
+                                 q3 = sf::load_point(g, k + 3, k + 3 < b);
+                    cnt += sf::l2_simple(p.x, p.y, p.z, q0.x, q0.y, q0.z) < r2 ? 1 : 0;
+                    cnt += (k + 1 < b && sf::l2_simple(p.x, p.y, p.z, q1.x, q1.y, q1.z) < r2) ? 1 : 0;
+                    cnt += (k + 2 < b && sf::l2_simple(p.x, p.y, p.z, q2.x, q2.y, q2.z) < r2) ? 1 : 0;
+                    cnt += (k + 3 < b && sf::l2_simple(p.x, p.y, p.z, q3.x, q3.y, q3.z) < r2) ? 1 : 0;
+                }
+            }
+        }
+        const uint32_t id = __float_as_uint(p.w);
+        keep = cnt > min_neighbors;
+        n_neighbors[id] = cnt;
+        flags[id] = keep ? 1 : 0;
+    }
+    add_kept(keep, kept);
+}
+
+// K of the statistical filter's neighbour list, 0 for arguments it refuses
+inline int sor_list_length(int k, int flavour)
+{
+    if (flavour == SF_SOR_PCL) return (k >= 1 && k <= SF_KNN_MAX - 1) ? k + 1 : 0;
+    if (flavour == SF_SOR_O3D) return (k >= 1 && k <= SF_KNN_MAX) ? k : 0;
+    return 0;
+}
+#define SF_CHECK_SOR(k, flavour) SF_CHECK(sor_list_length(k, flavour) > 0, SF_ERR_INVALID, "statistical outliers: flavour SF_SOR_PCL with k 1 .. %d or SF_SOR_O3D with k 1 .. %d (got flavour %d, k %d)", SF_KNN_MAX - 1, SF_KNN_MAX, flavour, k)
+#define SF_CHECK_ROR(radius, min_neighbors) SF_CHECK((radius) > 0 && std::isfinite(radius) && (min_neighbors) >= 0, SF_ERR_INVALID, "radius outliers: radius must be positive and finite, min_neighbors >= 0 (got %g, %d)", (double)(radius), min_neighbors)
+
+// where the host reads the sums and the kept count (ctx->h_pinned; the compaction, the patch and the carry use the bytes below 384)
+constexpr size_t OUT_PINNED_OFF = 384;
+
+// out_red: [the kept counters and their sum, KEPT_WORDS words | the levels of the tree, one after another]
+int outlier_buffers(sf_map *m, size_t val_bytes)
+{
+    const size_t n = (size_t)m->n, nb = (size_t)sf::div_up(m->n, 256);
+    SF_TRY(m->out_flags.reserve(n));
+    SF_TRY(m->out_val.reserve(val_bytes * n));
+    // the levels hold nb, ceil(nb / 256), ... 1 sums: each at most a 256th of the one before plus one, so together below
+    // nb + nb / 255 + (number of levels <= 4, m->n < 2^28) <= nb + nb / 128 + 8
+    SF_TRY(m->out_red.reserve(sizeof(double) * (KEPT_WORDS + nb + nb / 128 + 8)));
+    SF_HIP(hipMemsetAsync(m->out_red.p, 0, sizeof(unsigned long long) * KEPT_WORDS, m->ctx->stream));
+    return SF_OK;
+}
+
+// the tree sum of v[0 .. n) (or of its squared deviations from mean) -> *h_sum; synchronises the stream
+int tree_sum(sf_map *m, const double *v, int64_t n, bool sq, double mean, double *h_sum)
+{
+    sf_ctx *ctx = m->ctx;
+    double *level = m->out_red.as<double>() + KEPT_WORDS;
+    const double *in = v;
+    int64_t cnt = n;
+    bool first = true;
+    do {
+        const int64_t nb = sf::div_up(cnt, 256);
+        hipLaunchKernelGGL(k_tree_sum, dim3((unsigned)nb), dim3(256), 0, ctx->stream, in, cnt, (first && sq) ? 1 : 0, mean, level);
+        in = level;
+        level += nb;
+        cnt = nb;
+        first = false;
+    } while (cnt > 1);
+    double *h = reinterpret_cast<double *>(static_cast<unsigned char *>(ctx->h_pinned) + OUT_PINNED_OFF);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(h, in, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    *h_sum = *h;
+    return SF_OK;
+}
+
+int read_kept(sf_map *m, sf_outlier_stats *st)
+{
+    sf_ctx *ctx = m->ctx;
+    unsigned long long *h = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(ctx->h_pinned) + OUT_PINNED_OFF);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(h, m->out_red.as<unsigned long long>() + (size_t)KEPT_SLOTS * KEPT_STRIDE, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    prof_read(m);
+    st->n_kept = (int64_t)*h;
+    return SF_OK;
+}
+
+// The filters proper, shared by the map calls and the cloud calls: the flags stay in m->out_flags, the distances / counts in
+// m->out_val (original point order), only the statistics come to the host.  Arguments are checked by the callers.
+int statistical_outliers_device(sf_map *m, int K, bool pcl, double std_ratio, sf_outlier_stats *st)
+{
+    sf_ctx *ctx = m->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int64_t n = m->n, nv = m->grid.n;
+    *st = sf_outlier_stats{n, nv, 0, 0.0, 0.0, 0.0};
+    if (n == 0) return SF_OK;
+    SF_TRY(outlier_buffers(m, sizeof(double)));
+    double *dist = m->out_val.as<double>();
+    prof_begin(m);
+    hipLaunchKernelGGL(k_fill_f64, dim3(nblk(n)), dim3(256), 0, s, dist, n, (double)NAN);
+    if (nv > 0) {
+        hipLaunchKernelGGL(k_knn_mean_dist, dim3(nblk(nv)), dim3(256), 0, s, m->grid, K, pcl ? 1 : 0, dist);
+        double sum = 0.0, sum2 = 0.0;
+        int rc = tree_sum(m, dist, n, false, 0.0, &sum);
+        st->mean = sum / (double)nv;
+        if (rc == SF_OK && nv >= 2) {
+            rc = tree_sum(m, dist, n, true, st->mean, &sum2);
+            st->stddev = std::sqrt(sum2 / (double)(nv - 1));
+        }
+        if (rc != SF_OK) { // close the profiled span on the way out, so that the next call does not start inside one
+            prof_end(m);
+            return rc;
+        }
+        st->threshold = st->mean + std_ratio * st->stddev;
+    }
+    hipLaunchKernelGGL(k_flag_mean_dist, dim3(nblk(n)), dim3(256), 0, s, dist, n, st->threshold, pcl ? 0 : 1, m->out_flags.as<uint8_t>(), m->out_red.as<unsigned long long>());
+    hipLaunchKernelGGL(k_sum_kept, dim3(1), dim3(KEPT_SLOTS), 0, s, m->out_red.as<unsigned long long>());
+    prof_end(m);
+    return read_kept(m, st);
+}
+
+int radius_outliers_device(sf_map *m, double radius, int min_neighbors, sf_outlier_stats *st)
+{
+    sf_ctx *ctx = m->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int64_t n = m->n, nv = m->grid.n;
+    *st = sf_outlier_stats{n, nv, 0, 0.0, 0.0, 0.0};
+    if (n == 0) return SF_OK;
+    SF_TRY(outlier_buffers(m, sizeof(int32_t)));
+    const float r2 = (float)(radius * radius);
+    const SfGrid &g = m->grid;
+    // the reach (k_radius_count, (c)), in float64, capped by the grid before the conversion
+    const double reach = std::ceil((std::sqrt((double)r2) * (1.0 + 1.0e-6) + (double)g.gap_eps) * (double)g.inv_h);
+    const int R = (int)std::min(std::max(reach, 1.0), (double)std::max(g.dim[0], std::max(g.dim[1], g.dim[2])));
+    SF_HIP(hipMemsetAsync(m->out_flags.p, 0, (size_t)n, s)); // points that are not indexed: not kept, no neighbours
+    SF_HIP(hipMemsetAsync(m->out_val.p, 0, sizeof(int32_t) * (size_t)n, s));
+    prof_begin(m);
+    if (nv > 0)
+        hipLaunchKernelGGL(k_radius_count, dim3(nblk(nv)), dim3(256), 0, s, g, r2, R, min_neighbors, m->out_val.as<int32_t>(), m->out_flags.as<uint8_t>(),
+                           m->out_red.as<unsigned long long>());
+    hipLaunchKernelGGL(k_sum_kept, dim3(1), dim3(KEPT_SLOTS), 0, s, m->out_red.as<unsigned long long>());
+    prof_end(m);
+    return read_kept(m, st);
+}
+
+int download_outliers(sf_map *m, uint8_t *keep, void *val, size_t val_bytes)
+{
+    sf_ctx *ctx = m->ctx;
+    if (m->n == 0 || (!keep && !val)) return SF_OK;
+    if (keep) SF_HIP(hipMemcpyAsync(keep, m->out_flags.p, (size_t)m->n, hipMemcpyDeviceToHost, ctx->stream));
+    if (val) SF_HIP(hipMemcpyAsync(val, m->out_val.p, val_bytes * (size_t)m->n, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    return SF_OK;
+}
+
+// index the cloud with a temporary map, flag, compact (the order is kept: compact_cloud, as after a crop)
+template <class F>
+int remove_outliers(sf_cloud *c, float cell, sf_outlier_stats *stats, F filter)
+{
+    sf_outlier_stats st{0, 0, 0, 0.0, 0.0, 0.0};
+    if (stats) *stats = st;
+    sf::cloud_touch(c);
+    if (c->n == 0) { c->n_last_idx = 0; return SF_OK; }
+    sf_map *tmp = nullptr;
+    SF_TRY(sf_map_create(c->ctx, &tmp));
+    int rc = sf_map_build(tmp, c, cell);
+    if (rc == SF_OK) rc = filter(tmp, &st);
+    if (rc == SF_OK) rc = sf::compact_cloud(c, tmp->out_flags.as<uint8_t>());
+    sf_map_destroy(tmp);
+    if (rc == SF_OK && stats) *stats = st;
+    return rc;
+}
+
+} // namespace
+
+extern "C" int sf_map_statistical_outliers(sf_map *m, int k, double std_ratio, int flavour, uint8_t *keep, double *mean_dist, sf_outlier_stats *stats)
+{
+    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
+    SF_CHECK_SOR(k, flavour);
+    sf_outlier_stats st;
+    SF_TRY(statistical_outliers_device(m, sor_list_length(k, flavour), flavour == SF_SOR_PCL, std_ratio, &st));
+    if (stats) *stats = st;
+    return download_outliers(m, keep, mean_dist, sizeof(double));
+}
+
+extern "C" int sf_map_radius_outliers(sf_map *m, double radius, int min_neighbors, uint8_t *keep, int32_t *n_neighbors, sf_outlier_stats *stats)
+{
+    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
+    SF_CHECK_ROR(radius, min_neighbors);
+    sf_outlier_stats st;
+    SF_TRY(radius_outliers_device(m, radius, min_neighbors, &st));
+    if (stats) *stats = st;
+    return download_outliers(m, keep, n_neighbors, sizeof(int32_t));
+}
+
+extern "C" int sf_cloud_remove_statistical_outliers(sf_cloud *c, int k, double std_ratio, int flavour, float cell, sf_outlier_stats *stats)
+{
+    SF_CHECK(c, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK_SOR(k, flavour);
+    const int K = sor_list_length(k, flavour);
+    return remove_outliers(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return statistical_outliers_device(m, K, flavour == SF_SOR_PCL, std_ratio, st); });
+}
+
+extern "C" int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int min_neighbors, float cell, sf_outlier_stats *stats)
+{
+    SF_CHECK(c, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK_ROR(radius, min_neighbors);
+    return remove_outliers(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return radius_outliers_device(m, radius, min_neighbors, st); });
 }
 
 extern "C" int sf_map_profile_launches(sf_map *m, int on)
