@@ -270,9 +270,41 @@ int sf_map_radius_outliers(sf_map *m, double radius, int min_neighbors,
  * survivors, the flags never leave the device.  An empty cloud is SF_OK with zero stats. */
 int sf_cloud_remove_statistical_outliers(sf_cloud *c, int k, double std_ratio, int flavour, float cell, sf_outlier_stats *stats);
 int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int min_neighbors, float cell, sf_outlier_stats *stats);
-/* measurement (tools/knn_bench.py, tools/outlier_bench.py): with the switch on, sf_map_nn, sf_map_knn, sf_map_estimate_normals[_cov|_knn]
- * and sf_map_*_outliers record device events around their kernel launches (not the copies); sf_map_last_launch_ms reads the latest
- * (SF_ERR_STATE if there is none). */
+/* Clustering (extension, no reference code): pcl::EuclideanClusterExtraction, Open3D cluster_dbscan, scikit-learn DBSCAN.
+ * The window is ignored; the map's index, normals, covariances and neighbour table are not modified.  The labels are a function of
+ * the cloud and the parameters alone: not of the cell, the launch or the run.
+ * Edges.  r2 = (float)(eps * eps); indexed points i != j are adjacent iff d2(x_i, x_j) < r2 under the float32, unfused, strict rule
+ *   of sf_map_radius_outliers (symmetric bit for bit); count_i is that call's count_i at radius = eps, the point itself included.
+ * DBSCAN.  eps > 0 and finite, min_points >= 1, else SF_ERR_INVALID.  Point i is core iff count_i >= min_points (it counts itself,
+ *   as scikit-learn's min_samples and Open3D's min_points do).  Clusters are the connected components of the graph restricted to
+ *   the core points, numbered 0 .. C-1 in ascending order of their smallest core point's ORIGINAL index.  A point that is not core
+ *   and has a core neighbour is a border point and gets the smallest label among its core neighbours' clusters; every other point,
+ *   those not indexed (non-finite) included, is noise: -1.  These are the labels of scikit-learn's sequential DBSCAN; the one
+ *   divergence from the libraries is < in float32 where they have <= in float64.
+ * Euclidean.  DBSCAN with min_points = 1 (every indexed point is core; no border, no noise), then a size filter: clusters of fewer
+ *   than min_size or more than max_size points get -1 (max_size <= 0: no upper bound; min_size >= 1, else SF_ERR_INVALID) and the
+ *   others are renumbered compactly in the same order.  Divergence from PCL: it orders the clusters by size, descending; here the
+ *   order is by smallest member index and sizes[] is returned for a caller to sort by.
+ * labels [n] in ORIGINAL point order; sizes [min(n_clusters, cap_sizes)] per label, border points included; any of labels, sizes and
+ * stats may be NULL.  n_noise: the indexed points labelled -1 (Euclidean: the points the size filter took away); n_kept: the
+ * points with label >= 0; largest_size: the largest cluster left (0 when there is none).  SF_ERR_STATE for a map that is not built.
+ * With sf_map_profile_launches on, the device time from the first to the last kernel is recorded for sf_map_last_launch_ms. */
+typedef struct { int64_t n_points, n_valid, n_core, n_border, n_noise, n_clusters, largest_size, n_kept; } sf_cluster_stats;
+int sf_map_cluster_dbscan(sf_map *m, double eps, int min_points,
+                          int32_t *labels, int32_t *sizes, int64_t cap_sizes, sf_cluster_stats *stats);
+int sf_map_cluster_euclidean(sf_map *m, double tolerance, int64_t min_size, int64_t max_size,
+                             int32_t *labels, int32_t *sizes, int64_t cap_sizes, sf_cluster_stats *stats);
+/* The same applied to a cloud, as the sf_cloud_remove_*_outliers calls are: a temporary map (`cell` as in sf_map_build), the device
+ * code of sf_map_cluster_euclidean, compaction in place -- the order is kept, sf_cloud_last_indices reports the survivors, neither
+ * labels nor flags leave the device.  filter_clusters keeps the points whose cluster passes the size filter.  keep_largest_cluster
+ * keeps the cluster with the most points, on a tie the one with the smallest label; its stats are those of
+ * sf_map_cluster_euclidean(tolerance, 1, 0) except n_kept = largest_size and n_noise = n_valid - n_kept, what the call took away.
+ * An empty cloud is SF_OK with zero stats. */
+int sf_cloud_filter_clusters(sf_cloud *c, double tolerance, int64_t min_size, int64_t max_size, float cell, sf_cluster_stats *stats);
+int sf_cloud_keep_largest_cluster(sf_cloud *c, double tolerance, float cell, sf_cluster_stats *stats);
+/* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
+ * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
+ * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */
 int sf_map_profile_launches(sf_map *m, int on);
 int sf_map_last_launch_ms(sf_map *m, float *ms);
 /* Neighbour table: per indexed point one 32-byte entry -- the sorted positions of its up to 7 nearest other points

@@ -75,6 +75,14 @@ class OutlierStats(C.Structure):
                     threshold=float(self.threshold))
 
 
+class ClusterStats(C.Structure):
+    """sf_cluster_stats: what a clustering call found (n_noise, n_kept: the indexed points labelled -1 / the points with a label)."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_valid", "n_core", "n_border", "n_noise", "n_clusters", "largest_size", "n_kept")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
@@ -322,6 +330,21 @@ class Cloud:
         _check(self.lib.sf_cloud_remove_radius_outliers(self.h, C.c_double(radius), C.c_int(int(min_neighbors)), C.c_float(cell), C.byref(st)))
         return st.as_dict()
 
+    def filter_clusters(self, tolerance, min_size, max_size=0, cell=0.0):
+        """sf_cloud_filter_clusters (pcl::EuclideanClusterExtraction as a filter): keeps the points whose connected piece at `tolerance`
+        has min_size .. max_size points (max_size <= 0: no upper bound); in place, order kept, `last_indices` reports the survivors
+        -> stats dict.  `cell`: the cell of the temporary index (0 = automatic)."""
+        st = ClusterStats()
+        _check(self.lib.sf_cloud_filter_clusters(self.h, C.c_double(tolerance), C.c_int64(int(min_size)), C.c_int64(int(max_size)), C.c_float(cell), C.byref(st)))
+        return st.as_dict()
+
+    def keep_largest_cluster(self, tolerance, cell=0.0):
+        """sf_cloud_keep_largest_cluster: keeps the connected piece with the most points (a tie: the one holding the earliest point)
+        -> stats dict with n_kept = largest_size."""
+        st = ClusterStats()
+        _check(self.lib.sf_cloud_keep_largest_cluster(self.h, C.c_double(tolerance), C.c_float(cell), C.byref(st)))
+        return st.as_dict()
+
     def last_indices(self):
         n = C.c_int64()
         cap = 1 << 20
@@ -537,6 +560,25 @@ class Map:
         st = OutlierStats()
         _check(self.lib.sf_map_radius_outliers(self.h, C.c_double(radius), C.c_int(int(min_neighbors)), _p(keep), _p(cnt), C.byref(st)))
         return keep.astype(bool), cnt, st.as_dict()
+
+    def _clusters(self, call, *args):
+        n = len(self)
+        labels = np.empty(n, np.int32)
+        sizes = np.empty(max(n, 1), np.int32)                      # (there are at most n clusters)
+        st = ClusterStats()
+        _check(call(self.h, *args, _p(labels), _p(sizes), C.c_int64(len(sizes)), C.byref(st)))
+        return labels, sizes[:int(st.n_clusters)].copy(), st.as_dict()
+
+    def cluster_dbscan(self, eps, min_points):
+        """sf_map_cluster_dbscan (Open3D cluster_dbscan, scikit-learn DBSCAN): -> (labels int32 [n], sizes int32 [C], stats dict), original
+        point order.  A point is core when `min_points` indexed points, itself included, lie within eps (float32 d2 < float32(eps^2));
+        clusters are numbered by their smallest core point; a border point takes the smallest label among its core neighbours; -1: noise."""
+        return self._clusters(self.lib.sf_map_cluster_dbscan, C.c_double(eps), C.c_int(int(min_points)))
+
+    def cluster_euclidean(self, tolerance, min_size=1, max_size=0):
+        """sf_map_cluster_euclidean (pcl::EuclideanClusterExtraction): the connected pieces at `tolerance`, those with fewer than min_size
+        or more than max_size (> 0) points labelled -1, the others numbered by their smallest point -> (labels, sizes, stats dict)."""
+        return self._clusters(self.lib.sf_map_cluster_euclidean, C.c_double(tolerance), C.c_int64(int(min_size)), C.c_int64(int(max_size)))
 
     def build_neighbour_table(self):
         """sf_map_build_neighbour_table: per indexed point its up to 7 nearest other points and a radius free of any further

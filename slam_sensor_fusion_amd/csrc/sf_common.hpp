@@ -213,6 +213,8 @@ struct sf_map {
     // sf_map_*_outliers (and the sf_cloud_remove_*_outliers that run them on a temporary map), all in ORIGINAL point order:
     // keep flags uint8[n]; mean distances double[n] or neighbour counts int32[n]; the partial sums of the tree reduction
     sf::DevBuf out_flags, out_val, out_red;
+    // sf_map_cluster_* (and the sf_cloud_*_cluster[s] calls on a temporary map): the union-find, labels and sizes (sf_cluster.hpp, ClusterBufs)
+    sf::DevBuf cl;
     int64_t n = 0;
     bool built = false, has_normals = false, has_cov = false;
     uint64_t generation = 0; // process-unique stamp of the index contents (build / normals): captured hipGraphs key on it

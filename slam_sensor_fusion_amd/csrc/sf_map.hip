@@ -192,6 +192,7 @@ extern "C" void sf_map_destroy(sf_map *m)
         if (ev) { hipError_t e2 = hipEventDestroy(ev); (void)e2; }
     m->nbr.release();
     m->out_flags.release(); m->out_val.release(); m->out_red.release();
+    m->cl.release();
     sf_ctx *ctx = m->ctx;
     delete m;
     sf::ctx_release(ctx);
@@ -1670,6 +1671,13 @@ int statistical_outliers_device(sf_map *m, int K, bool pcl, double std_ratio, sf
     return read_kept(m, st);
 }
 
+// the reach (k_radius_count, (c)), in float64, capped by the grid before the conversion
+inline int radius_reach(const SfGrid &g, float r2)
+{
+    const double reach = std::ceil((std::sqrt((double)r2) * (1.0 + 1.0e-6) + (double)g.gap_eps) * (double)g.inv_h);
+    return (int)std::min(std::max(reach, 1.0), (double)std::max(g.dim[0], std::max(g.dim[1], g.dim[2])));
+}
+
 int radius_outliers_device(sf_map *m, double radius, int min_neighbors, sf_outlier_stats *st)
 {
     sf_ctx *ctx = m->ctx;
@@ -1681,9 +1689,7 @@ int radius_outliers_device(sf_map *m, double radius, int min_neighbors, sf_outli
     SF_TRY(outlier_buffers(m, sizeof(int32_t)));
     const float r2 = (float)(radius * radius);
     const SfGrid &g = m->grid;
-    // the reach (k_radius_count, (c)), in float64, capped by the grid before the conversion
-    const double reach = std::ceil((std::sqrt((double)r2) * (1.0 + 1.0e-6) + (double)g.gap_eps) * (double)g.inv_h);
-    const int R = (int)std::min(std::max(reach, 1.0), (double)std::max(g.dim[0], std::max(g.dim[1], g.dim[2])));
+    const int R = radius_reach(g, r2);
     SF_HIP(hipMemsetAsync(m->out_flags.p, 0, (size_t)n, s)); // points that are not indexed: not kept, no neighbours
     SF_HIP(hipMemsetAsync(m->out_val.p, 0, sizeof(int32_t) * (size_t)n, s));
     prof_begin(m);
@@ -1759,6 +1765,9 @@ extern "C" int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int m
     SF_CHECK_ROR(radius, min_neighbors);
     return remove_outliers(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return radius_outliers_device(m, radius, min_neighbors, st); });
 }
+
+// ------------------------------------------------------------------ clustering (extension, no reference code)
+#include "sf_cluster.hpp"
 
 extern "C" int sf_map_profile_launches(sf_map *m, int on)
 {
