@@ -56,7 +56,7 @@ extern "C" int sf_ctx_create(int device_id, void *hip_stream, sf_ctx **out)
         SF_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         ctx->own_stream = true;
     }
-    SF_HIP(hipHostMalloc(&ctx->h_pinned, 4096, hipHostMallocDefault));
+    SF_HIP(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_pinned), 4096, hipHostMallocDefault));
     *out = ctx;
     return SF_OK;
 }
@@ -357,7 +357,7 @@ int compact_cloud(sf_cloud *c, const uint8_t *d_flags)
     hipLaunchKernelGGL(k_count_flags, dim3((unsigned)nb), dim3(CB), 0, ctx->stream, d_flags, n, bc);
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, ctx->stream, bc, nb, bc + nb);
     hipLaunchKernelGGL(k_scatter_flags, dim3((unsigned)nb), dim3(CB), 0, ctx->stream, d_flags, n, bc, c->xyz.as<float>(), out.as<float>(), c->last_idx.as<int32_t>());
-    uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned);
+    uint32_t *h = ctx->h_pinned->counts;
     SF_HIP(hipMemcpyAsync(h, bc + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream)); // the kept count is a host value (sf_cloud_size)
     SF_HIP(hipGetLastError());

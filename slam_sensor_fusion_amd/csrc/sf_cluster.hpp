@@ -1,6 +1,7 @@
 // sf_cluster.hpp -- Euclidean and DBSCAN clustering of an indexed map (extension, no reference code).  Included by
 // sf_map.hip after the outlier block: it uses that block's k_radius_count, radius_reach, outlier_buffers, the kept counters and
-// the profiling span of sf_map.hip.
+// filter_cloud, and ProfSpan / read_words of sf_map.hip.  Neighbours are found by sf::radius_walk (sf_walk.hpp), the walk of
+// k_radius_count itself, so the core flags and the edges of the graph come from one rule and one proof.
 //
 // The graph: indexed points i != j are adjacent iff l2_simple(x_i, x_j) < r2 (float32, unfused, strict -- symmetric bit for bit).
 // Clusters are the connected components of the graph restricted to core points (count_i >= min_points; Euclidean: every indexed
@@ -12,59 +13,6 @@
 namespace {
 
 constexpr uint32_t CL_NONE = 0xFFFFFFFFu;
-
-// The row walk of k_radius_count -- the same block of cells, the same reach R, row skip and x-trim, so its proof (a)-(d) that
-// nothing the rule accepts is lost applies as it stands; only what is done with an accepted candidate differs.  visit(k, aux[k]) is
-// called for every sorted position k < end with l2_simple(p, pts[k]) < r2.  Rows lie in memory in the order they are walked, so the
-// first row that starts at or beyond `end` ends the walk.  AUX: aux[k] is loaded beside the point, four in flight as well, instead
-// of behind the comparison.
-template <bool AUX, class F>
-__device__ __forceinline__ void radius_walk(const SfGrid &g, const float4 p, float r2, int R, uint32_t end, const int32_t *__restrict__ aux, F visit)
-{
-    const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
-    const float gx = (p.x - g.org[0]) * g.inv_h, gy = (p.y - g.org[1]) * g.inv_h, gz = (p.z - g.org[2]) * g.inv_h;
-    const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
-    const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
-    const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
-    const int x0 = max(cx - R, 0), x1 = min(cx + R, nx - 1);
-    const int y0 = max(cy - R, 0), y1 = min(cy + R, ny - 1);
-    const int z0 = max(cz - R, 0), z1 = min(cz + R, nz - 1);
-    const float h = g.h, ge = g.gap_eps;
-    for (int z = z0; z <= z1; ++z) {
-        const float rz = sf::safe_gap(sf::cell_gap(gz, z, cz) * h, ge);
-        if (!(rz * rz * 0.998f < r2)) continue;
-        for (int y = y0; y <= y1; ++y) {
-            const float ry = sf::safe_gap(sf::cell_gap(gy, y, cy) * h, ge);
-            const float g2 = ry * ry + rz * rz;
-            if (!(g2 * 0.998f < r2)) continue;
-            int xa = x0, xb = x1;
-            while (xa < cx) {
-                const float gl = sf::safe_gap(sf::cell_gap(gx, xa, cx) * h, ge);
-                if ((g2 + gl * gl) * 0.998f < r2) break;
-                ++xa;
-            }
-            while (xb > cx) {
-                const float gr = sf::safe_gap(sf::cell_gap(gx, xb, cx) * h, ge);
-                if ((g2 + gr * gr) * 0.998f < r2) break;
-                --xb;
-            }
-            const size_t row = ((size_t)z * ny + y) * nx;
-            const uint32_t a = g.cell_start[row + xa];
-            if (a >= end) return;
-            const uint32_t b = min(g.cell_start[row + xb + 1], end);
-            for (uint32_t k = a; k < b; k += 4) { // four loads in flight, as k_radius_count has them
-                const float4 q0 = sf::load_point(g, k, true), q1 = sf::load_point(g, k + 1, k + 1 < b), q2 = sf::load_point(g, k + 2, k + 2 < b),
-                             q3 = sf::load_point(g, k + 3, k + 3 < b);
-                const int32_t a0 = AUX ? aux[k] : 0, a1 = AUX ? aux[k + 1 < b ? k + 1 : k] : 0, a2 = AUX ? aux[k + 2 < b ? k + 2 : k] : 0,
-                              a3 = AUX ? aux[k + 3 < b ? k + 3 : k] : 0;
-                if (sf::l2_simple(p.x, p.y, p.z, q0.x, q0.y, q0.z) < r2) visit(k, a0);
-                if (k + 1 < b && sf::l2_simple(p.x, p.y, p.z, q1.x, q1.y, q1.z) < r2) visit(k + 1, a1);
-                if (k + 2 < b && sf::l2_simple(p.x, p.y, p.z, q2.x, q2.y, q2.z) < r2) visit(k + 2, a2);
-                if (k + 3 < b && sf::l2_simple(p.x, p.y, p.z, q3.x, q3.y, q3.z) < r2) visit(k + 3, a3);
-            }
-        }
-    }
-}
 
 // ---- the union-find of k_cluster_hook.  parent[x] <= x always and parent[x] < x once x is not a root; a position that has
 // stopped being a root never becomes one again.  Inside the kernel EVERY access to parent[] is an agent-scope relaxed atomic
@@ -127,8 +75,8 @@ __global__ __launch_bounds__(256) void k_cluster_hook(SfGrid g, float r2, int R,
     if (j >= g.n) return;
     if (!ALL_CORE && !core[j]) return;
     uint32_t mine = (uint32_t)j;
-    radius_walk<false>(g, g.pts[j], r2, R, (uint32_t)j, nullptr, [&](uint32_t k, int32_t) {
-        if (ALL_CORE || core[k]) mine = cl_unite(parent, mine, k);
+    sf::radius_walk<false, true>(g, g.pts[j], r2, R, (uint32_t)j, nullptr, [&](uint32_t k, int32_t, bool hit) {
+        if (hit && (ALL_CORE || core[k])) mine = cl_unite(parent, mine, k);
     });
 }
 
@@ -206,7 +154,7 @@ __global__ __launch_bounds__(256) void k_cluster_border(SfGrid g, float r2, int 
     const uint32_t id = __float_as_uint(p.w);
     if (counts[id] <= 1) return;
     uint32_t best = CL_NONE;
-    radius_walk<true>(g, p, r2, R, (uint32_t)g.n, slab, [&](uint32_t, int32_t l) { best = min(best, (uint32_t)l); });
+    sf::radius_walk<true, false>(g, p, r2, R, 0u, slab, [&](uint32_t, int32_t l, bool hit) { if (hit) best = min(best, (uint32_t)l); });
     if (best != CL_NONE) {
         labels[id] = (int32_t)best;
         atomicAdd(sizes + best, 1);
@@ -315,6 +263,22 @@ int cluster_buffers(sf_map *m, ClusterBufs *b)
     return SF_OK;
 }
 
+// components of the core graph -> labels (and the border pass where there are points that are not core)
+template <bool ALL_CORE>
+int cluster_label(sf_map *m, const ClusterBufs &b, float r2, int R, const int32_t *counts)
+{
+    hipStream_t s = m->ctx->stream;
+    const SfGrid &g = m->grid;
+    const dim3 grid(nblk(g.n)), blk(256);
+    hipLaunchKernelGGL(k_cluster_hook<ALL_CORE>, grid, blk, 0, s, g, r2, R, b.core, b.parent);
+    hipLaunchKernelGGL(k_cluster_flatten<ALL_CORE>, grid, blk, 0, s, g, b.core, b.parent, b.rmin, b.rsize);
+    hipLaunchKernelGGL(k_cluster_heads<ALL_CORE>, grid, blk, 0, s, g.n, b.core, b.parent, b.rmin, b.head);
+    SF_TRY(sf::scan_u32<0>(m->ctx, b.head, b.head, m->n + 1));
+    hipLaunchKernelGGL(k_cluster_labels<ALL_CORE>, grid, blk, 0, s, g, b.core, b.parent, b.rmin, b.rsize, b.head, b.slab, b.labels, b.sizes);
+    if (!ALL_CORE) hipLaunchKernelGGL(k_cluster_border, grid, blk, 0, s, g, r2, R, counts, b.slab, b.labels, b.sizes);
+    return SF_OK;
+}
+
 // The clustering proper, shared by the four entry points.  min_points == 1: every indexed point is core, no counts are taken and
 // there is no border pass (the Euclidean form; min_size / max_size apply to it alone and are (1, 0) for DBSCAN).  Labels [n] and
 // sizes stay on the device (ClusterBufs), the statistics come to the host.  Arguments are checked by the callers.
@@ -336,7 +300,7 @@ int cluster_device(sf_map *m, double eps, int min_points, int64_t min_size, int6
     SF_HIP(hipMemsetAsync(b->head, 0, sizeof(uint32_t) * (size_t)(n + 1), s));
     SF_HIP(hipMemsetAsync(b->labels, 0xFF, sizeof(int32_t) * (size_t)n, s)); // -1: what is not indexed, not core and not border keeps it
     const uint32_t *n_clusters = b->head + n;
-    prof_begin(m);
+    ProfSpan span(m);
     if (nv > 0) {
         const dim3 grid(nblk(nv)), blk(256);
         int32_t *counts = m->out_val.as<int32_t>();
@@ -348,35 +312,12 @@ int cluster_device(sf_map *m, double eps, int min_points, int64_t min_size, int6
             hipLaunchKernelGGL(k_sum_kept, dim3(1), dim3(KEPT_SLOTS), 0, s, m->out_red.as<unsigned long long>());
         }
         hipLaunchKernelGGL(k_cluster_init, grid, blk, 0, s, g, all_core ? (const uint8_t *)nullptr : flags, b->parent, b->rmin, b->rsize, b->core);
-        if (all_core) {
-            hipLaunchKernelGGL(k_cluster_hook<true>, grid, blk, 0, s, g, r2, R, b->core, b->parent);
-            hipLaunchKernelGGL(k_cluster_flatten<true>, grid, blk, 0, s, g, b->core, b->parent, b->rmin, b->rsize);
-            hipLaunchKernelGGL(k_cluster_heads<true>, grid, blk, 0, s, nv, b->core, b->parent, b->rmin, b->head);
-        } else {
-            hipLaunchKernelGGL(k_cluster_hook<false>, grid, blk, 0, s, g, r2, R, b->core, b->parent);
-            hipLaunchKernelGGL(k_cluster_flatten<false>, grid, blk, 0, s, g, b->core, b->parent, b->rmin, b->rsize);
-            hipLaunchKernelGGL(k_cluster_heads<false>, grid, blk, 0, s, nv, b->core, b->parent, b->rmin, b->head);
-        }
-        int rc = sf::scan_u32<0>(ctx, b->head, b->head, n + 1);
-        if (rc != SF_OK) { // close the profiled span on the way out
-            prof_end(m);
-            return rc;
-        }
-        if (all_core)
-            hipLaunchKernelGGL(k_cluster_labels<true>, grid, blk, 0, s, g, b->core, b->parent, b->rmin, b->rsize, b->head, b->slab, b->labels, b->sizes);
-        else {
-            hipLaunchKernelGGL(k_cluster_labels<false>, grid, blk, 0, s, g, b->core, b->parent, b->rmin, b->rsize, b->head, b->slab, b->labels, b->sizes);
-            hipLaunchKernelGGL(k_cluster_border, grid, blk, 0, s, g, r2, R, counts, b->slab, b->labels, b->sizes);
-        }
+        SF_TRY(all_core ? cluster_label<true>(m, *b, r2, R, counts) : cluster_label<false>(m, *b, r2, R, counts));
         if (filter) { // rmin and rsize are free by now
             uint32_t *keepc = b->rmin;
             int32_t *sizes_out = reinterpret_cast<int32_t *>(b->rsize);
             hipLaunchKernelGGL(k_cluster_size_keep, dim3(nblk(nv + 1)), blk, 0, s, b->sizes, n_clusters, nv, min_size, max_size, keepc);
-            rc = sf::scan_u32<0>(ctx, keepc, keepc, nv + 1);
-            if (rc != SF_OK) {
-                prof_end(m);
-                return rc;
-            }
+            SF_TRY(sf::scan_u32<0>(ctx, keepc, keepc, nv + 1));
             hipLaunchKernelGGL(k_cluster_remap_sizes, grid, blk, 0, s, b->sizes, n_clusters, keepc, sizes_out);
             hipLaunchKernelGGL(k_cluster_remap_labels, dim3(nblk(n)), blk, 0, s, b->labels, n, keepc);
             n_clusters = keepc + nv;
@@ -384,13 +325,10 @@ int cluster_device(sf_map *m, double eps, int min_points, int64_t min_size, int6
         }
         hipLaunchKernelGGL(k_cluster_stats, grid, blk, 0, s, b->sizes_final, n_clusters, b->stat);
     }
-    prof_end(m);
-    unsigned long long *h = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(ctx->h_pinned) + OUT_PINNED_OFF);
-    SF_HIP(hipGetLastError());
-    SF_HIP(hipMemcpyAsync(h, b->stat, sizeof(unsigned long long) * 3, hipMemcpyDeviceToHost, s));
-    SF_HIP(hipMemcpyAsync(h + 3, m->out_red.as<unsigned long long>() + (size_t)KEPT_SLOTS * KEPT_STRIDE, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    SF_HIP(hipStreamSynchronize(s));
+    span.end();
+    SF_TRY(read_words(ctx, b->stat, 3, m->out_red.as<unsigned long long>() + (size_t)KEPT_SLOTS * KEPT_STRIDE, 1));
     prof_read(m);
+    const unsigned long long *h = ctx->h_pinned->readback;
     st->n_kept = (int64_t)h[0];
     st->largest_size = (int64_t)(h[1] >> 32);
     st->n_clusters = (int64_t)h[2];
@@ -411,29 +349,19 @@ int download_clusters(sf_map *m, const ClusterBufs &b, const sf_cluster_stats &s
     return SF_OK;
 }
 
-// index the cloud with a temporary map, cluster (Euclidean), turn the labels into flags on the device, compact (remove_outliers)
+// filter_cloud with Euclidean clustering: the labels become keep flags on the device
 int filter_cloud_clusters(sf_cloud *c, double tolerance, int64_t min_size, int64_t max_size, bool largest, float cell, sf_cluster_stats *stats)
 {
-    sf_cluster_stats st{0, 0, 0, 0, 0, 0, 0, 0};
-    if (stats) *stats = st;
-    sf::cloud_touch(c);
-    if (c->n == 0) { c->n_last_idx = 0; return SF_OK; }
-    sf_map *tmp = nullptr;
-    SF_TRY(sf_map_create(c->ctx, &tmp));
-    ClusterBufs b{};
-    int rc = sf_map_build(tmp, c, cell);
-    if (rc == SF_OK) rc = cluster_device(tmp, tolerance, 1, min_size, max_size, &b, &st);
-    if (rc == SF_OK) {
-        hipLaunchKernelGGL(k_cluster_keep_flags, dim3(nblk(tmp->n)), dim3(256), 0, c->ctx->stream, b.labels, tmp->n, largest ? 1 : 0, b.stat, tmp->out_flags.as<uint8_t>());
-        rc = sf::compact_cloud(c, tmp->out_flags.as<uint8_t>());
-    }
-    sf_map_destroy(tmp);
-    if (rc == SF_OK && largest) { // what stays is the largest cluster alone
-        st.n_kept = st.largest_size;
-        st.n_noise = st.n_valid - st.n_kept;
-    }
-    if (rc == SF_OK && stats) *stats = st;
-    return rc;
+    return filter_cloud(c, cell, stats, [=](sf_map *m, sf_cluster_stats *st) {
+        ClusterBufs b{};
+        SF_TRY(cluster_device(m, tolerance, 1, min_size, max_size, &b, st));
+        hipLaunchKernelGGL(k_cluster_keep_flags, dim3(nblk(m->n)), dim3(256), 0, m->ctx->stream, b.labels, m->n, largest ? 1 : 0, b.stat, m->out_flags.as<uint8_t>());
+        if (largest) { // what stays is the largest cluster alone
+            st->n_kept = st->largest_size;
+            st->n_noise = st->n_valid - st->n_kept;
+        }
+        return (int)SF_OK;
+    });
 }
 
 } // namespace

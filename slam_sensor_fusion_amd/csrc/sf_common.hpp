@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -89,6 +90,25 @@ struct DevBuf {
 
 inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+struct MergeExtremes { int mn[3], mx[3]; uint32_t touched_extreme, pad; }; // sf_cloud_voxel_merge (sf_voxel.hip)
+struct PatchFlags { uint32_t moved, pad; };                                // sf_map_patch (sf_map.hip)
+
+// sf_ctx::h_pinned: the 4 KiB of pinned staging, one member per user.  A copy into one member may still be in flight when the
+// next user writes its own (the merge's flag is read back by the synchronisation of the head scan), so members do not overlap
+// and their offsets stay where the users have always had them.
+struct PinnedStage {
+    uint32_t counts[2];                          // compact_cloud: the kept count; scan_heads, the merge: last prefix + last flag
+    alignas(32) uint32_t merge_flag;             // sf_cloud_voxel_merge: "keys not ascending"
+    alignas(128) MergeExtremes merge_ext;        // ... bounds of the centroids, a replaced extreme
+    alignas(256) PatchFlags patch;               // sf_map_patch
+    alignas(64) uint32_t carry_count;            // the normals carry: dirty positions
+    alignas(128) unsigned long long readback[8]; // sf_map.hip read_words: window count, outlier sums and kept count, cluster statistics
+};
+static_assert(sizeof(PinnedStage) <= 4096, "sf_ctx::h_pinned is 4 KiB");
+static_assert(offsetof(PinnedStage, merge_flag) == 32 && offsetof(PinnedStage, merge_ext) == 128 && offsetof(PinnedStage, patch) == 256 &&
+                  offsetof(PinnedStage, carry_count) == 320 && offsetof(PinnedStage, readback) == 384,
+              "the members keep their offsets");
+
 } // namespace sf
 
 struct sf_ctx {
@@ -102,7 +122,7 @@ struct sf_ctx {
     sf::DevBuf merge_tmp;  // sf_cloud_voxel_merge: per-voxel tables of the pending points
     uint64_t merge_epoch = 0; // bumped by every merge BEFORE it first reserves or writes merge_tmp, whichever path it then takes (sf_cloud::MergeRecord::epoch)
     sf::DevBuf vox_tmp[6]; // voxel grids: keys, keys', point ids, point ids', head flags, positions -- kept between calls (a growing map re-voxelises every few scans)
-    void *h_pinned = nullptr; // small pinned staging (4 KiB)
+    sf::PinnedStage *h_pinned = nullptr; // small pinned staging (4 KiB)
     // pageable -> device uploads go through two pinned buffers in turn (sf::upload_staged): the runtime's own staging of
     // a pageable hipMemcpyAsync moves ~5 GB/s and holds the host until the stream has reached the copy
     struct Stage { void *p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool pending = false; } stage[2];

@@ -914,9 +914,8 @@ struct CellKeyFn {
         const float qy = fmaf(P.T[4], p.x, fmaf(P.T[5], p.y, fmaf(P.T[6], p.z, P.T[7])));
         const float qz = fmaf(P.T[8], p.x, fmaf(P.T[9], p.y, fmaf(P.T[10], p.z, P.T[11])));
         if (!(isfinite(qx) && isfinite(qy) && isfinite(qz))) return sf::ORD_KEY_NONE; // non-finite queries go to the end of their scan
-        const int cx = (int)fminf(fmaxf(floorf((qx - g.org[0]) * g.inv_h), 0.0f), (float)(g.dim[0] - 1));
-        const int cy = (int)fminf(fmaxf(floorf((qy - g.org[1]) * g.inv_h), 0.0f), (float)(g.dim[1] - 1));
-        const int cz = (int)fminf(fmaxf(floorf((qz - g.org[2]) * g.inv_h), 0.0f), (float)(g.dim[2] - 1));
+        const int cx = sf::grid_cell((qx - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((qy - g.org[1]) * g.inv_h, g.dim[1]),
+                  cz = sf::grid_cell((qz - g.org[2]) * g.inv_h, g.dim[2]);
         if (lut) return (uint32_t)lut[order_cell(g, cx, cy, cz) >> lut_shift];
         const uint64_t key = order_cell(g, cx, cy, cz) >> shift;
         return (uint32_t)(key < (uint64_t)(sf::ORD_KEY_NONE - 1u) ? key : (uint64_t)(sf::ORD_KEY_NONE - 1u));
@@ -938,9 +937,8 @@ __global__ __launch_bounds__(256) void k_order_lut_hist(SfGrid g, int lut_shift,
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= g.n) return;
     const float4 p = g.pts[j];
-    const int cx = (int)fminf(fmaxf(floorf((p.x - g.org[0]) * g.inv_h), 0.0f), (float)(g.dim[0] - 1));
-    const int cy = (int)fminf(fmaxf(floorf((p.y - g.org[1]) * g.inv_h), 0.0f), (float)(g.dim[1] - 1));
-    const int cz = (int)fminf(fmaxf(floorf((p.z - g.org[2]) * g.inv_h), 0.0f), (float)(g.dim[2] - 1));
+    const int cx = sf::grid_cell((p.x - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((p.y - g.org[1]) * g.inv_h, g.dim[1]),
+              cz = sf::grid_cell((p.z - g.org[2]) * g.inv_h, g.dim[2]);
     atomicAdd(&hist[order_cell(g, cx, cy, cz) >> lut_shift], 1u);
 }
 // one workgroup: exclusive prefix of the histogram -> key of every stretch
@@ -1033,9 +1031,8 @@ struct TileKeyFn {
         const float qy = fmaf(P.T[4], p.x, fmaf(P.T[5], p.y, fmaf(P.T[6], p.z, P.T[7])));
         const float qz = fmaf(P.T[8], p.x, fmaf(P.T[9], p.y, fmaf(P.T[10], p.z, P.T[11])));
         if (!(isfinite(qx) && isfinite(qy) && isfinite(qz))) return TILE_KEY_NONE;
-        const int cx = (int)fminf(fmaxf(floorf((qx - g.org[0]) * g.inv_h), 0.0f), (float)(g.dim[0] - 1));
-        const int cy = (int)fminf(fmaxf(floorf((qy - g.org[1]) * g.inv_h), 0.0f), (float)(g.dim[1] - 1));
-        const int cz = (int)fminf(fmaxf(floorf((qz - g.org[2]) * g.inv_h), 0.0f), (float)(g.dim[2] - 1));
+        const int cx = sf::grid_cell((qx - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((qy - g.org[1]) * g.inv_h, g.dim[1]),
+                  cz = sf::grid_cell((qz - g.org[2]) * g.inv_h, g.dim[2]);
         return sf::tile_of_cell(tl, cx, cy, cz);
     }
     __device__ __forceinline__ uint32_t key(const Pose &P, const Point &p) const { return (full_key(P, p) >> (sf::ORD_KEY_BITS * digit)) & (uint32_t)(sf::ORD_BINS - 1); }

@@ -98,10 +98,7 @@ __device__ __forceinline__ int knn_search(const SfGrid &g, const SfWindow &w, fl
         if (gap * gap > thr) return 0;
     }
     const float gx = (qx - g.org[0]) * g.inv_h, gy = (qy - g.org[1]) * g.inv_h, gz = (qz - g.org[2]) * g.inv_h;
-    // clamp in float first: a far-away query must not overflow the int conversion
-    const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
-    const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
-    const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
+    const int cx = grid_cell(gx, nx), cy = grid_cell(gy, ny), cz = grid_cell(gz, nz);
     const float h = g.h, ge = g.gap_eps;
     const int rcap = max(nx, max(ny, nz));
     KnnSel sel;
@@ -129,6 +126,7 @@ __device__ __forceinline__ int knn_search(const SfGrid &g, const SfWindow &w, fl
                     const bool inner = R > KNN_FIRST_RING && abs(y - cy) < R && abs(z - cz) < R; // examined up to x +- (R - 1) by the rings before
                     if (!inner) {
                         if (side == 0) { // the whole x-run, less the end cells whose gap prunes them (the query's own column never is)
+                            // (trim_left / trim_right of sf_nn.hpp, written out: see there)
                             int xa = x0, xb = x1;
                             while (xa < cx) {
                                 const float gl = safe_gap(cell_gap(gx, xa, cx) * h, ge);
@@ -203,14 +201,7 @@ __device__ __forceinline__ int knn_search(const SfGrid &g, const SfWindow &w, fl
             }
         }
         if (sel.dirty && sel.cnt >= k) knn_compact(ws, sel, k, lane); // tau as tight as what has been seen allows
-        // distance from the query to the nearest face of the examined block that still has grid cells behind it (nn_rings)
-        float m = 3.0e38f;
-        if (cx - R > 0) m = fminf(m, (gx - (float)(cx - R)) * h);
-        if (cx + R < nx - 1) m = fminf(m, ((float)(cx + R + 1) - gx) * h);
-        if (cy - R > 0) m = fminf(m, (gy - (float)(cy - R)) * h);
-        if (cy + R < ny - 1) m = fminf(m, ((float)(cy + R + 1) - gy) * h);
-        if (cz - R > 0) m = fminf(m, (gz - (float)(cz - R)) * h);
-        if (cz + R < nz - 1) m = fminf(m, ((float)(cz + R + 1) - gz) * h);
+        const float m = block_face_gap(g, gx, gy, gz, cx, cy, cz, R);
         if (m >= 3.0e38f) break; // whole grid examined
         const float mm = safe_gap(m, ge) * 0.999f;
         if (__uint_as_float((uint32_t)(sel.tkey >> 32)) <= mm * mm) break;

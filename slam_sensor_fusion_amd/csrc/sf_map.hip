@@ -10,6 +10,7 @@
 #include "sf_common.hpp"
 #include "sf_nn.hpp"
 #include "sf_knn.hpp"
+#include "sf_walk.hpp"
 
 #include "sf_sort.hpp"
 #include <cmath>
@@ -21,25 +22,46 @@ inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)sf::div_up(n > 0
 
 struct GridGeom { float org[3]; float inv_h; int dim[3]; uint64_t ncell; };
 
-// sf_map_profile_launches: events around the launches of a query / estimate call, read after the call's own synchronise
-inline void prof_begin(sf_map *m)
-{
-    if (!m->profile) return;
-    for (int i = 0; i < 2; ++i) // (each on its own: one that could not be created is tried again, never recorded on)
-        if (!m->prof_ev[i] && hipEventCreate(&m->prof_ev[i]) != hipSuccess) { m->prof_ev[i] = nullptr; m->profile = false; return; }
-    hipError_t e = hipEventRecord(m->prof_ev[0], m->ctx->stream);
-    (void)e;
-}
-inline void prof_end(sf_map *m)
-{
-    if (!m->profile) return;
-    hipError_t e = hipEventRecord(m->prof_ev[1], m->ctx->stream);
-    (void)e;
-}
+// sf_map_profile_launches: events around the launches of a query / estimate call, read (prof_read) after the call's own
+// synchronise.  The span closes at end() or, on a return before it, when the scope is left: the next call never starts inside one.
+struct ProfSpan {
+    sf_map *m;
+    bool open = true;
+    explicit ProfSpan(sf_map *map) : m(map)
+    {
+        if (!m->profile) return;
+        for (int i = 0; i < 2; ++i) // (each on its own: one that could not be created is tried again, never recorded on)
+            if (!m->prof_ev[i] && hipEventCreate(&m->prof_ev[i]) != hipSuccess) { m->prof_ev[i] = nullptr; m->profile = false; return; }
+        hipError_t e = hipEventRecord(m->prof_ev[0], m->ctx->stream);
+        (void)e;
+    }
+    ProfSpan(const ProfSpan &) = delete;
+    ProfSpan &operator=(const ProfSpan &) = delete;
+    void end()
+    {
+        if (!open) return;
+        open = false;
+        if (!m->profile) return;
+        hipError_t e = hipEventRecord(m->prof_ev[1], m->ctx->stream);
+        (void)e;
+    }
+    ~ProfSpan() { end(); }
+};
 inline void prof_read(sf_map *m)
 {
     float ms = -1.0f;
     if (m->profile && hipEventElapsedTime(&ms, m->prof_ev[0], m->prof_ev[1]) == hipSuccess) m->last_launch_ms = ms;
+}
+
+// n (+ n2) 8-byte words from the device into ctx->h_pinned->readback, one run after the other; synchronises the stream
+int read_words(sf_ctx *ctx, const void *d, int n, const void *d2 = nullptr, int n2 = 0)
+{
+    unsigned long long *h = ctx->h_pinned->readback;
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(h, d, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (n2 > 0) SF_HIP(hipMemcpyAsync(h + n, d2, sizeof(unsigned long long) * (size_t)n2, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    return SF_OK;
 }
 
 // K = uint32_t while the grid has fewer than 2^32 cells, uint64_t beyond (large sparse extents: a dense table over
@@ -52,9 +74,7 @@ __global__ void k_cell_keys(const float *__restrict__ xyz, int64_t n, GridGeom g
     float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
     K key = (K)g.ncell; // non-finite points sort last and are not indexed (PCL drops them too)
     if (isfinite(x) && isfinite(y) && isfinite(z)) {
-        int cx = (int)fminf(fmaxf(floorf((x - g.org[0]) * g.inv_h), 0.0f), (float)(g.dim[0] - 1));
-        int cy = (int)fminf(fmaxf(floorf((y - g.org[1]) * g.inv_h), 0.0f), (float)(g.dim[1] - 1));
-        int cz = (int)fminf(fmaxf(floorf((z - g.org[2]) * g.inv_h), 0.0f), (float)(g.dim[2] - 1));
+        const int cx = sf::grid_cell((x - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((y - g.org[1]) * g.inv_h, g.dim[1]), cz = sf::grid_cell((z - g.org[2]) * g.inv_h, g.dim[2]);
         key = ((K)cz * (K)g.dim[1] + (K)cy) * (K)g.dim[0] + (K)cx;
     }
     keys[i] = key;
@@ -344,7 +364,7 @@ __device__ __forceinline__ uint32_t patch_key(const PatchGeom &g, float x, float
     return ((uint32_t)cz * (uint32_t)g.dim[1] + (uint32_t)cy) * (uint32_t)g.dim[0] + (uint32_t)cx;
 }
 
-struct PatchFlags { uint32_t moved, pad; };
+using sf::PatchFlags;
 
 // thread t in two roles.  As voxel g = t: key of its centroid, and the old entry it replaces marked in the bitmap over the old
 // sorted positions (+ the count of its block of 256 positions)
@@ -593,7 +613,7 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
              *blk_pre = reinterpret_cast<uint32_t *>(base + off_pre), *range = reinterpret_cast<uint32_t *>(base + off_range);
     uint64_t *packed = reinterpret_cast<uint64_t *>(base + off_packed);
     PatchFlags *d_ext = reinterpret_cast<PatchFlags *>(base + off_ext);
-    PatchFlags *h_ext = reinterpret_cast<PatchFlags *>(static_cast<unsigned char *>(ctx->h_pinned) + 256);
+    PatchFlags *h_ext = &ctx->h_pinned->patch;
     SF_TRY(m->pts4_alt.reserve(sizeof(float4) * (size_t)n_out));
     SF_TRY(m->keys.reserve(sizeof(uint32_t) * (size_t)n_out));
     if (carry) SF_TRY(m->nrm4_alt.reserve(sizeof(float4) * (size_t)n_out));
@@ -771,10 +791,8 @@ extern "C" int sf_map_window_count(sf_map *m, int64_t *n)
     unsigned long long *d = ctx->scratch2.as<unsigned long long>();
     SF_HIP(hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_window_count, dim3(nblk(m->grid.n)), dim3(256), 0, ctx->stream, m->grid, m->window, d);
-    unsigned long long *h = reinterpret_cast<unsigned long long *>(ctx->h_pinned);
-    SF_HIP(hipMemcpyAsync(h, d, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    *n = (int64_t)h[0];
+    SF_TRY(read_words(ctx, d, 1));
+    *n = (int64_t)ctx->h_pinned->readback[0];
     return SF_OK;
 }
 
@@ -790,12 +808,12 @@ extern "C" int sf_map_nn(sf_map *m, const float *queries, int64_t n, float max_d
     SF_TRY(di.reserve(sizeof(int32_t) * (size_t)n));
     SF_TRY(dd.reserve(sizeof(float) * (size_t)n));
     SF_HIP(hipMemcpyAsync(dq.p, queries, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    prof_begin(m);
+    ProfSpan span(m);
     if (m->window.kind)
         hipLaunchKernelGGL(k_map_nn_t<true>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, max_d2, di.as<int32_t>(), dd.as<float>());
     else
         hipLaunchKernelGGL(k_map_nn_t<false>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, max_d2, di.as<int32_t>(), dd.as<float>());
-    prof_end(m);
+    span.end();
     SF_HIP(hipGetLastError());
     SF_HIP(hipMemcpyAsync(idx, di.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipMemcpyAsync(d2, dd.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -818,36 +836,27 @@ __global__ __launch_bounds__(256) void k_neighbour_table(SfGrid g, uint4 *__rest
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= g.n) return;
     const float4 p = g.pts[j];
-    const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
-    const int cx = (int)fminf(fmaxf(floorf((p.x - g.org[0]) * g.inv_h), 0.0f), (float)(nx - 1));
-    const int cy = (int)fminf(fmaxf(floorf((p.y - g.org[1]) * g.inv_h), 0.0f), (float)(ny - 1));
-    const int cz = (int)fminf(fmaxf(floorf((p.z - g.org[2]) * g.inv_h), 0.0f), (float)(nz - 1));
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, nx - 1);
-    const int y0 = max(cy - 1, 0), y1 = min(cy + 1, ny - 1);
-    const int z0 = max(cz - 1, 0), z1 = min(cz + 1, nz - 1);
+    const int cx = sf::grid_cell((p.x - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((p.y - g.org[1]) * g.inv_h, g.dim[1]), cz = sf::grid_cell((p.z - g.org[2]) * g.inv_h, g.dim[2]);
     const float cap = sf::safe_gap(g.h, g.gap_eps) * 0.999f;
     const float cap2 = cap * cap;
     unsigned long long key[sf::NBR_K];
 #pragma unroll
     for (int i = 0; i < sf::NBR_K; ++i) key[i] = ~0ull;
-    for (int z = z0; z <= z1; ++z)
-        for (int y = y0; y <= y1; ++y) {
-            const size_t row = ((size_t)z * ny + y) * nx;
-            const uint32_t a = g.cell_start[row + x0], b = g.cell_start[row + x1 + 1];
-            for (uint32_t k = a; k < b; ++k) {
-                const float4 q = g.pts[k];
-                const float d2 = sf::l2_simple(p.x, p.y, p.z, q.x, q.y, q.z);
-                if (k == (uint32_t)j || !(d2 < cap2)) continue;
-                unsigned long long v = sf::hit_key(d2, (int)k);
-                if (v >= key[sf::NBR_K - 1]) continue;
+    sf::block_rows(g, cx, cy, cz, 1, [&](uint32_t a, uint32_t b) {
+        for (uint32_t k = a; k < b; ++k) {
+            const float4 q = g.pts[k];
+            const float d2 = sf::l2_simple(p.x, p.y, p.z, q.x, q.y, q.z);
+            if (k == (uint32_t)j || !(d2 < cap2)) continue;
+            unsigned long long v = sf::hit_key(d2, (int)k);
+            if (v >= key[sf::NBR_K - 1]) continue;
 #pragma unroll
-                for (int i = 0; i < sf::NBR_K; ++i) { // v sinks to its place, the larger keys move down one, the largest falls out
-                    const unsigned long long lo = v < key[i] ? v : key[i], hi = v < key[i] ? key[i] : v;
-                    key[i] = lo;
-                    v = hi;
-                }
+            for (int i = 0; i < sf::NBR_K; ++i) { // v sinks to its place, the larger keys move down one, the largest falls out
+                const unsigned long long lo = v < key[i] ? v : key[i], hi = v < key[i] ? key[i] : v;
+                key[i] = lo;
+                v = hi;
             }
         }
+    });
     const bool full = key[sf::NBR_K - 1] != ~0ull;
     const float r = full ? sqrtf(__uint_as_float((uint32_t)(key[sf::NBR_K - 1] >> 32))) * 0.9999f : cap;
     // (an absent slot's key is all ones: its low half is the "none" id)
@@ -1041,12 +1050,12 @@ extern "C" int sf_map_knn(sf_map *m, const float *queries, int64_t n, int k, flo
     SF_TRY(dd.reserve(sizeof(float) * (size_t)n * (size_t)k));
     SF_TRY(dc.reserve(sizeof(int32_t) * (size_t)n));
     SF_HIP(hipMemcpyAsync(dq.p, queries, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    prof_begin(m);
+    ProfSpan span(m);
     if (m->window.kind)
         hipLaunchKernelGGL(k_map_knn_t<true>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, k, max_d2, di.as<int32_t>(), dd.as<float>(), dc.as<int32_t>());
     else
         hipLaunchKernelGGL(k_map_knn_t<false>, dim3(nblk(n)), dim3(256), 0, ctx->stream, m->grid, m->window, dq.as<float>(), n, k, max_d2, di.as<int32_t>(), dd.as<float>(), dc.as<int32_t>());
-    prof_end(m);
+    span.end();
     SF_HIP(hipGetLastError());
     SF_HIP(hipMemcpyAsync(idx, di.p, sizeof(int32_t) * (size_t)n * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipMemcpyAsync(d2, dd.p, sizeof(float) * (size_t)n * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
@@ -1105,66 +1114,9 @@ __device__ void smallest_eigvec(const double C[9], double nrm[3])
     nrm[0] = x; nrm[1] = y; nrm[2] = z;
 }
 
-// the estimate of sorted position j: cells z-major, then y, then one contiguous x-run per row, ascending id inside a cell.  The
-// order of these float64 sums is what makes a carried estimate (sf_map_patch) the bits of a full one: k_normals and
-// k_normals_list both come here
-__device__ __forceinline__ void normals_point(const SfGrid &g, double r2, int R, int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
-{
-    const float4 p = g.pts[j];
-    const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
-    const int cx = (int)fminf(fmaxf(floorf((p.x - g.org[0]) * g.inv_h), 0.0f), (float)(nx - 1));
-    const int cy = (int)fminf(fmaxf(floorf((p.y - g.org[1]) * g.inv_h), 0.0f), (float)(ny - 1));
-    const int cz = (int)fminf(fmaxf(floorf((p.z - g.org[2]) * g.inv_h), 0.0f), (float)(nz - 1));
-    const int x0 = max(cx - R, 0), x1 = min(cx + R, nx - 1);
-    const int y0 = max(cy - R, 0), y1 = min(cy + R, ny - 1);
-    const int z0 = max(cz - R, 0), z1 = min(cz + R, nz - 1);
-    double sum[3] = {0, 0, 0}, mean[3] = {0, 0, 0}, C[6] = {0, 0, 0, 0, 0, 0};
-    int cnt = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1) {
-            if (cnt < 3) break;
-            for (int d = 0; d < 3; ++d) mean[d] = sum[d] / cnt;
-        }
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y) {
-                const size_t row = ((size_t)z * ny + y) * nx;
-                const uint32_t a = g.cell_start[row + x0], b = g.cell_start[row + x1 + 1];
-                for (uint32_t k = a; k < b; ++k) {
-                    const float4 q = g.pts[k];
-                    const double ex = (double)q.x - (double)p.x, ey = (double)q.y - (double)p.y, ez = (double)q.z - (double)p.z;
-                    if (!(ex * ex + ey * ey + ez * ez <= r2)) continue;
-                    if (pass == 0) { sum[0] += q.x; sum[1] += q.y; sum[2] += q.z; ++cnt; }
-                    else {
-                        const double ax = q.x - mean[0], ay = q.y - mean[1], az = q.z - mean[2];
-                        C[0] += ax * ax; C[1] += ax * ay; C[2] += ax * az; C[3] += ay * ay; C[4] += ay * az; C[5] += az * az;
-                    }
-                }
-            }
-    }
-    double nv[3] = {0, 0, 1};
-    if (cnt >= 3) {
-        const double M[9] = {C[0], C[1], C[2], C[1], C[3], C[4], C[2], C[4], C[5]};
-        smallest_eigvec(M, nv);
-    }
-    nrm4[j] = make_float4((float)nv[0], (float)nv[1], (float)nv[2], __int_as_float(cnt));
-    if (cov6) { // xx xy xz yy yz zz of the centred neighbourhood, divided by the neighbour count (zeros below 3 neighbours)
-#pragma unroll
-        for (int d = 0; d < 6; ++d) cov6[6 * (size_t)j + d] = cnt >= 3 ? C[d] / (double)cnt : 0.0;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, int R, float4 *__restrict__ nrm4, double *__restrict__ cov6)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= g.n) return;
-    normals_point(g, r2, R, j, nrm4, cov6);
-}
-
-// ---- k-NN / hybrid normals (DESIGN §13): the neighbourhood is the k-NN list of the point's own coordinates (sf_knn.hpp), the
-// float64 sums run over the list positions in the pairwise tree of wave_tree_sum (absent positions +0.0), so they depend on the
-// list alone.  A wave walks its 64 consecutive points one after another; each lane keeps the count and the six sums of "its"
-// point in registers and the Jacobi solve then runs once, lane per point (not once per wave with 63 lanes redundant).
-__device__ __forceinline__ void knn_normal_finish(int cnt, const double C[6], int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+// position j's normal (the smallest eigenvector of the centred sums C of its cnt neighbours; +z below 3), the count in .w, and
+// where asked xx xy xz yy yz zz of the centred neighbourhood divided by the count (zeros below 3 neighbours)
+__device__ __forceinline__ void store_normal_cov(int cnt, const double C[6], int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
 {
     double nv[3] = {0, 0, 1};
     if (cnt >= 3) {
@@ -1178,6 +1130,47 @@ __device__ __forceinline__ void knn_normal_finish(int cnt, const double C[6], in
     }
 }
 
+// the estimate of sorted position j: cells z-major, then y, then one contiguous x-run per row (block_rows), ascending id inside a
+// cell.  The order of these float64 sums is what makes a carried estimate (sf_map_patch) the bits of a full one: k_normals and
+// k_normals_list both come here
+__device__ __forceinline__ void normals_point(const SfGrid &g, double r2, int R, int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+{
+    const float4 p = g.pts[j];
+    const int cx = sf::grid_cell((p.x - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((p.y - g.org[1]) * g.inv_h, g.dim[1]), cz = sf::grid_cell((p.z - g.org[2]) * g.inv_h, g.dim[2]);
+    double sum[3] = {0, 0, 0}, mean[3] = {0, 0, 0}, C[6] = {0, 0, 0, 0, 0, 0};
+    int cnt = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1) {
+            if (cnt < 3) break;
+            for (int d = 0; d < 3; ++d) mean[d] = sum[d] / cnt;
+        }
+        sf::block_rows(g, cx, cy, cz, R, [&](uint32_t a, uint32_t b) {
+            for (uint32_t k = a; k < b; ++k) {
+                const float4 q = g.pts[k];
+                const double ex = (double)q.x - (double)p.x, ey = (double)q.y - (double)p.y, ez = (double)q.z - (double)p.z;
+                if (!(ex * ex + ey * ey + ez * ez <= r2)) continue;
+                if (pass == 0) { sum[0] += q.x; sum[1] += q.y; sum[2] += q.z; ++cnt; }
+                else {
+                    const double ax = q.x - mean[0], ay = q.y - mean[1], az = q.z - mean[2];
+                    C[0] += ax * ax; C[1] += ax * ay; C[2] += ax * az; C[3] += ay * ay; C[4] += ay * az; C[5] += az * az;
+                }
+            }
+        });
+    }
+    store_normal_cov(cnt, C, j, nrm4, cov6);
+}
+
+__global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, int R, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= g.n) return;
+    normals_point(g, r2, R, j, nrm4, cov6);
+}
+
+// ---- k-NN / hybrid normals (DESIGN §13): the neighbourhood is the k-NN list of the point's own coordinates (sf_knn.hpp), the
+// float64 sums run over the list positions in the pairwise tree of wave_tree_sum (absent positions +0.0), so they depend on the
+// list alone.  A wave walks its 64 consecutive points one after another; each lane keeps the count and the six sums of "its"
+// point in registers and the Jacobi solve then runs once, lane per point (not once per wave with 63 lanes redundant).
 __global__ __launch_bounds__(256) void k_normals_knn(SfGrid g, SfWindow w, int k, float thr, float4 *__restrict__ nrm4, double *__restrict__ cov6)
 {
     __shared__ sf::WaveKNN ws[256 / 64];
@@ -1214,7 +1207,7 @@ __global__ __launch_bounds__(256) void k_normals_knn(SfGrid g, SfWindow w, int k
         }
     }
     if (i >= g.n) return;
-    knn_normal_finish(mycnt, myC, i, nrm4, cov6);
+    store_normal_cov(mycnt, myC, i, nrm4, cov6);
 }
 
 // ---- the estimate carried over sf_map_patch: only where a neighbourhood changed
@@ -1235,25 +1228,18 @@ __global__ __launch_bounds__(256) void k_normals_mark(SfGrid g, int odx, int ody
     const float *src = removed ? g_old : g_centroid;
     const float px = src[3 * v], py = src[3 * v + 1], pz = src[3 * v + 2];
     const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
-    const int cx = (int)fminf(fmaxf(floorf((px - g.org[0]) * g.inv_h), 0.0f), (float)((removed ? odx : nx) - 1));
-    const int cy = (int)fminf(fmaxf(floorf((py - g.org[1]) * g.inv_h), 0.0f), (float)((removed ? ody : ny) - 1));
-    const int cz = (int)fminf(fmaxf(floorf((pz - g.org[2]) * g.inv_h), 0.0f), (float)((removed ? odz : nz) - 1));
-    const int x0 = max(cx - R, 0), x1 = min(cx + R, nx - 1);
-    const int y0 = max(cy - R, 0), y1 = min(cy + R, ny - 1);
-    const int z0 = max(cz - R, 0), z1 = min(cz + R, nz - 1);
-    if (x0 > x1) return; // (a removed point beyond a grid that shrank; only x is tested: the x-run reads cell_start before its own loop test, empty y / z ranges never enter theirs)
-    for (int z = z0; z <= z1; ++z)
-        for (int y = y0; y <= y1; ++y) {
-            const size_t row = ((size_t)z * ny + y) * nx;
-            const uint32_t a = g.cell_start[row + x0], b = g.cell_start[row + x1 + 1];
-            for (uint32_t k = a; k < b; ++k) {
-                const float4 q = g.pts[k];
-                const double ex = (double)px - (double)q.x, ey = (double)py - (double)q.y, ez = (double)pz - (double)q.z;
-                if (!(ex * ex + ey * ey + ez * ez <= r2)) continue;
-                const uint32_t bit = 1u << (k & 31u);
-                if (!(bitmap[k >> 5] & bit)) atomicOr(&bitmap[k >> 5], bit); // (neighbouring positions mark the same points: most find the bit set)
-            }
+    const int cx = sf::grid_cell((px - g.org[0]) * g.inv_h, removed ? odx : nx), cy = sf::grid_cell((py - g.org[1]) * g.inv_h, removed ? ody : ny),
+              cz = sf::grid_cell((pz - g.org[2]) * g.inv_h, removed ? odz : nz);
+    if (max(cx - R, 0) > min(cx + R, nx - 1)) return; // (a removed point beyond a grid that shrank; only x is tested: block_rows reads the bounds of the x-run before any test, empty y / z ranges never enter their loops)
+    sf::block_rows(g, cx, cy, cz, R, [&](uint32_t a, uint32_t b) {
+        for (uint32_t k = a; k < b; ++k) {
+            const float4 q = g.pts[k];
+            const double ex = (double)px - (double)q.x, ey = (double)py - (double)q.y, ez = (double)pz - (double)q.z;
+            if (!(ex * ex + ey * ey + ez * ez <= r2)) continue;
+            const uint32_t bit = 1u << (k & 31u);
+            if (!(bitmap[k >> 5] & bit)) atomicOr(&bitmap[k >> 5], bit); // (neighbouring positions mark the same points: most find the bit set)
         }
+    });
 }
 
 // dirty positions per block of 256 (8 words of the bitmap)
@@ -1308,7 +1294,7 @@ int carry_reestimate(sf_map *m, const sf_cloud::MergeRecord &rec, const int old_
     hipLaunchKernelGGL(k_normals_mark, dim3(nblk(2 * ng)), dim3(256), 0, st, g, old_dim[0], old_dim[1], old_dim[2], r2, R, rec.g_fresh, rec.g_centroid, rec.g_old, ng, bitmap);
     hipLaunchKernelGGL(k_normals_count, dim3(nblk(nb)), dim3(256), 0, st, bitmap, nb, blk_cnt);
     SF_TRY(sf::scan_u32<0>(ctx, blk_cnt, blk_pre, nb + 1));
-    uint32_t *h_cnt = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(ctx->h_pinned) + 320);
+    uint32_t *h_cnt = &ctx->h_pinned->carry_count;
     SF_HIP(hipMemcpyAsync(h_cnt, blk_pre + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SF_HIP(hipGetLastError());
     SF_HIP(hipStreamSynchronize(st)); // the one read-back: the size of the list launch (and sf_map_normals_carry_info)
@@ -1353,33 +1339,43 @@ __global__ void k_normals_to_host_order(SfGrid g, const float4 *__restrict__ nrm
 
 } // namespace
 
-extern "C" int sf_map_estimate_normals_cov(sf_map *m, float radius, int with_covariance)
+namespace {
+// what the two estimates share: the buffers, the profiled span around launch(nrm4, cov6 or nullptr), the synchronise and the
+// record of how the normals were made (what sf_map_patch carries or re-runs: sf_map_set_normals_carry)
+template <class L>
+int estimate_normals(sf_map *m, int knn_k, float radius, int with_covariance, L launch)
 {
-    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
-    SF_CHECK(radius > 0, SF_ERR_INVALID, "radius must be positive");
     sf_ctx *ctx = m->ctx;
     SF_HIP(hipSetDevice(ctx->device));
     SF_TRY(m->nrm4.reserve(sizeof(float4) * (size_t)std::max<int64_t>(m->n, 1)));
     m->has_cov = false;
     if (with_covariance) SF_TRY(m->cov6.reserve(sizeof(double) * 6 * (size_t)std::max<int64_t>(m->n, 1)));
-    const int R = normals_reach(radius, m->grid.h);
-    prof_begin(m);
-    if (m->grid.n > 0)
-        hipLaunchKernelGGL(k_normals, dim3(nblk(m->grid.n)), dim3(256), 0, ctx->stream, m->grid, (double)radius * (double)radius, R, m->nrm4.as<float4>(),
-                           with_covariance ? m->cov6.as<double>() : nullptr);
-    prof_end(m);
+    ProfSpan span(m);
+    if (m->grid.n > 0) launch(m->nrm4.as<float4>(), with_covariance ? m->cov6.as<double>() : nullptr);
+    span.end();
     SF_HIP(hipGetLastError());
     SF_HIP(hipStreamSynchronize(ctx->stream));
     prof_read(m);
     m->grid.nrm = m->nrm4.as<float4>();
     m->has_normals = true;
     m->has_cov = with_covariance != 0;
-    m->nrm_estimated = true; // what sf_map_patch carries (sf_map_set_normals_carry)
-    m->nrm_knn_k = 0;
+    m->nrm_estimated = true;
+    m->nrm_knn_k = knn_k; // 0: the radius form, carried; > 0: re-run in full behind a patch
     m->nrm_radius = radius;
     m->nrm_with_cov = with_covariance != 0;
     m->generation = sf::next_generation();
     return SF_OK;
+}
+} // namespace
+
+extern "C" int sf_map_estimate_normals_cov(sf_map *m, float radius, int with_covariance)
+{
+    SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
+    SF_CHECK(radius > 0, SF_ERR_INVALID, "radius must be positive");
+    const int R = normals_reach(radius, m->grid.h);
+    return estimate_normals(m, 0, radius, with_covariance, [&](float4 *nrm4, double *cov6) {
+        hipLaunchKernelGGL(k_normals, dim3(nblk(m->grid.n)), dim3(256), 0, m->ctx->stream, m->grid, (double)radius * (double)radius, R, nrm4, cov6);
+    });
 }
 
 extern "C" int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, int with_covariance)
@@ -1387,29 +1383,10 @@ extern "C" int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, i
     SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
     SF_CHECK(k >= 1 && k <= SF_KNN_MAX, SF_ERR_INVALID, "k must be 1 .. %d (got %d)", SF_KNN_MAX, k);
     SF_CHECK(!std::isnan(max_radius), SF_ERR_INVALID, "max_radius must be a number (<= 0 or inf: no limit)");
-    sf_ctx *ctx = m->ctx;
-    SF_HIP(hipSetDevice(ctx->device));
-    SF_TRY(m->nrm4.reserve(sizeof(float4) * (size_t)std::max<int64_t>(m->n, 1)));
-    m->has_cov = false;
-    if (with_covariance) SF_TRY(m->cov6.reserve(sizeof(double) * 6 * (size_t)std::max<int64_t>(m->n, 1)));
     const float thr = (max_radius > 0 && std::isfinite(max_radius)) ? (float)(max_radius * max_radius) : INFINITY;
-    SfWindow none{};
-    prof_begin(m);
-    if (m->grid.n > 0)
-        hipLaunchKernelGGL(k_normals_knn, dim3(nblk(m->grid.n)), dim3(256), 0, ctx->stream, m->grid, none, k, thr, m->nrm4.as<float4>(), with_covariance ? m->cov6.as<double>() : nullptr);
-    prof_end(m);
-    SF_HIP(hipGetLastError());
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    prof_read(m);
-    m->grid.nrm = m->nrm4.as<float4>();
-    m->has_normals = true;
-    m->has_cov = with_covariance != 0;
-    m->nrm_estimated = true; // what sf_map_patch re-estimates (sf_map_set_normals_carry): in full, by this call
-    m->nrm_knn_k = k;
-    m->nrm_radius = max_radius;
-    m->nrm_with_cov = with_covariance != 0;
-    m->generation = sf::next_generation();
-    return SF_OK;
+    return estimate_normals(m, k, max_radius, with_covariance, [&](float4 *nrm4, double *cov6) {
+        hipLaunchKernelGGL(k_normals_knn, dim3(nblk(m->grid.n)), dim3(256), 0, m->ctx->stream, m->grid, SfWindow{}, k, thr, nrm4, cov6);
+    });
 }
 
 // ------------------------------------------------------------------ outlier removal (extension, no reference code)
@@ -1501,24 +1478,9 @@ __global__ __launch_bounds__(256) void k_flag_mean_dist(const double *__restrict
     add_kept(keep, kept);
 }
 
-// count_j = the number of indexed points q with l2_simple(p_j, q) < r2 (float32, unfused, strict; p_j itself included), one lane per
-// indexed point, walking the block of cells within R of its own cell row by row, each row one contiguous cell_start run.
-//
-// Nothing the rule accepts is lost.  Write G(x) = fl(fl(x - org) * inv_h) for the grid coordinate every point is binned by
-// (k_cell_keys; the cell is floor(G) clamped to the grid), u = 2^-24, and let q be accepted for p.
-// (a) Per axis |p - q| < r (1 + 2u), r = sqrt(r2): rounding is monotone, so the float sum of non-negative terms is at least each
-//     term, fl(d2) >= fl(fl(dx)^2) >= dx^2 (1 - u)^3, and fl(d2) < r2.  (A square that underflows belongs to |dx| < 2^-62 m.)
-// (b) G(x) = (x - org) inv_h (1 + e1)(1 + e2), |e| <= u, and (x - org) inv_h < dim (1 + u) for every indexed point, so
-//     |G(p) - G(q)| <= |p - q| inv_h + S with S = 2^-22 maxdim (1 + 3u) cells: S h is below gap_eps = 1.5 * 2^-22 maxdim h, the
-//     slack SfGrid carries for exactly this.
-// (c) Reach: floor(a) - floor(b) <= ceil(D) whenever a - b <= D, and the clamp only brings cells closer, so q's cell is within
-//     R = ceil((r (1 + 1e-6) + gap_eps) inv_h) of p's on every axis (the host computes it in float64; 1e-6 covers (a) and its own
-//     roundings).  normals_reach's ceil(radius / h - 1e-9) is one short when r is a whole number of cells and p, q straddle it.
-// (d) Row skip and x-trim, the rule of knn_search with tau = r2: a point binned in cell c != cq has G on the far side of the face
-//     between, so by (b) its true axis distance from p is at least safe_gap(cell_gap * h, gap_eps), up to the relative roundings of
-//     forming it (a few u).  A row or an end cell is left out only when the sum g2 of those squared gaps has g2 * 0.998 >= r2;
-//     then dy^2 + dz^2 (+ dx^2) >= g2 (1 - 8u) and fl(d2) >= that (1 - 5u) >= r2 / 0.998 * (1 - 13u) > r2: rejected by the rule itself.
-// No early exit at count > min_neighbors: the counts are an output.
+// count_j = the number of indexed points q with l2_simple(p_j, q) < r2 (p_j itself included), one lane per indexed point: the
+// radius_walk of sf_walk.hpp, which proves that nothing the rule accepts is lost.  No early exit at count > min_neighbors: the
+// counts are an output.
 __global__ __launch_bounds__(256) void k_radius_count(SfGrid g, float r2, int R, int min_neighbors, int32_t *__restrict__ n_neighbors, uint8_t *__restrict__ flags,
                                                        unsigned long long *__restrict__ kept)
 {
@@ -1526,46 +1488,8 @@ __global__ __launch_bounds__(256) void k_radius_count(SfGrid g, float r2, int R,
     bool keep = false;
     if (j < g.n) {
         const float4 p = g.pts[j];
-        const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
-        const float gx = (p.x - g.org[0]) * g.inv_h, gy = (p.y - g.org[1]) * g.inv_h, gz = (p.z - g.org[2]) * g.inv_h;
-        const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
-        const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
-        const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
-        const int x0 = max(cx - R, 0), x1 = min(cx + R, nx - 1);
-        const int y0 = max(cy - R, 0), y1 = min(cy + R, ny - 1);
-        const int z0 = max(cz - R, 0), z1 = min(cz + R, nz - 1);
-        const float h = g.h, ge = g.gap_eps;
         int cnt = 0;
-        for (int z = z0; z <= z1; ++z) {
-            const float rz = sf::safe_gap(sf::cell_gap(gz, z, cz) * h, ge);
-            if (!(rz * rz * 0.998f < r2)) continue;
-            for (int y = y0; y <= y1; ++y) {
-                const float ry = sf::safe_gap(sf::cell_gap(gy, y, cy) * h, ge);
-                const float g2 = ry * ry + rz * rz;
-                if (!(g2 * 0.998f < r2)) continue;
-                int xa = x0, xb = x1; // the x-run less the end cells whose gap excludes them (the point's own column never is)
-                while (xa < cx) {
-                    const float gl = sf::safe_gap(sf::cell_gap(gx, xa, cx) * h, ge);
-                    if ((g2 + gl * gl) * 0.998f < r2) break;
-                    ++xa;
-                }
-                while (xb > cx) {
-                    const float gr = sf::safe_gap(sf::cell_gap(gx, xb, cx) * h, ge);
-                    if ((g2 + gr * gr) * 0.998f < r2) break;
-                    --xb;
-                }
-                const size_t row = ((size_t)z * ny + y) * nx;
-                const uint32_t a = g.cell_start[row + xa], b = g.cell_start[row + xb + 1];
-                for (uint32_t k = a; k < b; k += 4) { // four loads in flight (scan4 of sf_nn.hpp)
-                    const float4 q0 = sf::load_point(g, k, true), q1 = sf::load_point(g, k + 1, k + 1 < b), q2 = sf::load_point(g, k + 2, k + 2 < b),
-                                 q3 = sf::load_point(g, k + 3, k + 3 < b);
-                    cnt += sf::l2_simple(p.x, p.y, p.z, q0.x, q0.y, q0.z) < r2 ? 1 : 0;
-                    cnt += (k + 1 < b && sf::l2_simple(p.x, p.y, p.z, q1.x, q1.y, q1.z) < r2) ? 1 : 0;
-                    cnt += (k + 2 < b && sf::l2_simple(p.x, p.y, p.z, q2.x, q2.y, q2.z) < r2) ? 1 : 0;
-                    cnt += (k + 3 < b && sf::l2_simple(p.x, p.y, p.z, q3.x, q3.y, q3.z) < r2) ? 1 : 0;
-                }
-            }
-        }
+        sf::radius_walk<false, false>(g, p, r2, R, 0u, nullptr, [&](uint32_t, int32_t, bool hit) { cnt += hit ? 1 : 0; });
         const uint32_t id = __float_as_uint(p.w);
         keep = cnt > min_neighbors;
         n_neighbors[id] = cnt;
@@ -1583,9 +1507,6 @@ inline int sor_list_length(int k, int flavour)
 }
 #define SF_CHECK_SOR(k, flavour) SF_CHECK(sor_list_length(k, flavour) > 0, SF_ERR_INVALID, "statistical outliers: flavour SF_SOR_PCL with k 1 .. %d or SF_SOR_O3D with k 1 .. %d (got flavour %d, k %d)", SF_KNN_MAX - 1, SF_KNN_MAX, flavour, k)
 #define SF_CHECK_ROR(radius, min_neighbors) SF_CHECK((radius) > 0 && std::isfinite(radius) && (min_neighbors) >= 0, SF_ERR_INVALID, "radius outliers: radius must be positive and finite, min_neighbors >= 0 (got %g, %d)", (double)(radius), min_neighbors)
-
-// where the host reads the sums and the kept count (ctx->h_pinned; the compaction, the patch and the carry use the bytes below 384)
-constexpr size_t OUT_PINNED_OFF = 384;
 
 // out_red: [the kept counters and their sum, KEPT_WORDS words | the levels of the tree, one after another]
 int outlier_buffers(sf_map *m, size_t val_bytes)
@@ -1616,23 +1537,16 @@ int tree_sum(sf_map *m, const double *v, int64_t n, bool sq, double mean, double
         cnt = nb;
         first = false;
     } while (cnt > 1);
-    double *h = reinterpret_cast<double *>(static_cast<unsigned char *>(ctx->h_pinned) + OUT_PINNED_OFF);
-    SF_HIP(hipGetLastError());
-    SF_HIP(hipMemcpyAsync(h, in, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
-    *h_sum = *h;
+    SF_TRY(read_words(ctx, in, 1));
+    std::memcpy(h_sum, ctx->h_pinned->readback, sizeof(double));
     return SF_OK;
 }
 
 int read_kept(sf_map *m, sf_outlier_stats *st)
 {
-    sf_ctx *ctx = m->ctx;
-    unsigned long long *h = reinterpret_cast<unsigned long long *>(static_cast<unsigned char *>(ctx->h_pinned) + OUT_PINNED_OFF);
-    SF_HIP(hipGetLastError());
-    SF_HIP(hipMemcpyAsync(h, m->out_red.as<unsigned long long>() + (size_t)KEPT_SLOTS * KEPT_STRIDE, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipStreamSynchronize(ctx->stream));
+    SF_TRY(read_words(m->ctx, m->out_red.as<unsigned long long>() + (size_t)KEPT_SLOTS * KEPT_STRIDE, 1));
     prof_read(m);
-    st->n_kept = (int64_t)*h;
+    st->n_kept = (int64_t)m->ctx->h_pinned->readback[0];
     return SF_OK;
 }
 
@@ -1648,7 +1562,7 @@ int statistical_outliers_device(sf_map *m, int K, bool pcl, double std_ratio, sf
     if (n == 0) return SF_OK;
     SF_TRY(outlier_buffers(m, sizeof(double)));
     double *dist = m->out_val.as<double>();
-    prof_begin(m);
+    ProfSpan span(m);
     hipLaunchKernelGGL(k_fill_f64, dim3(nblk(n)), dim3(256), 0, s, dist, n, (double)NAN);
     if (nv > 0) {
         hipLaunchKernelGGL(k_knn_mean_dist, dim3(nblk(nv)), dim3(256), 0, s, m->grid, K, pcl ? 1 : 0, dist);
@@ -1659,19 +1573,16 @@ int statistical_outliers_device(sf_map *m, int K, bool pcl, double std_ratio, sf
             rc = tree_sum(m, dist, n, true, st->mean, &sum2);
             st->stddev = std::sqrt(sum2 / (double)(nv - 1));
         }
-        if (rc != SF_OK) { // close the profiled span on the way out, so that the next call does not start inside one
-            prof_end(m);
-            return rc;
-        }
+        SF_TRY(rc);
         st->threshold = st->mean + std_ratio * st->stddev;
     }
     hipLaunchKernelGGL(k_flag_mean_dist, dim3(nblk(n)), dim3(256), 0, s, dist, n, st->threshold, pcl ? 0 : 1, m->out_flags.as<uint8_t>(), m->out_red.as<unsigned long long>());
     hipLaunchKernelGGL(k_sum_kept, dim3(1), dim3(KEPT_SLOTS), 0, s, m->out_red.as<unsigned long long>());
-    prof_end(m);
+    span.end();
     return read_kept(m, st);
 }
 
-// the reach (k_radius_count, (c)), in float64, capped by the grid before the conversion
+// the reach (radius_walk, (c)), in float64, capped by the grid before the conversion
 inline int radius_reach(const SfGrid &g, float r2)
 {
     const double reach = std::ceil((std::sqrt((double)r2) * (1.0 + 1.0e-6) + (double)g.gap_eps) * (double)g.inv_h);
@@ -1692,12 +1603,12 @@ int radius_outliers_device(sf_map *m, double radius, int min_neighbors, sf_outli
     const int R = radius_reach(g, r2);
     SF_HIP(hipMemsetAsync(m->out_flags.p, 0, (size_t)n, s)); // points that are not indexed: not kept, no neighbours
     SF_HIP(hipMemsetAsync(m->out_val.p, 0, sizeof(int32_t) * (size_t)n, s));
-    prof_begin(m);
+    ProfSpan span(m);
     if (nv > 0)
         hipLaunchKernelGGL(k_radius_count, dim3(nblk(nv)), dim3(256), 0, s, g, r2, R, min_neighbors, m->out_val.as<int32_t>(), m->out_flags.as<uint8_t>(),
                            m->out_red.as<unsigned long long>());
     hipLaunchKernelGGL(k_sum_kept, dim3(1), dim3(KEPT_SLOTS), 0, s, m->out_red.as<unsigned long long>());
-    prof_end(m);
+    span.end();
     return read_kept(m, st);
 }
 
@@ -1711,18 +1622,19 @@ int download_outliers(sf_map *m, uint8_t *keep, void *val, size_t val_bytes)
     return SF_OK;
 }
 
-// index the cloud with a temporary map, flag, compact (the order is kept: compact_cloud, as after a crop)
-template <class F>
-int remove_outliers(sf_cloud *c, float cell, sf_outlier_stats *stats, F filter)
+// index the cloud with a temporary map, let flag(map, &st) leave the keep flags in its out_flags, compact (the order is kept:
+// compact_cloud, as after a crop).  The outlier filters and the cluster filters (sf_cluster.hpp) of a cloud all come here.
+template <class S, class F>
+int filter_cloud(sf_cloud *c, float cell, S *stats, F flag)
 {
-    sf_outlier_stats st{0, 0, 0, 0.0, 0.0, 0.0};
+    S st{};
     if (stats) *stats = st;
     sf::cloud_touch(c);
     if (c->n == 0) { c->n_last_idx = 0; return SF_OK; }
     sf_map *tmp = nullptr;
     SF_TRY(sf_map_create(c->ctx, &tmp));
     int rc = sf_map_build(tmp, c, cell);
-    if (rc == SF_OK) rc = filter(tmp, &st);
+    if (rc == SF_OK) rc = flag(tmp, &st);
     if (rc == SF_OK) rc = sf::compact_cloud(c, tmp->out_flags.as<uint8_t>());
     sf_map_destroy(tmp);
     if (rc == SF_OK && stats) *stats = st;
@@ -1756,14 +1668,14 @@ extern "C" int sf_cloud_remove_statistical_outliers(sf_cloud *c, int k, double s
     SF_CHECK(c, SF_ERR_INVALID, "bad arguments");
     SF_CHECK_SOR(k, flavour);
     const int K = sor_list_length(k, flavour);
-    return remove_outliers(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return statistical_outliers_device(m, K, flavour == SF_SOR_PCL, std_ratio, st); });
+    return filter_cloud(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return statistical_outliers_device(m, K, flavour == SF_SOR_PCL, std_ratio, st); });
 }
 
 extern "C" int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int min_neighbors, float cell, sf_outlier_stats *stats)
 {
     SF_CHECK(c, SF_ERR_INVALID, "bad arguments");
     SF_CHECK_ROR(radius, min_neighbors);
-    return remove_outliers(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return radius_outliers_device(m, radius, min_neighbors, st); });
+    return filter_cloud(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return radius_outliers_device(m, radius, min_neighbors, st); });
 }
 
 // ------------------------------------------------------------------ clustering (extension, no reference code)

@@ -221,6 +221,51 @@ __device__ __forceinline__ float cell_gap(float gc, int c, int cq)
     return d > 0.0f ? d : 0.0f;
 }
 
+// the cell of grid coordinate gc on an axis of n cells.  Clamp in float first: a far-away query must not overflow the int
+// conversion
+__device__ __forceinline__ int grid_cell(float gc, int n) { return (int)fminf(fmaxf(floorf(gc), 0.0f), (float)(n - 1)); }
+
+// The exactness certificate: the distance from grid coordinates (gx, gy, gz), binned in cell (cx, cy, cz), to the nearest face of
+// the block of radius R around that cell that still has grid cells behind it; 3e38 when the block covers the grid.  Every point
+// outside the block is at least safe_gap(this, gap_eps) away.
+__device__ __forceinline__ float block_face_gap(const SfGrid &g, float gx, float gy, float gz, int cx, int cy, int cz, int R)
+{
+    const float h = g.h;
+    float m = 3.0e38f;
+    if (cx - R > 0) m = fminf(m, (gx - (float)(cx - R)) * h);
+    if (cx + R < g.dim[0] - 1) m = fminf(m, ((float)(cx + R + 1) - gx) * h);
+    if (cy - R > 0) m = fminf(m, (gy - (float)(cy - R)) * h);
+    if (cy + R < g.dim[1] - 1) m = fminf(m, ((float)(cy + R + 1) - gy) * h);
+    if (cz - R > 0) m = fminf(m, (gz - (float)(cz - R)) * h);
+    if (cz + R < g.dim[2] - 1) m = fminf(m, ((float)(cz + R + 1) - gz) * h);
+    return m;
+}
+
+// Row trim: the x-run [x0, x1] of a row whose (y, z) gap squared is g2, less the end cells whose own gap prunes them against
+// `bound` (the query's own column cx never is).  Two functions that return a value: one with two reference results more than
+// doubled every kernel that inlines it.  radius_walk (sf_walk.hpp) calls them; knn_search keeps the two loops written out,
+// because called there they made k_normals_knn 0.3 - 4 % slower (profiles/grid_walk_first_form_ab.jsonl).
+__device__ __forceinline__ int trim_left(const SfGrid &g, float gx, int cx, int x0, float g2, float bound)
+{
+    int xa = x0;
+    while (xa < cx) {
+        const float gl = safe_gap(cell_gap(gx, xa, cx) * g.h, g.gap_eps);
+        if ((g2 + gl * gl) * 0.998f < bound) break;
+        ++xa;
+    }
+    return xa;
+}
+__device__ __forceinline__ int trim_right(const SfGrid &g, float gx, int cx, int x1, float g2, float bound)
+{
+    int xb = x1;
+    while (xb > cx) {
+        const float gr = safe_gap(cell_gap(gx, xb, cx) * g.h, g.gap_eps);
+        if ((g2 + gr * gr) * 0.998f < bound) break;
+        --xb;
+    }
+    return xb;
+}
+
 // thr: candidates are accepted iff d2 < thr (reference: max_correspondence_dist_ itself,
 // icp_point_to_point.cpp:70; Open3D: radius^2)
 // rings R_first, R_first + 1, ... around the query's cell until the exactness test holds
@@ -229,10 +274,7 @@ __device__ __forceinline__ void nn_rings(const SfGrid &g, const SfWindow &w, flo
 {
     const float gx = (qx - g.org[0]) * g.inv_h, gy = (qy - g.org[1]) * g.inv_h, gz = (qz - g.org[2]) * g.inv_h;
     const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
-    // clamp in float first: a far-away query must not overflow the int conversion
-    const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
-    const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
-    const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
+    const int cx = grid_cell(gx, nx), cy = grid_cell(gy, ny), cz = grid_cell(gz, nz);
     const float h = g.h;
     const int rcap = max(nx, max(ny, nz));
 
@@ -318,15 +360,7 @@ __device__ __forceinline__ void nn_rings(const SfGrid &g, const SfWindow &w, flo
                 }
             }
         }
-        // distance from the query to the nearest face of the scanned block that still has
-        // grid cells behind it
-        float m = 3.0e38f;
-        if (cx - R > 0) m = fminf(m, (gx - (float)(cx - R)) * h);
-        if (cx + R < nx - 1) m = fminf(m, ((float)(cx + R + 1) - gx) * h);
-        if (cy - R > 0) m = fminf(m, (gy - (float)(cy - R)) * h);
-        if (cy + R < ny - 1) m = fminf(m, ((float)(cy + R + 1) - gy) * h);
-        if (cz - R > 0) m = fminf(m, (gz - (float)(cz - R)) * h);
-        if (cz + R < nz - 1) m = fminf(m, ((float)(cz + R + 1) - gz) * h);
+        const float m = block_face_gap(g, gx, gy, gz, cx, cy, cz, R);
         if (m >= 3.0e38f) break; // whole grid scanned
         const float mm = safe_gap(m, g.gap_eps) * 0.999f;
         if (hit.d2 <= mm * mm) break;
@@ -397,9 +431,9 @@ __device__ __forceinline__ QueryGeo query_geo(const SfGrid &g, float qx, float q
 {
     QueryGeo G;
     const float gx = (qx - g.org[0]) * g.inv_h, gy = (qy - g.org[1]) * g.inv_h, gz = (qz - g.org[2]) * g.inv_h;
-    G.cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(g.dim[0] - 1));
-    G.cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(g.dim[1] - 1));
-    G.cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(g.dim[2] - 1));
+    G.cx = grid_cell(gx, g.dim[0]);
+    G.cy = grid_cell(gy, g.dim[1]);
+    G.cz = grid_cell(gz, g.dim[2]);
     const float h = g.h;
     const float fx = gx - (float)G.cx, fy = gy - (float)G.cy, fz = gz - (float)G.cz;
     const float ge = g.gap_eps;
@@ -738,17 +772,8 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
         }
         // exactness of ring 1 (same test as nn_rings); otherwise on to ring 2
         const float gx = (qx - g.org[0]) * g.inv_h, gy = (qy - g.org[1]) * g.inv_h, gz = (qz - g.org[2]) * g.inv_h;
-        const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
-        const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
-        const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
-        const float h = g.h;
-        float mface = 3.0e38f;
-        if (cx - 1 > 0) mface = fminf(mface, (gx - (float)(cx - 1)) * h);
-        if (cx + 1 < nx - 1) mface = fminf(mface, ((float)(cx + 2) - gx) * h);
-        if (cy - 1 > 0) mface = fminf(mface, (gy - (float)(cy - 1)) * h);
-        if (cy + 1 < ny - 1) mface = fminf(mface, ((float)(cy + 2) - gy) * h);
-        if (cz - 1 > 0) mface = fminf(mface, (gz - (float)(cz - 1)) * h);
-        if (cz + 1 < nz - 1) mface = fminf(mface, ((float)(cz + 2) - gz) * h);
+        const int cx = grid_cell(gx, nx), cy = grid_cell(gy, ny), cz = grid_cell(gz, nz);
+        const float mface = block_face_gap(g, gx, gy, gz, cx, cy, cz, 1);
         const float mm = safe_gap(mface, g.gap_eps) * 0.999f;
         if (mface < 3.0e38f) {
             hit.lb2 = fminf(hit.lb2, mm * mm); // nothing outside the 27 cells is closer than their boundary
@@ -789,9 +814,7 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
             const int dyi = r / side - R, dzi = r - (r / side) * side - R;
             const float4 Q = ws->q[owner];
             const float gx = (Q.x - g.org[0]) * g.inv_h, gy = (Q.y - g.org[1]) * g.inv_h, gz = (Q.z - g.org[2]) * g.inv_h;
-            const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
-            const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
-            const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
+            const int cx = grid_cell(gx, nx), cy = grid_cell(gy, ny), cz = grid_cell(gz, nz);
             const int y = cy + dyi, z = cz + dzi;
             if ((unsigned)y >= (unsigned)ny || (unsigned)z >= (unsigned)nz) continue;
             const float ry = safe_gap(cell_gap(gy, y, cy) * h, ge), rz = safe_gap(cell_gap(gz, z, cz) * h, ge);
@@ -835,16 +858,8 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
             }
             hit.lb2 = 0.0f; // no runner-up bound is kept beyond ring 1
             const float gx = (qx - g.org[0]) * g.inv_h, gy = (qy - g.org[1]) * g.inv_h, gz = (qz - g.org[2]) * g.inv_h;
-            const int cx = (int)fminf(fmaxf(floorf(gx), 0.0f), (float)(nx - 1));
-            const int cy = (int)fminf(fmaxf(floorf(gy), 0.0f), (float)(ny - 1));
-            const int cz = (int)fminf(fmaxf(floorf(gz), 0.0f), (float)(nz - 1));
-            float mface = 3.0e38f; // the nearest face of the block of radius R that still has grid cells behind it
-            if (cx - R > 0) mface = fminf(mface, (gx - (float)(cx - R)) * h);
-            if (cx + R < nx - 1) mface = fminf(mface, ((float)(cx + R + 1) - gx) * h);
-            if (cy - R > 0) mface = fminf(mface, (gy - (float)(cy - R)) * h);
-            if (cy + R < ny - 1) mface = fminf(mface, ((float)(cy + R + 1) - gy) * h);
-            if (cz - R > 0) mface = fminf(mface, (gz - (float)(cz - R)) * h);
-            if (cz + R < nz - 1) mface = fminf(mface, ((float)(cz + R + 1) - gz) * h);
+            const int cx = grid_cell(gx, nx), cy = grid_cell(gy, ny), cz = grid_cell(gz, nz);
+            const float mface = block_face_gap(g, gx, gy, gz, cx, cy, cz, R);
             const float mm = safe_gap(mface, ge) * 0.999f;
             more = mface < 3.0e38f && !(hit.d2 <= mm * mm);
         }

@@ -209,16 +209,8 @@ __device__ __forceinline__ TileHit tile_search(const SfGrid &g, const TileRegion
         tile_scan(L, xm ? s0 : s1, xp ? s3 : s2, qx, qy, qz, hit);
     }
     // exactness of ring 1 (the test of nn_search_wave): the nearest face of the 27 cells that still has grid cells behind it
-    const int nx = g.dim[0];
     const float gx = (qx - g.org[0]) * g.inv_h, gy = (qy - g.org[1]) * g.inv_h, gz = (qz - g.org[2]) * g.inv_h;
-    const float h = g.h;
-    float mface = 3.0e38f;
-    if (G.cx - 1 > 0) mface = fminf(mface, (gx - (float)(G.cx - 1)) * h);
-    if (G.cx + 1 < nx - 1) mface = fminf(mface, ((float)(G.cx + 2) - gx) * h);
-    if (G.cy - 1 > 0) mface = fminf(mface, (gy - (float)(G.cy - 1)) * h);
-    if (G.cy + 1 < nyg - 1) mface = fminf(mface, ((float)(G.cy + 2) - gy) * h);
-    if (G.cz - 1 > 0) mface = fminf(mface, (gz - (float)(G.cz - 1)) * h);
-    if (G.cz + 1 < nzg - 1) mface = fminf(mface, ((float)(G.cz + 2) - gz) * h);
+    const float mface = block_face_gap(g, gx, gy, gz, G.cx, G.cy, G.cz, 1);
     const float mm = safe_gap(mface, g.gap_eps) * 0.999f;
     *more = false;
     if (mface < 3.0e38f) {

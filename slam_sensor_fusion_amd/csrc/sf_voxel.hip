@@ -126,7 +126,7 @@ int scan_heads(sf_ctx *ctx, const K *keys, int64_t n_valid, uint32_t *flags, uin
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_heads<K>, dim3(nblk(n_valid)), dim3(256), 0, st, keys, n_valid, flags);
     SF_TRY(sf::scan_u32<0>(ctx, flags, pos, n_valid));
-    uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned);
+    uint32_t *h = ctx->h_pinned->counts;
     SF_HIP(hipMemcpyAsync(h, pos + (n_valid - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SF_HIP(hipMemcpyAsync(h + 1, flags + (n_valid - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     SF_HIP(hipStreamSynchronize(st));
@@ -358,7 +358,7 @@ inline float float_from_ordered(int o)
     return f;
 }
 
-struct MergeExtremes { int mn[3], mx[3]; uint32_t touched_extreme, pad; };
+using sf::MergeExtremes;
 
 // bounds of the centroids; does a replaced old point hold one of the map's bounds?  (a few workgroups, grid-stride: the six
 // atomics per workgroup all land on one cache line)
@@ -528,15 +528,15 @@ extern "C" int sf_cloud_voxel_merge(sf_cloud *map, sf_cloud *pending, double lea
     uint32_t *sk = nullptr, *sv = nullptr;
     SF_TRY(sf::radix_sort_pairs<uint32_t>(ctx, nk, nk2, nv, nv2, m, end_bit, &sk, &sv));
     int64_t n_groups = 0;
-    uint32_t *h_flag = reinterpret_cast<uint32_t *>(ctx->h_pinned) + 8;
+    uint32_t *h_flag = &ctx->h_pinned->merge_flag;
     SF_HIP(hipMemcpyAsync(h_flag, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st)); // (read back by the synchronisation inside scan_heads)
     SF_TRY(scan_heads<uint32_t>(ctx, sk, b.n_finite, flags.as<uint32_t>(), pos.as<uint32_t>(), &n_groups));
     if (*h_flag) return full_path();
     hipLaunchKernelGGL(k_merge_groups, dim3(nblk(b.n_finite)), dim3(256), 0, st, map->xyz.as<float>(), old_keys.as<uint32_t>(), n, pending->xyz.as<float>(), sk, sv, flags.as<uint32_t>(),
                        pos.as<uint32_t>(), b.n_finite, g_rank, g_fresh, g_centroid, g_old);
     SF_TRY(sf::scan_u32<0>(ctx, g_fresh, fresh_pos, n_groups));
-    uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned);
-    MergeExtremes *h_ext = reinterpret_cast<MergeExtremes *>(static_cast<unsigned char *>(ctx->h_pinned) + 128);
+    uint32_t *h = ctx->h_pinned->counts;
+    MergeExtremes *h_ext = &ctx->h_pinned->merge_ext;
     for (int d = 0; d < 3; ++d) { h_ext->mn[d] = INT32_MAX; h_ext->mx[d] = INT32_MIN; }
     h_ext->touched_extreme = h_ext->pad = 0u;
     SF_HIP(hipMemcpyAsync(d_ext, h_ext, sizeof(MergeExtremes), hipMemcpyHostToDevice, st));

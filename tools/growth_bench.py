@@ -6,7 +6,8 @@ scans of --scan-points points, half of them re-observing the map and half beyond
 --normals RADIUS adds two legs on the same workload for a map that keeps normals (point-to-plane registration): "patch + full
 estimate" (sf_map_patch, then sf_map_estimate_normals over the whole map) and "patch with carry" (sf_map_set_normals_carry:
 the normals ride along with the patch and are estimated again only where the merge changed a neighbourhood), and compares
-the two results bit for bit after the last step.
+the two results bit for bit after the last step.  Every leg also lists the times of its steps (step_ms_all: merge + index, ms), for a
+caller that needs the spread behind the medians.
    python tools/growth_bench.py [--map-points 20000000] [--steps 12] [--normals 0.25]"""
 import argparse
 import json
@@ -81,7 +82,7 @@ def main():
                 elif how == "patch_full_estimate":
                     redone.append(1.0)
         out[how] = dict(merge_ms_median=float(np.median(t_merge)), index_ms_median=float(np.median(t_index)), step_ms_median=float(np.median(np.add(t_merge, t_index))),
-                        step_ms_max=float(np.max(np.add(t_merge, t_index))), merged_steps=n_merged, patched_steps=patched, map_points_start_end=[int(n0), int(len(cloud))])
+                        step_ms_max=float(np.max(np.add(t_merge, t_index))), step_ms_all=[round(float(t), 4) for t in np.add(t_merge, t_index)], merged_steps=n_merged, patched_steps=patched, map_points_start_end=[int(n0), int(len(cloud))])
         if how in ("patch_full_estimate", "patch_carry"):
             # the normals' share of the step: the estimate itself / what the patch takes beyond the plain patch leg of this run
             nrm_ms = float(np.median(t_normals)) if how == "patch_full_estimate" else out[how]["index_ms_median"] - out["patch"]["index_ms_median"]
