@@ -858,6 +858,27 @@ int sf_ekf_update_pose_cov(sf_ekf *e, const double T[16], const double cov[36]);
 int sf_ekf_get(const sf_ekf *e, double T[16], double v[3], double P[81]);            /* any output may be NULL; P = the (dp, dv, dtheta) block */
 int sf_ekf_get_full(const sf_ekf *e, double gyro_bias[3], double accel_bias[3], double P[225]); /* biases and the whole 15x15 covariance */
 
+/* ------------------------------------------------------------------ test hooks (NOT part of the drop-in boundary)
+ * The stable radix sort and the device scans every indexed structure stands on (voxel grids, grid index, sorted crop,
+ * cluster labels), run directly on host arrays so that the suite can compare them with a plain reference.  No reference
+ * counterpart; nothing in an integration calls them.  Both run the library's own kernels on the context's stream,
+ * synchronise and copy the result back.  Every device array is carved from one allocation as
+ * [guard | lead | n elements | guard] with guards of 4096 elements holding a fixed pattern; *guard_damage = the 32-bit
+ * guard words that no longer hold it afterwards (0 unless a kernel wrote outside its array).
+ * sf_test_radix_sort: stable sort of n (key, value) pairs by the low passes x bits bits of the key, passes =
+ *   ceil(end_bit / 8), bits = ceil(end_bit / passes) (end_bit rounded up to equally wide passes; every key arrives whole).
+ *   vals == vals_out == NULL: keys only.  lead / lead_alt: elements by which the first element of the primary /
+ *   ping-pong arrays is displaced from a 16-byte boundary.
+ * sf_test_scan_u32: op 0: out[i] = carry0 + in[0] + ... + in[i-1] (uint32 arithmetic); op 1: out[i] = max(carry0, in[0..i]).
+ *   in_place != 0 scans the device array onto itself.
+ * n = 0 and n = 1 succeed.  SF_ERR_INVALID, nothing touched: key_bytes not 4 or 8; end_bit = 0 with n > 1 or
+ * end_bit > 8 key_bytes; a lead outside 0..3; op not 0 or 1; n < 0 or n > 2^26; a NULL array that is needed (vals and
+ * vals_out go together). */
+int sf_test_radix_sort(sf_ctx *ctx, int key_bytes /* 4 | 8 */, const void *keys, const uint32_t *vals /* or NULL: keys only */, int64_t n, unsigned end_bit,
+                       int lead /* 0..3 */, int lead_alt /* 0..3 */, void *keys_out, uint32_t *vals_out /* or NULL */, int64_t *guard_damage);
+int sf_test_scan_u32(sf_ctx *ctx, int op /* 0: exclusive sum, 1: inclusive max */, const uint32_t *in, int64_t n, uint32_t carry0, int in_place, uint32_t *out,
+                     int64_t *guard_damage);
+
 #ifdef __cplusplus
 }
 #endif

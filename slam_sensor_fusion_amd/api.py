@@ -134,6 +134,8 @@ def load_library():
     lib.sf_icp_set_degeneracy_thresholds.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]
     lib.sf_icp_fetch_covariance.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_icp_fetch_covariance_previous.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_test_radix_sort.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_test_scan_u32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -169,6 +171,31 @@ def _f64(a):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def hook_radix_sort(ctx, keys, vals, end_bit, lead=0, lead_alt=0):
+    """Test hook (sf_test_radix_sort): the library's stable radix sort on host arrays.  keys: uint32 or uint64; vals: uint32
+    or None (keys only).  Returns (sorted keys, sorted vals or None, damaged guard words)."""
+    keys = np.ascontiguousarray(keys)
+    if keys.dtype not in (np.uint32, np.uint64):
+        raise SlamFusionError("hook_radix_sort: keys must be uint32 or uint64, not %s" % keys.dtype)
+    vals = None if vals is None else np.ascontiguousarray(vals, dtype=np.uint32)
+    keys_out = np.empty_like(keys)
+    vals_out = None if vals is None else np.empty_like(vals)
+    damage = C.c_int64(-1)
+    _check(ctx.lib.sf_test_radix_sort(ctx.h, keys.dtype.itemsize, _p(keys), None if vals is None else _p(vals), len(keys), int(end_bit), int(lead), int(lead_alt),
+                                      _p(keys_out), None if vals is None else _p(vals_out), C.addressof(damage)))
+    return keys_out, vals_out, damage.value
+
+
+def hook_scan_u32(ctx, op, values, carry0=0, in_place=False):
+    """Test hook (sf_test_scan_u32): the library's device scan of a uint32 array, op 0 = carry0 + exclusive sum, 1 = inclusive
+    max with carry0.  Returns (scanned array, damaged guard words)."""
+    values = np.ascontiguousarray(values, dtype=np.uint32)
+    out = np.empty_like(values)
+    damage = C.c_int64(-1)
+    _check(ctx.lib.sf_test_scan_u32(ctx.h, int(op), _p(values), len(values), int(carry0), int(bool(in_place)), _p(out), C.addressof(damage)))
+    return out, damage.value
 
 
 def _pc2_layout(msg):

@@ -288,7 +288,8 @@ __global__ __launch_bounds__(SORT_BLK) void k_scan_apply(const uint32_t *__restr
     }
 }
 
-// out[i] = sum of in[0..i) (OP 0) or max(carry0, in[0..i]) (OP 1); in == out allowed.  Enqueue only.
+// out[i] = carry0 + sum of in[0..i) (OP 0, uint32 arithmetic: wraps) or max(carry0, in[0..i]) (OP 1): k_scan_tiles starts both
+// operations from carry0.  in == out allowed.  Enqueue only.
 template <int OP>
 int scan_u32(sf_ctx *ctx, const uint32_t *in, uint32_t *out, int64_t n, uint32_t carry0 = 0u)
 {
@@ -304,7 +305,11 @@ int scan_u32(sf_ctx *ctx, const uint32_t *in, uint32_t *out, int64_t n, uint32_t
     return SF_OK;
 }
 
-// Sorts n pairs by the low `end_bit` bits of the key, stable.  vals / vals_alt may both be NULL (keys only).  keys / vals and keys_alt / vals_alt are ping-pong buffers of n
+// Sorts n pairs, stable, by the low passes x bits bits of the key: passes = ceil(end_bit / 8) equally wide passes of
+// bits = ceil(end_bit / passes) bits, which can be up to 7 bits MORE than end_bit (end_bit 9 -> 2 x 5 = 10, 17 -> 3 x 6 = 18,
+// 25 -> 4 x 7 = 28).  Bits above passes x bits are ignored and every key arrives whole.  Callers keep their keys below
+// 2^end_bit, so for them this is the order of the whole key; a caller that leaves other data above end_bit must expect the
+// extra bits to take part.  vals / vals_alt may both be NULL (keys only).  keys / vals and keys_alt / vals_alt are ping-pong buffers of n
 // elements; *keys_sorted / *vals_sorted point at the buffers that hold the result.  Enqueue only (context stream).
 template <class K>
 int radix_sort_pairs(sf_ctx *ctx, K *keys, K *keys_alt, uint32_t *vals, uint32_t *vals_alt, int64_t n, unsigned end_bit, K **keys_sorted, uint32_t **vals_sorted)

@@ -8,7 +8,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("n,extent", [(1, 1.0), (63, 0.5), (4097, 3.0), (300_000, 30.0), (1_000_003, 8.0)])
+@pytest.mark.parametrize("n,extent", [(1, 1.0), (63, 0.5), (4097, 3.0), (300_000, 30.0), (1_000_003, 8.0),
+                                      (1_048_576, 8.0), (1_048_577, 8.0)])   # 2^20 and 2^20 + 1: the 16-keys-per-thread sort right at its boundary
 def test_voxel_grid_matches_oracle_across_sizes(api, ctx, orc, n, extent):
     rng = np.random.default_rng(n)
     pts = rng.uniform(-extent, extent, (n, 3)).astype(np.float32)
