@@ -879,6 +879,46 @@ int sf_test_radix_sort(sf_ctx *ctx, int key_bytes /* 4 | 8 */, const void *keys,
 int sf_test_scan_u32(sf_ctx *ctx, int op /* 0: exclusive sum, 1: inclusive max */, const uint32_t *in, int64_t n, uint32_t carry0, int in_place, uint32_t *out,
                      int64_t *guard_damage);
 
+/* The float64 numerical core, run directly on host float64 arrays: the hooks launch kernels that CALL
+ * the production device functions of csrc/sf_icp.hip, csrc/sf_cov.hpp and csrc/sf_map.hip -- no copy, no second
+ * implementation -- on the context's stream, synchronise and copy the result back.
+ * sf_test_linalg: `cases` independent cases, one per thread in workgroups of 64 (one working lane per case, as in
+ *   production).  Case i reads in[i * in_stride ..] and writes out[i * out_stride ..]; doubles read / written by op:
+ *     SF_TEST_OP_RSQRT    x                        ->  rsqrt_nr(x), recip_nr(x)                          1 / 2
+ *     SF_TEST_OP_SVD3     A (3x3 row-major)        ->  U (9), S (3, descending), V (9):  A = U S V^T      9 / 21
+ *     SF_TEST_OP_KABSCH   record (32: n, sum s, sum t, sum s t^T row-major, rest ignored) -> T (4x4)      32 / 16
+ *     SF_TEST_OP_LDLT6    A (6x6), b (6)           ->  rc (0 | -1 as a double), x (6; zeros when rc = -1) 42 / 7
+ *     SF_TEST_OP_VEC6     v = (rx, ry, rz, t)      ->  T (4x4) = [Rz Ry Rx | t]                           6 / 16
+ *     SF_TEST_OP_JACOBI3  A (3x3 symmetric)        ->  eigenvalues (unsorted), V (9), sweeps that rotated 9 / 13
+ *     SF_TEST_OP_JACOBI6  A (6x6 symmetric)        ->  eigenvalues (unsorted), V (36), sweeps             36 / 43
+ *     SF_TEST_OP_ROBUST   kind, k, r               ->  w(r) of SF_ROBUST_<kind>                           3 / 1
+ *     SF_TEST_OP_EIGVEC   C (3x3 symmetric)        ->  the unit normal smallest_eigvec(C) of the map normals  9 / 3
+ *   Doubles of out beyond what the op writes come back as they went in.
+ * sf_test_wave_reduce: one workgroup of 256; lane l of it holds in[l * width .. + width]; out[l] = what
+ *   wave_reduce_<width> returned on lane l (width 32: the wave's total of component (l % 64) >> 1; 16: of component
+ *   ((l % 64) >> 2) & 15; 1: of the one value).
+ * sf_test_block_reduce: block_reduce_store<nrec> of one workgroup of 256 (lane l contributes in[l * nrec .. + nrec]) into
+ *   a device copy of out[32]: out[c < nrec] = the workgroup's total of component c, out[c >= nrec] as it went in.
+ * sf_test_reduce_partials: reduce_partials<nrec, nt> over part[nblocks][32] by one workgroup of nt threads -> out[32]
+ *   (out[c >= nrec] = 0).  Only the instantiations the library uses: nt = 256 with nrec 11 | 17 | 24 | 30, nt = 1024 with
+ *   nrec 17 | 30.
+ * SF_ERR_INVALID, nothing touched: an unknown op / width / nrec / (nrec, nt); a stride below what the op reads or writes or
+ *   above 64; cases outside [0, 2^20]; nblocks outside [0, 65536]; a NULL array that is needed (none for cases = 0 or
+ *   nblocks = 0). */
+#define SF_TEST_OP_RSQRT 0
+#define SF_TEST_OP_SVD3 1
+#define SF_TEST_OP_KABSCH 2
+#define SF_TEST_OP_LDLT6 3
+#define SF_TEST_OP_VEC6 4
+#define SF_TEST_OP_JACOBI3 5
+#define SF_TEST_OP_JACOBI6 6
+#define SF_TEST_OP_ROBUST 7
+#define SF_TEST_OP_EIGVEC 8
+int sf_test_linalg(sf_ctx *ctx, int op, const double *in, int in_stride, int64_t cases, double *out, int out_stride);
+int sf_test_wave_reduce(sf_ctx *ctx, int width /* 1 | 16 | 32 */, const double *in /* [256][width] */, double *out /* [256] */);
+int sf_test_block_reduce(sf_ctx *ctx, int nrec /* 17 | 30 */, const double *in /* [256][nrec] */, double *out /* [32], in and out */);
+int sf_test_reduce_partials(sf_ctx *ctx, int nrec /* 11 | 17 | 24 | 30 */, int nt /* 256 | 1024 */, const double *part /* [nblocks][32] */, int nblocks, double *out /* [32] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,10 @@ def load_library():
     lib.sf_icp_fetch_covariance_previous.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_radix_sort.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_test_scan_u32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_test_linalg.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int]
+    lib.sf_test_wave_reduce.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_test_block_reduce.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_test_reduce_partials.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -196,6 +200,45 @@ def hook_scan_u32(ctx, op, values, carry0=0, in_place=False):
     damage = C.c_int64(-1)
     _check(ctx.lib.sf_test_scan_u32(ctx.h, int(op), _p(values), len(values), int(carry0), int(bool(in_place)), _p(out), C.addressof(damage)))
     return out, damage.value
+
+
+# ops of sf_test_linalg: name -> (SF_TEST_OP_*, doubles read, doubles written per case)
+LINALG_OPS = {"rsqrt": (0, 1, 2), "svd3": (1, 9, 21), "kabsch": (2, 32, 16), "ldlt6": (3, 42, 7), "vec6": (4, 6, 16),
+              "jacobi3": (5, 9, 13), "jacobi6": (6, 36, 43), "robust": (7, 3, 1), "eigvec": (8, 9, 3)}
+
+
+def hook_linalg(ctx, op, cases):
+    """Test hook (sf_test_linalg): one production float64 routine per row of `cases` (rows of LINALG_OPS[op][1] doubles), one
+    case per GPU thread.  Returns an array of LINALG_OPS[op][2] doubles per case."""
+    code, n_in, n_out = LINALG_OPS[op]
+    cases = _f64(cases).reshape(-1, n_in)
+    out = np.zeros((len(cases), n_out))
+    _check(ctx.lib.sf_test_linalg(ctx.h, code, _p(cases), n_in, len(cases), _p(out), n_out))
+    return out
+
+
+def hook_wave_reduce(ctx, width, values):
+    """Test hook (sf_test_wave_reduce): values[256][width] -> what wave_reduce_<width> returned on each of the 256 lanes."""
+    values = _f64(values).reshape(256, int(width))
+    out = np.zeros(256)
+    _check(ctx.lib.sf_test_wave_reduce(ctx.h, int(width), _p(values), _p(out)))
+    return out
+
+
+def hook_block_reduce(ctx, nrec, values, fill=0.0):
+    """Test hook (sf_test_block_reduce): block_reduce_store<nrec> of values[256][nrec] into 32 doubles that start as `fill`."""
+    values = _f64(values).reshape(256, int(nrec))
+    out = np.full(32, fill, dtype=np.float64)
+    _check(ctx.lib.sf_test_block_reduce(ctx.h, int(nrec), _p(values), _p(out)))
+    return out
+
+
+def hook_reduce_partials(ctx, nrec, nt, part):
+    """Test hook (sf_test_reduce_partials): reduce_partials<nrec, nt> over part[nblocks][32] -> the 32 doubles of rec."""
+    part = _f64(part).reshape(-1, 32)
+    out = np.full(32, np.nan)
+    _check(ctx.lib.sf_test_reduce_partials(ctx.h, int(nrec), int(nt), _p(part), len(part), _p(out)))
+    return out
 
 
 def _pc2_layout(msg):

@@ -253,6 +253,8 @@ int compact_cloud(sf_cloud *c, const uint8_t *d_flags);
 int ensure_scratch(sf_ctx *ctx, size_t bytes);
 // dst (device) <- src (any host memory), stream-ordered on the context's stream; src may be freed on return
 int upload_staged(sf_ctx *ctx, void *dst, const void *src, size_t bytes);
+// sf_map.hip: the eigvec op of sf_test_linalg (sf_icp.hip) -- smallest_eigvec lives in sf_map.hip's normals namespace
+int test_map_eigvec(sf_ctx *ctx, const double *in, int in_stride, int64_t cases, double *out, int out_stride);
 uint64_t next_generation();
 // sf_map.hip: the index's points moved (build / patch): a new stamp, the neighbour table no longer describes them
 void map_points_moved(sf_map *m);

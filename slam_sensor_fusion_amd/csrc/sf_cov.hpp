@@ -138,17 +138,20 @@ __device__ __forceinline__ bool jacobi_sym_sweep(double (&A)[N * N], double (&V)
 }
 
 // A = V diag(A_kk) V^T on return (A symmetric on entry; its off-diagonal is rotated away).  Converges quadratically: 6 x 6
-// takes 5-7 sweeps, the cap is never the reason to stop.
+// takes 5-7 sweeps (8 with clustered eigenvalues, 4 for 3 x 3: tests/test_gpu_linalg_direct.py asserts <= 12), the cap is never
+// the reason to stop.  Returns the number of sweeps that rotated.
 template <int N>
-__device__ __forceinline__ void jacobi_sym(double (&A)[N * N], double (&V)[N * N])
+__device__ __forceinline__ int jacobi_sym(double (&A)[N * N], double (&V)[N * N])
 {
 #pragma unroll
     for (int i = 0; i < N * N; ++i) V[i] = (i / N == i % N) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 24; ++sweep)
+    int sweep = 0;
+    for (; sweep < 24; ++sweep)
         if (!jacobi_sym_sweep<N, 0, 1>(A, V)) break;
+    return sweep; // (24: the cap stopped it)
 }
 
-__device__ __forceinline__ double recip_nr(double x) // 1 / x for x > 0, finite (no divide expansion on the one working lane)
+__device__ __forceinline__ double recip_nr(double x) // 1 / x within 5 ulp for x in rsqrt_nr's domain (normal, positive, finite): no divide expansion on the one working lane
 {
     const double y = rsqrt_nr(x);
     return y * y;

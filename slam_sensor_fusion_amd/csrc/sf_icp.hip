@@ -84,7 +84,11 @@ __device__ __forceinline__ void mat4_mul(const double A[16], const double B[16],
     for (int i = 0; i < 16; ++i) C[i] = R[i];
 }
 
-// 1 / sqrt(x) for x > 0, finite: the hardware estimate and two Newton steps (full float64 accuracy to an ulp or two).
+// 1 / sqrt(x) for NORMAL x in [DBL_MIN, 1e300]: the hardware estimate and two Newton steps, within 2 ulp of the exact
+// value over that whole range (measured 2.0 ulp; recip_nr = its square: within 5 ulp, measured 4.0).  Outside the
+// domain -- 0, subnormals, inf, negative x, NaN -- the estimate is inf / 0 / NaN and the Newton steps make NaN of inf * 0:
+// every caller guards (svd3 by n2 > 1e-300, jacobi_pair / jacobi_sym_pair by their skip tests, k_cov_solve by its eigenvalue
+// floor and by W > 0).
 // The solve runs on ONE lane while the rest of its workgroup -- on the per-scan path the whole grid -- waits, so the
 // float64 divide / sqrt expansions (a few dozen dependent instructions each) are what an iteration's controller costs:
 // measured 6.2 us per controller step with divides and square roots, 3.2-4.0 us with this.
@@ -142,7 +146,14 @@ __device__ __forceinline__ void swap_cols_if_less(double (&s)[3], double (&u)[9]
 }
 
 // one-sided Jacobi SVD of a 3x3 (row-major), S descending — stands in for
-// Eigen::JacobiSVD<Matrix3f> at icp_point_to_point.cpp:137 (float64 here)
+// Eigen::JacobiSVD<Matrix3f> at icp_point_to_point.cpp:137 (float64 here).
+// Domain: |A| = 0 or 1e-60 <= |A| <= 1e60 (tests/test_gpu_linalg_direct.py::test_svd3_supported_scale_range).  jacobi_pair
+// works on SQUARED column norms: below |A| ~ 1e-67 its |ga| < 1e-150 guard ends the sweeps before the columns are orthogonal
+// to eps (from 1e-75 down nothing rotates: V = I, S = the column norms, and n2 > 1e-300 zeroes S below 1e-150); above
+// |A| ~ 1e77 the product al * be overflows, inf <= inf skips every rotation and the result is finite and WRONG.  H of a Kabsch
+// step is a sum of products of metres and never comes near either end.  Columns whose singular value is below 8 eps S0 are
+// completed, not normalised: rank 0 gives U = I, rank 1 a unit vector orthogonal to the first column and then the cross
+// product, rank 2 the cross product -- U is orthonormal with det +1 whenever the rank is below 3.
 __device__ __forceinline__ void svd3(const double (&A)[9], double (&U)[9], double (&S)[3], double (&V)[9])
 {
 #pragma unroll
@@ -3040,6 +3051,7 @@ __global__ __launch_bounds__(BLK) void k_icp_fused_rob(SfGrid g, SfWindow w, con
 }
 
 #include "sf_cov.hpp"
+#include "sf_icp_testhooks.hpp"
 
 } // namespace
 
@@ -5452,4 +5464,40 @@ extern "C" int sf_icp_profile_read_phases(sf_icp *icp, int kind, float *ms, int6
     SF_CHECK(cap >= (int64_t)v.size(), SF_ERR_INVALID, "buffer too small");
     std::memcpy(ms, v.data(), sizeof(float) * v.size());
     return SF_OK;
+}
+
+// ------------------------------------------------------------------ test hooks of the numerical core (sf_icp_testhooks.hpp)
+extern "C" int sf_test_linalg(sf_ctx *ctx, int op, const double *in, int in_stride, int64_t cases, double *out, int out_stride)
+{
+    SF_CHECK(ctx, SF_ERR_INVALID, "sf_test_linalg: ctx is NULL");
+    SF_CHECK(op >= 0 && op < TEST_OP_COUNT, SF_ERR_INVALID, "sf_test_linalg: unknown op %d", op);
+    SF_CHECK(cases >= 0 && cases <= TEST_MAX_CASES, SF_ERR_INVALID, "sf_test_linalg: cases %lld outside [0, 2^20]", (long long)cases);
+    SF_CHECK(in_stride >= TEST_OP_IN[op] && in_stride <= 64 && out_stride >= TEST_OP_OUT[op] && out_stride <= 64, SF_ERR_INVALID,
+             "sf_test_linalg: op %d reads %d and writes %d doubles per case (strides %d / %d, at most 64)", op, TEST_OP_IN[op], TEST_OP_OUT[op], in_stride, out_stride);
+    SF_CHECK((in && out) || cases == 0, SF_ERR_INVALID, "sf_test_linalg: in or out is NULL");
+    if (op == TEST_OP_EIGVEC) return sf::test_map_eigvec(ctx, in, in_stride, cases, out, out_stride);
+    return test_linalg_run(ctx, op, in, in_stride, cases, out, out_stride);
+}
+
+extern "C" int sf_test_wave_reduce(sf_ctx *ctx, int width, const double *in, double *out)
+{
+    SF_CHECK(ctx && in && out, SF_ERR_INVALID, "sf_test_wave_reduce: ctx, in or out is NULL");
+    SF_CHECK(width == 1 || width == 16 || width == 32, SF_ERR_INVALID, "sf_test_wave_reduce: width %d (1, 16 or 32)", width);
+    return test_wave_reduce_run(ctx, width, in, out);
+}
+
+extern "C" int sf_test_block_reduce(sf_ctx *ctx, int nrec, const double *in, double *out)
+{
+    SF_CHECK(ctx && in && out, SF_ERR_INVALID, "sf_test_block_reduce: ctx, in or out is NULL");
+    SF_CHECK(nrec == NREC_P2P || nrec == NREC_PLANE, SF_ERR_INVALID, "sf_test_block_reduce: nrec %d (%d or %d)", nrec, NREC_P2P, NREC_PLANE);
+    return test_block_reduce_run(ctx, nrec, in, out);
+}
+
+extern "C" int sf_test_reduce_partials(sf_ctx *ctx, int nrec, int nt, const double *part, int nblocks, double *out)
+{
+    SF_CHECK(ctx && out, SF_ERR_INVALID, "sf_test_reduce_partials: ctx or out is NULL");
+    SF_CHECK(test_reduce_partials_known(nrec, nt), SF_ERR_INVALID, "sf_test_reduce_partials: <%d, %d> is not an instantiation the library uses (11 | 17 | 24 | 30 by 256, 17 | 30 by 1024)", nrec, nt);
+    SF_CHECK(nblocks >= 0 && nblocks <= TEST_MAX_ROWS, SF_ERR_INVALID, "sf_test_reduce_partials: nblocks %d outside [0, 65536]", nblocks);
+    SF_CHECK(part || nblocks == 0, SF_ERR_INVALID, "sf_test_reduce_partials: part is NULL");
+    return test_reduce_partials_run(ctx, nrec, nt, part, nblocks, out);
 }

@@ -1071,6 +1071,10 @@ extern "C" int sf_map_knn(sf_map *m, const float *queries, int64_t n, int k, flo
 // 3 x k . k x 3 with k ~ 10-30: VALU work, not a dense contraction worth MFMA.
 namespace {
 
+// Unit eigenvector of the smallest eigenvalue of the symmetric C, oriented z > 0, then y > 0, then x > 0.  An axis-aligned C
+// (off-diagonals exactly 0) takes no rotation: the answer is the axis of the smallest diagonal entry, the FIRST one among
+// equals -- so the zero matrix (every neighbour on one spot) gives +x, while store_normal_cov gives +z below 3 neighbours
+// without coming here.  Pinned by tests/test_gpu_linalg_direct.py::test_smallest_eigvec_matches_eigh[zero].
 __device__ void smallest_eigvec(const double C[9], double nrm[3])
 {
     double a[9], v[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
@@ -1337,7 +1341,35 @@ __global__ void k_normals_to_host_order(SfGrid g, const float4 *__restrict__ nrm
     cnt_orig[i] = __float_as_int(v.w);
 }
 
+// test hook (sf_test_linalg, op eigvec): smallest_eigvec itself, one case per thread, workgroups of 64
+__global__ __launch_bounds__(64) void k_test_eigvec(const double *__restrict__ in, int in_stride, int64_t cases, double *__restrict__ out, int out_stride)
+{
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= cases) return;
+    double C[9], nv[3];
+    for (int k = 0; k < 9; ++k) C[k] = in[(size_t)i * in_stride + k];
+    smallest_eigvec(C, nv);
+    for (int k = 0; k < 3; ++k) out[(size_t)i * out_stride + k] = nv[k];
+}
+
 } // namespace
+
+int sf::test_map_eigvec(sf_ctx *ctx, const double *in, int in_stride, int64_t cases, double *out, int out_stride)
+{
+    if (cases == 0) return SF_OK;
+    SF_HIP(hipSetDevice(ctx->device));
+    const size_t n_in = (size_t)cases * in_stride, n_out = (size_t)cases * out_stride;
+    sf::DevBuf din, dout; // freed on every path
+    SF_TRY(din.reserve(sizeof(double) * n_in));
+    SF_TRY(dout.reserve(sizeof(double) * n_out));
+    SF_TRY(sf::upload_staged(ctx, din.p, in, sizeof(double) * n_in));
+    SF_TRY(sf::upload_staged(ctx, dout.p, out, sizeof(double) * n_out));
+    hipLaunchKernelGGL(k_test_eigvec, dim3((unsigned)sf::div_up(cases, 64)), dim3(64), 0, ctx->stream, din.as<double>(), in_stride, cases, dout.as<double>(), out_stride);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    return SF_OK;
+}
 
 namespace {
 // what the two estimates share: the buffers, the profiled span around launch(nrm4, cov6 or nullptr), the synchronise and the
