@@ -326,6 +326,14 @@ int sf_map_download_neighbour_table(sf_map *m, uint32_t *table, int64_t cap_entr
  * sf_map_download_index lists them; negative or out of range: no seed).  served[i] = 1: idx / d2 are sf_map_nn's answer, bit for
  * bit; served[i] = 0: undecided (idx = -1, d2 = +inf).  Needs a table and no window. */
 int sf_map_nn_seeded(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *served);
+/* Stage 0 of the look-up: behind the table lies one float per indexed point, its nearest gap g1 -- the distance to the nearest
+ * other point, rounded down (the table's cap when nothing is listed, 0 for a coincident twin).  A query within g1 / 2 of its
+ * cached neighbour is settled by that one value: the neighbour is still the exact nearest and g1 less the query's distance
+ * bounds the runner-up.  sf_map_download_nearest_gap: [n] float32 in sorted order (parity tests).  sf_map_nn_seeded_stages:
+ * sf_map_nn_seeded with stage[i] = 0 not served, 1 settled by the gap alone, 2 by the table, and lb2[i] the squared runner-up
+ * bound a served query leaves (0 where not served). */
+int sf_map_download_nearest_gap(sf_map *m, float *gap, int64_t cap_entries, int64_t *n);
+int sf_map_nn_seeded_stages(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *stage, float *lb2);
 
 /* ------------------------------------------------------------------ ICP */
 /* a13: ICPResult — icp_point_to_point.h:28-39 (+ float64 and diagnostics) */
@@ -519,6 +527,8 @@ int sf_icp_set_neighbour_research(sf_icp *icp, int from_launch);
  * looks its unserved queries up a second time and counts them twice.  SF_ERR_STATE when profiling is off or its counters are
  * full (1024 launches since sf_icp_profile_enable; enabling again resets them). */
 int sf_icp_neighbour_stats(sf_icp *icp, int64_t out[3]);
+/* the same three and, fourth, how many of the served queries the nearest gap alone settled (sf_map_download_nearest_gap) */
+int sf_icp_neighbour_gap_stats(sf_icp *icp, int64_t out[4]);
 /* Robust M-estimator kernel of SF_ICP_P2PLANE (REF_CPP and O3D_P2P ignore it, as Open3D's point-to-point estimator takes no
  * kernel).  With r = (y - p) . n the float64 point-to-plane residual of a pair (y the transformed source point, p / n the
  * neighbour and its normal) and the scale k > 0 in metres, every pair enters the normal equations with the weight w(r):

@@ -688,6 +688,26 @@ class Map:
         _check(self.lib.sf_map_nn_seeded(self.h, _p(q), C.c_int64(len(q)), _p(s), C.c_float(min(max_d2, 3.0e38)), _p(idx), _p(d2), _p(served)))
         return idx, d2, served.astype(bool)
 
+    def download_nearest_gap(self):
+        """sf_map_download_nearest_gap: the nearest gap of every indexed point, [n] float32 in sorted order."""
+        gap = np.zeros(max(self.neighbour_table_info()["entries"], 1), np.float32)
+        n = C.c_int64()
+        _check(self.lib.sf_map_download_nearest_gap(self.h, _p(gap), C.c_int64(len(gap)), C.byref(n)))
+        return gap[:n.value].copy()
+
+    def nn_seeded_stages(self, queries, seed_pos, max_d2=np.inf):
+        """sf_map_nn_seeded_stages -> (idx, d2, stage, lb2): nn_seeded with the stage that served each query (0 not served,
+        1 the nearest gap alone, 2 the table) and the squared runner-up bound it left."""
+        q = _f32(queries).reshape(-1, 3)
+        s = np.ascontiguousarray(seed_pos, dtype=np.int32).reshape(-1)
+        assert len(s) == len(q)
+        idx = np.empty(len(q), np.int32)
+        d2 = np.empty(len(q), np.float32)
+        stage = np.empty(len(q), np.uint8)
+        lb2 = np.empty(len(q), np.float32)
+        _check(self.lib.sf_map_nn_seeded_stages(self.h, _p(q), C.c_int64(len(q)), _p(s), C.c_float(min(max_d2, 3.0e38)), _p(idx), _p(d2), _p(stage), _p(lb2)))
+        return idx, d2, stage, lb2
+
     def profile_launches(self, on=True):
         """sf_map_profile_launches: device events around the kernel launches of nn / knn / estimate_normals*."""
         _check(self.lib.sf_map_profile_launches(self.h, C.c_int(int(bool(on)))))
@@ -907,6 +927,12 @@ class Icp:
         a = (C.c_int64 * 3)()
         _check(self.lib.sf_icp_neighbour_stats(self.h, a))
         return {"served": a[0], "not_served": a[1], "waves_searched": a[2]}
+
+    def neighbour_gap_stats(self):
+        """neighbour_stats and "by_gap": the served queries the nearest gap alone settled (sf_icp_neighbour_gap_stats)."""
+        a = (C.c_int64 * 4)()
+        _check(self.lib.sf_icp_neighbour_gap_stats(self.h, a))
+        return {"served": a[0], "not_served": a[1], "waves_searched": a[2], "by_gap": a[3]}
 
     def defer_stats(self):
         """Of the last batched alignment (sf_icp_defer_stats): queries that went to the dense pass, waves that hit the cap."""

@@ -508,7 +508,7 @@ constexpr int VERIFY_FROM_SEARCH = 4; // wide scans: from the fifth launch of an
 #define SF_NBR_FROM 2 // measured against 1: profiles/LADDER.md round 7
 #endif
 constexpr int NN_STATS_SHARDS = 256; // counters of one profiled launch
-constexpr int NN_STATS_PER = 4;      // per shard: queries that searched, waves that searched, queries the neighbour table served, queries it was tried for and did not serve
+constexpr int NN_STATS_PER = 5;      // per shard: queries that searched, waves that searched, queries the neighbour table served, queries it was tried for and did not serve, served queries the nearest gap alone settled
 
 struct LanePair {
     double sx, sy, sz; // the transformed scan point (float64)
@@ -662,13 +662,15 @@ __device__ __forceinline__ LanePair make_pair(const QueryIn &q, const sf::NNHit 
 // One lane's look into the neighbour table (sf_nn.hpp: nn_research_table) for a query whose certificate failed with a cached
 // neighbour at hand (seed.j >= 0).  Served: hit / tn are the pair the search would have found and the cache entry is written
 // as the search path writes it -- E from the table's runner-up bound; the winner's normal is fetched only when the winner is
-// not the cached point.  Not served: nothing is touched.
+// not the cached point (never for a query the nearest gap settled: its winner is the cached point).  Not served: nothing is
+// touched.  Returns the stage that served it (sf::NBR_BY_GAP / sf::NBR_BY_TABLE), 0 when not served.
 template <int MODE>
-__device__ __forceinline__ bool table_serve(const SfGrid &g, const QueryIn &q, float thr, float m_now, const sf::NNHit &seed, float4 *__restrict__ qcache, int64_t cache_n,
+__device__ __forceinline__ int table_serve(const SfGrid &g, const QueryIn &q, float thr, float m_now, const sf::NNHit &seed, float4 *__restrict__ qcache, int64_t cache_n,
                                             sf::NNHit &hit, float4 &tn)
 {
     sf::NNHit th;
-    if (!sf::nn_research_table(g, q.qx, q.qy, q.qz, thr, seed, th)) return false;
+    const int stage = sf::nn_research_table(g, q.qx, q.qy, q.qz, thr, seed, th);
+    if (stage == 0) return 0;
     const bool same = th.j == seed.j;
     hit = th;
     if (MODE == 2) tn = same ? make_float4(q.c2.x, q.c2.y, q.c2.z, 0.0f) : (th.j >= 0 ? g.nrm[th.j] : make_float4(0.f, 0.f, 0.f, 0.f));
@@ -676,7 +678,20 @@ __device__ __forceinline__ bool table_serve(const SfGrid &g, const QueryIn &q, f
     if (!same) qcache[q.o] = make_float4(th.px, th.py, th.pz, __int_as_float(th.j));
     if (MODE == 2) qcache[(size_t)cache_n + q.o] = make_float4(tn.x, tn.y, tn.z, en);
     else reinterpret_cast<float *>(qcache + (size_t)cache_n)[q.o] = en;
-    return true;
+    return stage;
+}
+
+// the look-up's profiling counters of one wave (every lane of the wave calls it): tried = the lane looked its cached neighbour up,
+// stage = what table_serve returned for it
+__device__ __forceinline__ void table_count(uint32_t *__restrict__ stats, bool tried, int stage)
+{
+    const unsigned long long tm = __ballot(tried), sm = __ballot(stage != 0), gm = __ballot(stage == sf::NBR_BY_GAP);
+    if ((threadIdx.x & 63) == 0 && tm) {
+        uint32_t *sh = stats + NN_STATS_PER * ((blockIdx.x + blockIdx.y * gridDim.x) & (NN_STATS_SHARDS - 1)); // sharded: one address would serialise 100 k waves
+        atomicAdd(&sh[2], (uint32_t)__popcll(sm));
+        atomicAdd(&sh[3], (uint32_t)__popcll(tm & ~sm));
+        atomicAdd(&sh[4], (uint32_t)__popcll(gm));
+    }
 }
 
 template <int MODE, bool WINDOW, bool SHARD>
@@ -705,19 +720,12 @@ __device__ __forceinline__ LanePair nn_pair(const SfGrid &g, const SfWindow &w, 
     if constexpr (!WINDOW && !SHARD) {
         if (try_table && g.nbr != nullptr && S->n_research >= g.nbr_from) {
             const bool tried = need && seed.j >= 0;
-            bool served = false;
+            int served = 0;
             if (tried) {
                 served = table_serve<MODE>(g, q, thr, m_now, seed, qcache, cache_n, hit, tn);
-                need = !served;
+                need = served == 0;
             }
-            if (stats) { // profiling only
-                const unsigned long long tm = __ballot(tried), sm = __ballot(served);
-                if ((threadIdx.x & 63) == 0 && tm) {
-                    uint32_t *sh = stats + NN_STATS_PER * ((blockIdx.x + blockIdx.y * gridDim.x) & (NN_STATS_SHARDS - 1));
-                    atomicAdd(&sh[2], (uint32_t)__popcll(sm));
-                    atomicAdd(&sh[3], (uint32_t)__popcll(tm & ~sm));
-                }
-            }
+            if (stats) table_count(stats, tried, served); // profiling only
         }
     }
     // every lane takes part in the search (lanes without a query still execute other lanes' tasks)
@@ -2022,19 +2030,12 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_df(SfGrid g, SfWin
             // the neighbour table first: only what it cannot serve is listed (or searched in place)
             if (g.nbr != nullptr && S->n_research >= g.nbr_from) {
                 const bool tried = need[u] && seed.j >= 0;
-                bool served = false;
+                int served = 0;
                 if (tried) {
                     served = table_serve<MODE>(g, q, thr, m_now, seed, qcache, cache_n, hit, tn);
-                    need[u] = !served;
+                    need[u] = served == 0;
                 }
-                if (stats) { // profiling only
-                    const unsigned long long tm = __ballot(tried), sm = __ballot(served);
-                    if (lane == 0 && tm) {
-                        uint32_t *sh = stats + NN_STATS_PER * ((blockIdx.x + blockIdx.y * gridDim.x) & (NN_STATS_SHARDS - 1));
-                        atomicAdd(&sh[2], (uint32_t)__popcll(sm));
-                        atomicAdd(&sh[3], (uint32_t)__popcll(tm & ~sm));
-                    }
-                }
+                if (stats) table_count(stats, tried, served); // profiling only
             }
             P[u] = make_pair(q, hit, tn); // (a failing query: no pair, a zero contribution)
         }
@@ -4559,21 +4560,35 @@ extern "C" int sf_icp_set_neighbour_research(sf_icp *icp, int from_launch)
 
 // {queries the table served, queries it was tried for and did not serve, waves that still searched} over the launches of
 // the last alignment enqueued with sf_icp_align_batch_async; counted in profiled runs only (sf_icp_profile_enable)
-extern "C" int sf_icp_neighbour_stats(sf_icp *icp, int64_t out[3])
+namespace {
+int neighbour_stats(sf_icp *icp, int64_t out[4])
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
     SF_CHECK(icp->profiling && icp->nn_stats.p, SF_ERR_STATE, "the neighbour statistics are counted in profiled runs (sf_icp_profile_enable)");
     SF_CHECK(icp->nn_stats_used < sf_icp::NN_STATS_CAP, SF_ERR_STATE, "the profiling counters are full (%lld launches since sf_icp_profile_enable): enable profiling again to reset them", (long long)sf_icp::NN_STATS_CAP);
     SF_HIP(hipStreamSynchronize(icp->ctx->stream));
-    out[0] = out[1] = out[2] = 0;
+    out[0] = out[1] = out[2] = out[3] = 0;
     const int64_t first = icp->nbr_stats_first, used = icp->nn_stats_used;
     if (used <= first) return SF_OK;
     const size_t per = (size_t)NN_STATS_PER * NN_STATS_SHARDS;
     std::vector<uint32_t> st(per * (size_t)(used - first), 0u);
     SF_HIP(hipMemcpy(st.data(), icp->nn_stats.as<uint32_t>() + per * (size_t)first, sizeof(uint32_t) * st.size(), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < st.size(); i += NN_STATS_PER) { out[0] += st[i + 2]; out[1] += st[i + 3]; out[2] += st[i + 1]; }
+    for (size_t i = 0; i < st.size(); i += NN_STATS_PER) { out[0] += st[i + 2]; out[1] += st[i + 3]; out[2] += st[i + 1]; out[3] += st[i + 4]; }
     return SF_OK;
 }
+} // namespace
+
+extern "C" int sf_icp_neighbour_stats(sf_icp *icp, int64_t out[3])
+{
+    int64_t all[4];
+    SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
+    SF_TRY(neighbour_stats(icp, all));
+    out[0] = all[0]; out[1] = all[1]; out[2] = all[2];
+    return SF_OK;
+}
+
+// sf_icp_neighbour_stats and, fourth, the served queries that the nearest gap alone settled (no table entry read)
+extern "C" int sf_icp_neighbour_gap_stats(sf_icp *icp, int64_t out[4]) { return neighbour_stats(icp, out); }
 
 extern "C" int sf_icp_defer_stats(sf_icp *icp, int64_t out[2])
 {

@@ -830,8 +830,10 @@ extern "C" int sf_map_nn(sf_map *m, const float *queries, int64_t n, float max_d
 // (less the rounding of the grid coordinates) away.  Seven listed: r = sqrt(d2 of the 7th) * 0.9999; fewer: r = cap.
 // One lane per point; the seven keys stay sorted in registers by an unrolled insertion.  The entry depends on the index
 // alone: the key order is total, whatever order the cells are walked in.
+// Behind the n entries, in the same allocation, one float per point (sf::nbr_gap): the nearest gap g1 = sqrt(d2 of the first
+// listed) * 0.9999, the cap when nothing is listed, 0 for a point with a coincident twin -- stage 0 of the look-up.
 namespace {
-__global__ __launch_bounds__(256) void k_neighbour_table(SfGrid g, uint4 *__restrict__ tab)
+__global__ __launch_bounds__(256) void k_neighbour_table(SfGrid g, uint4 *__restrict__ tab, float *__restrict__ gap)
 {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= g.n) return;
@@ -862,17 +864,18 @@ __global__ __launch_bounds__(256) void k_neighbour_table(SfGrid g, uint4 *__rest
     // (an absent slot's key is all ones: its low half is the "none" id)
     tab[2 * (size_t)j] = make_uint4((uint32_t)key[0], (uint32_t)key[1], (uint32_t)key[2], (uint32_t)key[3]);
     tab[2 * (size_t)j + 1] = make_uint4((uint32_t)key[4], (uint32_t)key[5], (uint32_t)key[6], __float_as_uint(r));
+    gap[j] = key[0] != ~0ull ? sqrtf(__uint_as_float((uint32_t)(key[0] >> 32))) * 0.9999f : cap;
 }
 
 // the re-search of sf_nn.hpp on its own, one query per lane: sf_map_nn_seeded
 __global__ __launch_bounds__(256) void k_map_nn_seeded(SfGrid g, const float *__restrict__ q, int64_t n, const int32_t *__restrict__ seed_pos, float thr, int32_t *__restrict__ idx,
-                                                       float *__restrict__ d2, uint8_t *__restrict__ served)
+                                                       float *__restrict__ d2, uint8_t *__restrict__ stage, float *__restrict__ lb2)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
     const int32_t s = seed_pos[i];
-    bool ok = false;
+    int ok = 0; // the stage that served it (sf::NBR_BY_GAP / sf::NBR_BY_TABLE)
     sf::NNHit hit{0.0f, -1, 0.0f, 0.0f, 0.0f, 0.0f};
     if (s >= 0 && (int64_t)s < g.n && isfinite(qx) && isfinite(qy) && isfinite(qz)) {
         const float4 p = g.pts[s];
@@ -882,7 +885,8 @@ __global__ __launch_bounds__(256) void k_map_nn_seeded(SfGrid g, const float *__
     const bool has = ok && hit.j >= 0;
     idx[i] = has ? (int32_t)__float_as_uint(g.pts[hit.j].w) : -1;
     d2[i] = has ? hit.d2 : INFINITY;
-    served[i] = ok ? 1 : 0;
+    stage[i] = (uint8_t)ok;
+    if (lb2) lb2[i] = ok ? hit.lb2 : 0.0f; // (sf_map_nn_seeded_stages)
 }
 } // namespace
 
@@ -899,7 +903,7 @@ int map_neighbour_table_ensure(sf_map *m)
     if (map_neighbour_table_present(m)) return SF_OK;
     sf_ctx *ctx = m->ctx;
     SF_HIP(hipSetDevice(ctx->device));
-    SF_TRY(m->nbr.reserve(sizeof(uint4) * 2 * (size_t)std::max<int64_t>(m->grid.n, 1)));
+    SF_TRY(m->nbr.reserve((sizeof(uint4) * 2 + sizeof(float)) * (size_t)std::max<int64_t>(m->grid.n, 1))); // the entries, then the nearest gaps
     m->nbr_timed = false;
     if (m->profile) {
         bool ok = true;
@@ -909,7 +913,7 @@ int map_neighbour_table_ensure(sf_map *m)
     }
     SfGrid g = m->grid;
     g.nbr = nullptr;
-    if (g.n > 0) hipLaunchKernelGGL(k_neighbour_table, dim3(nblk(g.n)), dim3(256), 0, ctx->stream, g, m->nbr.as<uint4>());
+    if (g.n > 0) hipLaunchKernelGGL(k_neighbour_table, dim3(nblk(g.n)), dim3(256), 0, ctx->stream, g, m->nbr.as<uint4>(), reinterpret_cast<float *>(m->nbr.as<uint4>() + 2 * (size_t)g.n));
     SF_HIP(hipGetLastError());
     if (m->nbr_timed) m->nbr_timed = hipEventRecord(m->nbr_ev[1], ctx->stream) == hipSuccess;
     m->nbr_build_ms = -1.0f;
@@ -967,35 +971,70 @@ extern "C" int sf_map_download_neighbour_table(sf_map *m, uint32_t *table, int64
     return SF_OK;
 }
 
+// the nearest gaps behind the table (stage 0 of the look-up), for the parity tests: [n] float32 in sorted order
+extern "C" int sf_map_download_nearest_gap(sf_map *m, float *gap, int64_t cap_entries, int64_t *n)
+{
+    SF_CHECK(m && m->built && n, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(sf::map_neighbour_table_present(m), SF_ERR_STATE, "no neighbour table (sf_map_build_neighbour_table)");
+    *n = m->grid.n;
+    if (!gap || m->grid.n == 0) return SF_OK;
+    SF_CHECK(cap_entries >= m->grid.n, SF_ERR_INVALID, "buffer too small");
+    SF_HIP(hipSetDevice(m->ctx->device));
+    SF_HIP(hipMemcpyAsync(gap, m->nbr.as<uint4>() + 2 * (size_t)m->grid.n, sizeof(float) * (size_t)m->grid.n, hipMemcpyDeviceToHost, m->ctx->stream));
+    SF_HIP(hipStreamSynchronize(m->ctx->stream));
+    return SF_OK;
+}
+
 // Test entry of the table re-search: query i starts from the indexed point at SORTED position seed_pos[i] (-1, or anything
 // outside the index: no seed).  served[i] = 1: idx / d2 are sf_map_nn's answer for the query, bit for bit (original ids,
 // -1 / +inf when nothing lies within max_d2); served[i] = 0: the table could not decide it (idx = -1, d2 = +inf).
-extern "C" int sf_map_nn_seeded(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *served)
+namespace {
+// -> stage[i]: 0 not served, sf::NBR_BY_GAP / sf::NBR_BY_TABLE; lb2 (optional): the squared runner-up bound
+int map_nn_seeded(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *stage, float *lb2)
 {
     SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
-    SF_CHECK(n >= 0 && (n == 0 || (queries && seed_pos && idx && d2 && served)), SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(n >= 0 && (n == 0 || (queries && seed_pos && idx && d2 && stage)), SF_ERR_INVALID, "bad arguments");
     SF_CHECK(sf::map_neighbour_table_present(m), SF_ERR_STATE, "no neighbour table (sf_map_build_neighbour_table)");
     SF_CHECK(m->window.kind == 0, SF_ERR_STATE, "the neighbour table knows no window");
     if (n == 0) return SF_OK;
     sf_ctx *ctx = m->ctx;
     SF_HIP(hipSetDevice(ctx->device));
-    sf::DevBuf dq, ds, di, dd, dv;
+    sf::DevBuf dq, ds, di, dd, dv, dl;
     SF_TRY(dq.reserve(sizeof(float) * 3 * (size_t)n));
     SF_TRY(ds.reserve(sizeof(int32_t) * (size_t)n));
     SF_TRY(di.reserve(sizeof(int32_t) * (size_t)n));
     SF_TRY(dd.reserve(sizeof(float) * (size_t)n));
     SF_TRY(dv.reserve((size_t)n));
+    if (lb2) SF_TRY(dl.reserve(sizeof(float) * (size_t)n));
     SF_HIP(hipMemcpyAsync(dq.p, queries, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     SF_HIP(hipMemcpyAsync(ds.p, seed_pos, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     SfGrid g = m->grid;
     g.nbr = m->nbr.as<uint4>();
-    hipLaunchKernelGGL(k_map_nn_seeded, dim3(nblk(n)), dim3(256), 0, ctx->stream, g, dq.as<float>(), n, ds.as<int32_t>(), max_d2, di.as<int32_t>(), dd.as<float>(), dv.as<uint8_t>());
+    hipLaunchKernelGGL(k_map_nn_seeded, dim3(nblk(n)), dim3(256), 0, ctx->stream, g, dq.as<float>(), n, ds.as<int32_t>(), max_d2, di.as<int32_t>(), dd.as<float>(), dv.as<uint8_t>(),
+                       lb2 ? dl.as<float>() : nullptr);
     SF_HIP(hipGetLastError());
     SF_HIP(hipMemcpyAsync(idx, di.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipMemcpyAsync(d2, dd.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SF_HIP(hipMemcpyAsync(served, dv.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipMemcpyAsync(stage, dv.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (lb2) SF_HIP(hipMemcpyAsync(lb2, dl.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SF_HIP(hipStreamSynchronize(ctx->stream));
     return SF_OK;
+}
+} // namespace
+
+extern "C" int sf_map_nn_seeded(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *served)
+{
+    SF_TRY(map_nn_seeded(m, queries, n, seed_pos, max_d2, idx, d2, served, nullptr));
+    for (int64_t i = 0; i < n; ++i) served[i] = served[i] != 0; // the stage, collapsed to the flag
+    return SF_OK;
+}
+
+// sf_map_nn_seeded with the stage that served each query (0: not served, 1: the nearest gap alone, 2: the table) and the
+// runner-up bound lb2 it left (squared; 0 where not served)
+extern "C" int sf_map_nn_seeded_stages(sf_map *m, const float *queries, int64_t n, const int32_t *seed_pos, float max_d2, int32_t *idx, float *d2, uint8_t *stage, float *lb2)
+{
+    SF_CHECK(n == 0 || lb2, SF_ERR_INVALID, "bad arguments");
+    return map_nn_seeded(m, queries, n, seed_pos, max_d2, idx, d2, stage, lb2);
 }
 
 // ------------------------------------------------------------------ exact k-NN (sf_knn.hpp)

@@ -884,8 +884,23 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
 // (everything else is at least that far from p, by the key order of the list); it serves the same queries -- r4 <= r and the
 // winner is proven among the five -- with a bound from r4.
 // Pure: no LDS, no wave cooperation; the lane either takes the result or searches as before with its seed unchanged.
+//
+// Stage 0, the nearest gap: behind the n entries lies one float per point, g1 = |x1 - p| * 0.9999 for the first listed point
+// x1 (the nearest other point of p; the cap when nothing is listed, 0 for a coincident twin).  A lane with
+// (|q - p| + |q - p|) * 1.0001 + 2e-6 < g1 is settled from that one 4-byte gather: it is the served rule above with best = p
+// and g1 in place of r.  Every other map point x has |x - p| >= g1 (the list is in key order), so
+// |x - q| >= |x - p| - |q - p| >= g1 - |q - p| > |q - p|: p is the exact nearest, ties excluded, and g1 - |q - p| bounds the
+// runner-up.  It serves nothing the table would not: the listed points are farther from q than p by the same inequality (the
+// margins cover the roundings as above), so the table's winner is p too, and g1 <= r4 <= r under the same roundings -- sqrtf is
+// monotone over the key order of the list, and a listed distance is under the cap -- so the table's rule holds with either
+// radius.  The result is the table's for the winner p (index, d2, the "nothing within the acceptance radius" form); only the
+// bound is the looser g1 - |q - p|.  A lane that fails it takes the look-up below unchanged.
 constexpr uint32_t NBR_NONE = 0xffffffffu;
 constexpr int NBR_K = 7;
+constexpr int NBR_BY_GAP = 1, NBR_BY_TABLE = 2; // what nn_research_table returns for a served query (0: not served)
+
+// the nearest-gap array of a table of g.n entries: behind the entries, in the same allocation (SfGrid does not grow)
+__device__ __forceinline__ const float *nbr_gap(const SfGrid &g) { return reinterpret_cast<const float *>(g.nbr + 2 * (size_t)g.n); }
 
 __device__ __forceinline__ void nbr_fold(const float4 &p, uint32_t id, float qx, float qy, float qz, unsigned long long &best, float4 &bp, float &second)
 {
@@ -899,15 +914,39 @@ __device__ __forceinline__ void nbr_fold(const float4 &p, uint32_t id, float qx,
     if (take) { best = key; bp = p; }
 }
 
-// seed: the cached neighbour (seed.j >= 0) with its current squared distance, as reuse_certificate leaves it
-__device__ __forceinline__ bool nn_research_table(const SfGrid &g, float qx, float qy, float qz, float thr, const NNHit &seed, NNHit &out)
+// what a served look-up returns: best = (d2b, j, bp) is the winner, lb bounds every other point from below
+__device__ __forceinline__ void nbr_result(float d2b, int j, const float4 &bp, float lb, float thr, NNHit &out)
 {
+    // nothing under the threshold: the entry will say "no neighbour", and for such an entry the bound speaks of EVERY map
+    // point (reuse_certificate: "still nothing within the acceptance radius") -- the best candidate itself comes under it, as
+    // the would-be best of a search that found nothing enters its runner-up bound
+    if (!(d2b < thr)) lb = fminf(lb, sqrtf(d2b) * 0.9999f);
+    const float l2 = lb * lb;
+    out.lb2 = l2 > 0.0f ? __uint_as_float(__float_as_uint(l2) - 1u) : 0.0f; // one step below the rounded square
+    if (d2b < thr) {
+        out.d2 = d2b; out.j = j; out.px = bp.x; out.py = bp.y; out.pz = bp.z;
+    } else { // nothing within the acceptance radius: what a search that found nothing returns
+        out.d2 = search_start(thr); out.j = -1; out.px = out.py = out.pz = 0.0f;
+    }
+}
+
+// seed: the cached neighbour (seed.j >= 0) with its current squared distance, as reuse_certificate leaves it
+// -> 0: not served; NBR_BY_GAP / NBR_BY_TABLE: served, by which stage
+__device__ __forceinline__ int nn_research_table(const SfGrid &g, float qx, float qy, float qz, float thr, const NNHit &seed, NNHit &out)
+{
+    const float dp = sqrtf(seed.d2);
+    { // stage 0 (g1 is dead before the entry is loaded)
+        const float g1 = nbr_gap(g)[seed.j];
+        if ((dp + dp) * 1.0001f + 2.0e-6f < g1) {
+            nbr_result(seed.d2, seed.j, make_float4(seed.px, seed.py, seed.pz, 0.0f), fmaxf(g1 - dp * 1.0001f - 1.0e-6f, 0.0f), thr, out);
+            return NBR_BY_GAP;
+        }
+    }
     const uint4 e0 = g.nbr[2 * (size_t)seed.j], e1 = g.nbr[2 * (size_t)seed.j + 1];
     const float r = __uint_as_float(e1.w);
     unsigned long long best = hit_key(seed.d2, seed.j);
     float4 bp = make_float4(seed.px, seed.py, seed.pz, 0.0f);
     float second = 3.0e38f;
-    const float dp = sqrtf(seed.d2);
     float rr = r;
     bool rest = e1.x != NBR_NONE; // (key order: no fifth, no sixth or seventh)
     { // two batches (4 + 3): at most four candidates' coordinates live at a time
@@ -932,20 +971,9 @@ __device__ __forceinline__ bool nn_research_table(const SfGrid &g, float qx, flo
         nbr_fold(p6, e1.z, qx, qy, qz, best, bp, second);
     }
     const float d2b = __uint_as_float((uint32_t)(best >> 32));
-    if (!((dp + sqrtf(d2b)) * 1.0001f + 2.0e-6f < rr)) return false;
-    float lb = fmaxf(fminf(sqrtf(second) * 0.9999f, rr - dp * 1.0001f - 1.0e-6f), 0.0f);
-    // nothing under the threshold: the entry will say "no neighbour", and for such an entry the bound speaks of EVERY map
-    // point (reuse_certificate: "still nothing within the acceptance radius") -- the best candidate itself comes under it, as
-    // the would-be best of a search that found nothing enters its runner-up bound
-    if (!(d2b < thr)) lb = fminf(lb, sqrtf(d2b) * 0.9999f);
-    const float l2 = lb * lb;
-    out.lb2 = l2 > 0.0f ? __uint_as_float(__float_as_uint(l2) - 1u) : 0.0f; // one step below the rounded square
-    if (d2b < thr) {
-        out.d2 = d2b; out.j = (int)(uint32_t)best; out.px = bp.x; out.py = bp.y; out.pz = bp.z;
-    } else { // nothing within the acceptance radius: what a search that found nothing returns
-        out.d2 = search_start(thr); out.j = -1; out.px = out.py = out.pz = 0.0f;
-    }
-    return true;
+    if (!((dp + sqrtf(d2b)) * 1.0001f + 2.0e-6f < rr)) return 0;
+    nbr_result(d2b, (int)(uint32_t)best, bp, fmaxf(fminf(sqrtf(second) * 0.9999f, rr - dp * 1.0001f - 1.0e-6f), 0.0f), thr, out);
+    return NBR_BY_TABLE;
 }
 
 } // namespace sf
