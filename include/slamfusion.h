@@ -517,8 +517,21 @@ int sf_icp_freeze_stats(sf_icp *icp, int64_t out[5]);
 int sf_icp_set_defer_search(sf_icp *icp, int on);
 /* of the last batched alignment: {queries that went to the dense pass, waves with more failing queries than the cap, which
  * searched in place} -- zeros when the schedule did not run or the switch is off.  Whether it ran is recorded when the
- * alignment is enqueued: a later sf_icp_fetch_results that re-learns the freeze schedule does not change the answer. */
+ * alignment is enqueued: a later sf_icp_fetch_results that re-learns the freeze schedule does not change the answer.
+ * An alignment that consults a neighbour table has several deferring launches (sf_icp_lookup_launch_stats): the two
+ * numbers are then the sums over all of them. */
 int sf_icp_defer_stats(sf_icp *icp, int64_t out[2]);
+/* Look-up launches.  An alignment on the frozen-pairs schedule with the deferred search on that consults a neighbour table
+ * (unsharded, whole map) runs every launch from the first that consults the table (sf_icp_set_neighbour_research) up to the
+ * launch before from_launch (sf_icp_set_freeze_params) in the deferring form: two queries per lane, table and nearest gap
+ * first, the few queries they leave to the dense pass.  Same pairs as the searching launches they replace; their terms enter
+ * the float64 sums at another place.  Without a table the schedule is unchanged.  While from_launch is left to the library the
+ * first look-up launch of the NEXT alignment is learnt like from_launch itself (sf_icp_fetch_results): a look-up launch in which
+ * more than one wave in eight exceeded the cap moves it behind that launch; sf_icp_set_freeze_params and
+ * sf_icp_set_neighbour_research start over.  Of the last batched alignment, as recorded
+ * when it was enqueued: {launches that ran in look-up form, queries they deferred, their capped waves, the index of the first
+ * of them (-1: none)}. */
+int sf_icp_lookup_launch_stats(sf_icp *icp, int64_t out[4]);
 /* The first launch index (>= 1; default 2, the third launch) of an alignment from which lanes consult the map's neighbour
  * table (sf_map_set_neighbour_table); negative: never.  Earlier launches move the pose too far for the table to serve many. */
 int sf_icp_set_neighbour_research(sf_icp *icp, int from_launch);

@@ -940,6 +940,13 @@ class Icp:
         _check(self.lib.sf_icp_defer_stats(self.h, a))
         return {"deferred_queries": a[0], "capped_waves": a[1]}
 
+    def lookup_launch_stats(self):
+        """Of the last batched alignment (sf_icp_lookup_launch_stats): how many launches ran in look-up form and the index of the
+        first (-1: none), the queries they deferred and their capped waves."""
+        a = (C.c_int64 * 4)()
+        _check(self.lib.sf_icp_lookup_launch_stats(self.h, a))
+        return {"launches": a[0], "deferred_queries": a[1], "capped_waves": a[2], "first": a[3]}
+
     def set_query_order(self, order="auto"):
         """'auto' | 'as_given' | 'cell' (SF_ORDER_*): the order a scan's points are walked in."""
         _check(self.lib.sf_icp_set_query_order(self.h, C.c_int({"auto": 0, "as_given": 1, "cell": 2}[order])))

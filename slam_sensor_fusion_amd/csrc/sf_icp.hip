@@ -500,7 +500,8 @@ __global__ void k_state_init(IcpState *__restrict__ st, const double *__restrict
 #endif
 constexpr int64_t WIDE_SCAN_POINTS = 131072;
 constexpr int64_t WIDE_AUTO_POINTS = 65536; // see sf_icp::wide_auto
-constexpr int VERIFY_FROM_SEARCH = 4; // wide scans: from the fifth launch of an alignment on a wave first tries to verify all its queries at once
+constexpr int VERIFY_FROM_SEARCH = 4; // wide scans WITHOUT a neighbour table: from the fifth launch of an alignment on a wave first tries to verify all its queries at once
+                                      // (with a table the look-up launches start earlier, at the first launch that consults it: lookup_form / defer_first)
 #ifndef NN_RED_WAVES
 #define NN_RED_WAVES 4
 #endif
@@ -1967,7 +1968,7 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_fz_few(SfGrid g, S
     }
 }
 
-// ------------------------------------------------------------------ deferred search (the last verifying launch before the freeze)
+// ------------------------------------------------------------------ deferred search (the verifying / look-up launches before the freeze)
 // In the launch before the first chance to freeze ~0.4 % of the queries still fail their certificate, but a wave that holds
 // ONE of them drops what it loaded and walks the search's chain of dependent round trips with one or two lanes busy: 42 % of
 // the waves.  Here such a wave lists its failing queries instead (up to DF_WCAP; a segment of its own per wave, filled in
@@ -1976,27 +1977,38 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_fz_few(SfGrid g, S
 // and writes their records to FZ_FEW rows of their own per scan, which the reduce adds after the ordinary rows.  Same pairs,
 // another place in the sum -- frozen-pairs schedule only, which sums in an order of its own anyway.  A wave with more than
 // DF_WCAP failing queries searches in place as k_nn_red does (count 255: "capped").
+//
+// Which launches run this way (defer_first): without a neighbour table the one before the first chance to freeze, as described.
+// With a table every launch from the first that consults it (launch indices 2, 3 and 4 by default) -- the look-up launches: the
+// certificate fails for most queries of launch index 2 and for 8 % of index 3, but the nearest gap and the table settle all but
+// 0.2 % / none of them, so the one-query-per-lane searching kernel these launches used to run paid twice the waves (butterflies,
+// barrier, slab row), a sparse look-up chain per wave and an in-place search for the odd lane the table left (round 9: 499 -> 451
+// and 243 -> 218 us).  A failing query here is one the table did not serve either.  The deferral buffers are the lane's own and are
+// reused launch after launch: on one stream k_nn_red_df writes counts and lists, k_nn_deferred reads them and writes df.part, the
+// launch's reduce reads df.part -- all before the next launch's k_nn_red_df.
 
 #ifndef SF_DF_WCAP
 #define SF_DF_WCAP 8
 #endif
 constexpr int DF_WCAP = SF_DF_WCAP; // measured: 4, 8 and 16 (profiles/LADDER.md round 6)
 constexpr int DF_CAPPED = 255;
+constexpr int DF_STAT_LAUNCHES = 32; // launch indices with a capped-wave count of their own (later ones share the last)
 static_assert((BLK / 64) * DF_WCAP <= FZ_CAP && DF_WCAP < DF_CAPPED, "a row defers fewer queries than it could list as active");
 struct DeferBufs {
     uint8_t *cnt;   // [scan][row][wave]: queries the wave deferred, DF_CAPPED: it searched in place
     uint16_t *ids;  // [scan][row][wave][DF_WCAP]: their places in the row (u * BLK + thread)
     double *part;   // [scan][FZ_FEW][REC_STRIDE]: the records of the deferred queries
-    uint32_t *stat; // {deferred queries, capped waves} of the alignment
+    uint32_t *stat; // {deferred queries, capped waves} of the alignment, then the capped waves of launch index 0 .. DF_STAT_LAUNCHES - 1 (freeze_learn_schedule)
 };
 
-// k_nn_red<2, false, false, Q> from VERIFY_FROM_SEARCH on, with the deferral above.  The count and the list are written BEFORE
+// k_nn_red<2, false, false, Q> from launch index attempt_from on (the first deferring launch of the schedule: an argument, so that
+// the look-up launches of a table alignment attempt too), with the deferral above.  The count and the list are written BEFORE
 // the branch that searches: with anything of the bookkeeping live across the search the kernel took 121 VGPRs (4 waves per
 // SIMD) instead of the 92 (5) of the kernel it replaces.
 template <int Q>
 __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_df(SfGrid g, SfWindow w, const float *__restrict__ X0x, const float *__restrict__ X0y, const float *__restrict__ X0z,
                                                                  int n, const IcpState *__restrict__ st, float thr, double *__restrict__ partials, int nblocks,
-                                                                 float4 *__restrict__ qcache, int64_t cache_n, uint32_t *__restrict__ stats, DeferBufs df)
+                                                                 float4 *__restrict__ qcache, int64_t cache_n, uint32_t *__restrict__ stats, DeferBufs df, int attempt_from)
 {
     constexpr int MODE = 2;
     constexpr int NREC = NREC_PLANE;
@@ -2015,7 +2027,7 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_red_df(SfGrid g, SfWin
     bool need[Q];
 #pragma unroll
     for (int u = 0; u < Q; ++u) need[u] = false;
-    const bool attempted = qcache != nullptr && S->cache_live != 0 && S->n_research >= VERIFY_FROM_SEARCH;
+    const bool attempted = qcache != nullptr && S->cache_live != 0 && S->n_research >= attempt_from;
     bool fast = false;   // the wave goes on with the pairs of the all-at-once attempt
     uint32_t listed = 0; // what the wave leaves in df.cnt
     if (attempted) {
@@ -2169,7 +2181,10 @@ __global__ __launch_bounds__(BLK, 2) void k_nn_deferred(SfGrid g, SfWindow w, co
     __syncthreads();
     if (threadIdx.x == 0) { // (integers: order independent)
         if (n_listed) atomicAdd(&df.stat[0], n_listed);
-        if (capped) atomicAdd(&df.stat[1], capped);
+        if (capped) {
+            atomicAdd(&df.stat[1], capped);
+            atomicAdd(&df.stat[2 + min(max(S->n_research, 0), DF_STAT_LAUNCHES - 1)], capped); // (n_research: this launch's index)
+        }
     }
 }
 
@@ -2451,7 +2466,7 @@ __global__ __launch_bounds__(RBLK) void k_reduce_solve_fz(IcpState *__restrict__
 __global__ void k_fz_init(FreezeState *__restrict__ fz, int batch, uint32_t *__restrict__ df_stat)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b == 0) df_stat[0] = df_stat[1] = 0u;
+    if (b < 2 + DF_STAT_LAUNCHES) df_stat[b] = 0u; // (every launch of this kernel has at least 64 threads)
     if (b >= batch) return;
     FreezeState *F = fz + b;
     F->mode = 0; F->tries = 0; F->froze = 0; F->thawed = 0; F->n_active = 0; F->guard = 0.0f; F->launch_mode = 0; F->motion0 = 0.0;
@@ -3117,13 +3132,14 @@ struct sf_icp {
         uint64_t nbr_stamp = 0; // the neighbour table this alignment consults (0: none), its address and the first launch that does
         const void *nbr = nullptr;
         int nbr_from = 0;
+        int defer_first = -1; // the first deferring launch (look-up launches: defer_first())
         float max_corr = 0, accept = 0, eps = 0;
         double robust_k = 0;
         double cov_prm[5] = {0, 0, 0, 0, 0};
         bool operator==(const GraphKey &o) const
         {
             return mode == o.mode && iters == o.iters && batch == o.batch && window == o.window && ordered == o.ordered && reuse == o.reuse && n == o.n && map == o.map &&
-                   map_generation == o.map_generation && epochs == o.epochs && nbr_stamp == o.nbr_stamp && nbr == o.nbr && nbr_from == o.nbr_from && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
+                   map_generation == o.map_generation && epochs == o.epochs && nbr_stamp == o.nbr_stamp && nbr == o.nbr && nbr_from == o.nbr_from && defer_first == o.defer_first && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
                    robust_kind == o.robust_kind && robust_k == o.robust_k && cov_on == o.cov_on && std::memcmp(cov_prm, o.cov_prm, sizeof(cov_prm)) == 0;
         }
     };
@@ -3238,6 +3254,10 @@ struct sf_icp {
     uint64_t mark_nbr_stamp = 0;
     int defer = 1;                  // sf_icp_set_defer_search: the verifying launches of the frozen-pairs schedule list their stragglers for a dense pass (k_nn_red_df)
     bool df_planned = false;        // the last alignment's launch list held a deferring launch (fz_from as it stood THEN: a fetch may re-learn it)
+    int lk_first = -1, lk_launches = 0; // the last alignment's look-up launches (lookup_form): the first one's index and how many (sf_icp_lookup_launch_stats)
+    int64_t lk_waves = 0;           // and the waves of one of them
+    int lk_min = 0;                 // no look-up launch before this index: learnt with fz_from (freeze_learn_schedule), 0 while from_launch is pinned
+    bool step_nbr = false;          // stepping: the alignment begun with first != 0 consults the neighbour table
     int64_t nn_stats_used = 0;
     static constexpr int64_t NN_STATS_CAP = 1024;
     // robust kernel of P2PLANE (sf_icp_set_robust_kernel): read at enqueue, passed to the kernels by value
@@ -3666,6 +3686,8 @@ void prof_collect(sf_icp *icp)
     icp->ev_used = 0;
 }
 
+int defer_first(const sf_icp *icp, int mode);
+
 sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
 {
     const Lane &ln = icp->cur(); const SrcSet &ss = icp->src();
@@ -3675,6 +3697,7 @@ sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
     k.map = (const void *)icp->map;
     k.map_generation = icp->map->generation;
     if (icp->nbr_active) { k.nbr_stamp = icp->map->nbr_stamp; k.nbr = icp->map->nbr.p; k.nbr_from = icp->nbr_from; }
+    k.defer_first = defer_first(icp, mode);
     k.robust_kind = robust_on(icp, mode) ? icp->robust_kind : SF_ROBUST_NONE; k.robust_k = robust_on(icp, mode) ? icp->robust_k : 0.0; // (passed by value to the robust kernels)
     k.cov_on = icp->cov_on;
     if (icp->cov_on) { const double cp[5] = {icp->cov_arg.sensor_sigma, icp->cov_arg.thr_t, icp->cov_arg.thr_r, icp->cov_arg.infl_t, icp->cov_arg.infl_r}; std::memcpy(k.cov_prm, cp, sizeof(cp)); }
@@ -3820,7 +3843,7 @@ int freeze_alloc(sf_icp *icp)
     SF_TRY(ln.df_cnt.reserve(sizeof(uint8_t) * (BLK / 64) * rows));
     SF_TRY(ln.df_ids.reserve(sizeof(uint16_t) * (BLK / 64) * DF_WCAP * rows));
     SF_TRY(ln.df_part.reserve(sizeof(double) * REC_STRIDE * FZ_FEW * (size_t)ss.batch));
-    SF_TRY(ln.df_stat.reserve(sizeof(uint32_t) * 2));
+    SF_TRY(ln.df_stat.reserve(sizeof(uint32_t) * (2 + DF_STAT_LAUNCHES)));
     return SF_OK;
 }
 
@@ -3852,12 +3875,46 @@ DeferBufs defer_bufs(sf_icp *icp)
 // last launch through k_nn_red before the first chance to freeze, when it runs two queries per lane and every wave first
 // tries to verify.  The freeze launch and the launches after it search in place (the freeze launch has next to nothing left
 // to search: the pass behind it measured as a loss, profiles/LADDER.md round 6), as do the sharded paths.
-bool defer_now(const sf_icp *icp, int mode, int k)
+//
+// Look-up launches: an alignment that consults a neighbour table (nbr_prepare has said so: unsharded, whole map) runs EVERY
+// launch from the first that consults it (nbr_from) up to the freeze launch this way.  From there on the table and the nearest
+// gap settle nearly every query whose certificate fails, so these launches look up, they do not search: two queries per lane
+// with all loads requested at once, the few queries the table leaves to the dense pass (profiles/LADDER.md round 9).
+// Configuration alone decides, as for the table itself; without a table the schedule is what it was.
+// lk_min: like fz_from, the schedule of the NEXT alignment learns from the one fetched (freeze_learn_schedule) -- a look-up launch
+// in which many waves exceed the cap is slower than the launch it replaces, and the first look-up launch moves behind it.
+// -> the first look-up launch of the alignment, fz_from when it has none
+int lookup_first(const sf_icp *icp, int mode)
 {
-    return freeze_on(icp, mode) && icp->defer != 0 && !icp->shard && k >= VERIFY_FROM_SEARCH && k + 1 == icp->fz_from;
+    if (!freeze_on(icp, mode) || icp->defer == 0 || icp->shard || !icp->nbr_active || icp->nbr_from < 1) return icp->fz_from;
+    return std::min(icp->fz_from, std::max(icp->nbr_from, icp->lk_min));
 }
 
-bool defer_planned(const sf_icp *icp, int mode) { return defer_now(icp, mode, icp->fz_from - 1); }
+bool lookup_form(const sf_icp *icp, int mode) { return lookup_first(icp, mode) < icp->fz_from; }
+
+// the first deferring launch of the alignment; the launches from it up to fz_from - 1 defer (fz_from: none does)
+int defer_first(const sf_icp *icp, int mode)
+{
+    if (!freeze_on(icp, mode) || icp->defer == 0 || icp->shard) return icp->fz_from;
+    const int last = icp->fz_from - 1 >= VERIFY_FROM_SEARCH ? icp->fz_from - 1 : icp->fz_from; // (the deferring launch of the schedule without a table)
+    return std::min(lookup_first(icp, mode), last);
+}
+
+bool defer_now(const sf_icp *icp, int mode, int k) { return k >= defer_first(icp, mode) && k < icp->fz_from; }
+
+bool defer_planned(const sf_icp *icp, int mode) { return defer_first(icp, mode) < icp->fz_from; }
+
+// one query per lane: a wide scan's launches while nearly every query searches, unless the launch is a look-up launch
+bool one_per_lane_now(const sf_icp *icp, int mode, int k) { return mode == SF_ICP_P2PLANE && icp->src().qpl > 1 && k < VERIFY_FROM_SEARCH && !defer_now(icp, mode, k); }
+
+// what sf_icp_lookup_launch_stats reports of the alignment being enqueued
+void lookup_describe(sf_icp *icp, int mode)
+{
+    const bool on = !icp->last_fused && lookup_form(icp, mode);
+    icp->lk_first = on ? lookup_first(icp, mode) : -1;
+    icp->lk_launches = on ? icp->fz_from - icp->lk_first : 0;
+    icp->lk_waves = (int64_t)icp->src().batch * icp->src().nblocks_nn * (BLK / 64);
+}
 
 void launch_nn_deferred(sf_icp *icp, uint32_t *stats)
 {
@@ -3878,7 +3935,8 @@ void launch_nn_red_df(sf_icp *icp)
     uint32_t *stats = nullptr;
     if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
     hipLaunchKernelGGL((k_nn_red_df<SF_WIDE_QPL>), grid, blk, 0, icp->ctx->stream, grid_for(icp), m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(),
-                       o3d_thr(icp), ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp));
+                       o3d_thr(icp), ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp),
+                       lookup_form(icp, SF_ICP_P2PLANE) ? lookup_first(icp, SF_ICP_P2PLANE) : VERIFY_FROM_SEARCH);
     launch_nn_deferred(icp, stats);
 }
 
@@ -4032,15 +4090,16 @@ int enqueue_align(sf_icp *icp, int mode)
         // 929, 804, 508, 414 against 954, 836, 539, 439 us); from the launch in which waves start to certify whole, two
         const bool wide = ss.qpl > 1 && !icp->shard;
         for (int k = 0; k < K; ++k) {
-            const bool q1 = wide && k < VERIFY_FROM_SEARCH; // (the same schedule with the reuse off: it is part of the summation order, and reuse on == off bit for bit)
-            const bool df = !q1 && defer_now(icp, mode, k);
+            const bool df = defer_now(icp, mode, k); // (a look-up launch of a table alignment, or the last launch before the freeze launch)
+            const bool q1 = wide && k < VERIFY_FROM_SEARCH && !df; // (the same schedule with the reuse off: it is part of the summation order, and reuse on == off bit for bit)
             if (fz && k >= icp->fz_from) launch_nn_red_fz(icp, false, k > icp->fz_from);
-            else if (tile_launch(icp, k)) launch_tile_search<2>(icp, q1);
             else if (df) launch_nn_red_df(icp);
+            else if (tile_launch(icp, k)) launch_tile_search<2>(icp, q1);
             else launch_nn_red<2>(icp, false, q1);
-            if (fz && k + 1 >= icp->fz_from) // (after a one-query-per-lane launch too: an ordinary record of twice as many rows, and the solve may ask for the freeze launch)
+            if (fz && (df || k + 1 >= icp->fz_from)) // (after a one-query-per-lane launch too: an ordinary record of twice as many rows, and the solve may ask for the freeze launch;
+                                                      // behind every deferring launch: the deferred rows are added here.  Only the solve before fz_from asks for a freeze)
                 hipLaunchKernelGGL(k_reduce_solve_fz, dim3(B), dim3(RBLK), 0, s, st, part, q1 ? ss.nblocks : ss.nblocks_nn, n, K, ss.d_boxes.as<ScanBox>(), freeze_bufs(icp, true, df),
-                                   icp->fz_prm, (int)(k + 2 < K));
+                                   icp->fz_prm, (int)(k + 1 >= icp->fz_from && k + 2 < K));
             else if (q1)
                 hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks, n, k, K, ss.d_boxes.as<ScanBox>());
             else
@@ -4555,6 +4614,7 @@ extern "C" int sf_icp_set_neighbour_research(sf_icp *icp, int from_launch)
     SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
     SF_CHECK(from_launch != 0, SF_ERR_INVALID, "from_launch must be at least 1 (the first launch has no cached neighbours), or negative for off");
     icp->nbr_from = from_launch < 0 ? -1 : from_launch;
+    icp->lk_min = 0;
     return SF_OK;
 }
 
@@ -4603,6 +4663,21 @@ extern "C" int sf_icp_defer_stats(sf_icp *icp, int64_t out[2])
     return SF_OK;
 }
 
+extern "C" int sf_icp_lookup_launch_stats(sf_icp *icp, int64_t out[4])
+{
+    SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
+    out[0] = out[1] = out[2] = 0;
+    out[3] = -1;
+    if (icp->lk_launches <= 0) return SF_OK; // (as recorded when the alignment was enqueued)
+    int64_t df[2];
+    SF_TRY(sf_icp_defer_stats(icp, df)); // with a table every deferring launch is a look-up launch
+    out[0] = icp->lk_launches;
+    out[1] = df[0];
+    out[2] = df[1];
+    out[3] = icp->lk_first;
+    return SF_OK;
+}
+
 extern "C" int sf_icp_set_freeze(sf_icp *icp, int on)
 {
     SF_CHECK(icp, SF_ERR_INVALID, "icp is NULL");
@@ -4624,8 +4699,21 @@ void freeze_learn_schedule(sf_icp *icp)
 {
     if (!icp->fz_from_auto || icp->last_fused || icp->shard || icp->last_mode != SF_ICP_P2PLANE) return;
     const int K = icp->prm.num_iters;
-    if (++icp->fz_fetches >= FZ_PROBE_EVERY) { icp->fz_fetches = 0; icp->fz_from = FZ_FROM_DEFAULT; return; }
+    if (++icp->fz_fetches >= FZ_PROBE_EVERY) { icp->fz_fetches = 0; icp->fz_from = FZ_FROM_DEFAULT; icp->lk_min = 0; return; }
     if (!freeze_on(icp, icp->last_mode)) return; // (nothing was tried: nothing learnt)
+    // Look-up launches (round 9): with priors decimetres off the early ones still move the pose too far for the table -- waves with
+    // more than the cap left search in place after a wasted attempt, and the launch is slower than the searching launch it replaced
+    // (tools/city_bench.py, 0.3 m / 1.5 degrees: launch index 2 644 -> 813 us).  A launch without capped waves gained a tenth, so
+    // the form stops paying somewhere near one capped wave in six: the next alignment starts its look-up launches behind the last
+    // one that had more than one in eight.  (Only later, never earlier: a launch that did not run this way counted nothing; the
+    // probe above starts over.)
+    if (icp->lk_launches > 0 && icp->cur().df_stat.p) {
+        uint32_t h[2 + DF_STAT_LAUNCHES];
+        if (hipMemcpy(h, icp->cur().df_stat.p, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) { // (the stream has drained: states_to_host)
+            for (int k = icp->lk_first; k < icp->lk_first + icp->lk_launches && k < DF_STAT_LAUNCHES - 1; ++k)
+                if ((int64_t)h[2 + k] * 8 > icp->lk_waves) icp->lk_min = std::max(icp->lk_min, k + 1);
+        }
+    }
     int latest = -1, never = 0;
     for (int b = 0; b < icp->src().batch; ++b) {
         const IcpState &S = icp->h_state[(size_t)b];
@@ -4655,6 +4743,7 @@ extern "C" int sf_icp_set_freeze_params(sf_icp *icp, float guard_scale, float gu
     icp->fz_prm = FreezeParams{guard_scale, guard_min, guard_max, max_tries};
     icp->fz_from = from_launch;
     icp->fz_from_auto = false;
+    icp->lk_min = 0;
     return SF_OK;
 }
 
@@ -4849,9 +4938,10 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     const SrcSet &ss = icp->src(); // (an alignment never flips the source set)
     icp->last_mode = mode;
     icp->last_fused = fused_eligible(icp, mode);
-    icp->df_planned = !icp->last_fused && defer_planned(icp, mode);
     SF_TRY(order_lut_prepare(icp));
     SF_TRY(nbr_prepare(icp, mode));
+    icp->df_planned = !icp->last_fused && defer_planned(icp, mode); // (behind nbr_prepare: a table moves the first deferring launch)
+    lookup_describe(icp, mode);
     icp->nbr_stats_first = icp->nn_stats_used;
     // the launch list takes a lane (see sf_icp::Lane); the single launch, profiled runs and a count left on the device stay on the context's stream
     const bool beside = icp->unfetched; // an alignment of this object is still unfetched: this one may run beside it
@@ -5165,11 +5255,16 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     SF_HIP(hipSetDevice(icp->ctx->device));
     icp->last_mode = mode;
     icp->last_fused = false;
-    icp->nbr_active = false; // (the stepping paths search as always)
+    if (first) { // (the unsharded stepping path consults the table as the launch list does: the same launches, bit for bit)
+        SF_TRY(nbr_prepare(icp, mode));
+        icp->step_nbr = icp->nbr_active;
+        icp->nbr_stats_first = icp->nn_stats_used;
+    }
+    icp->nbr_active = icp->step_nbr;
     icp->map->served = true;
     if (first) SF_TRY(step_adopt_source(icp)); // (sf_icp_align_group and the all-reduce form of sf_icp_align_sharded_async start here too)
     if (first == 1) lane_describe(icp, mode, false);
-    if (first) icp->df_planned = defer_planned(icp, mode);
+    if (first) { icp->df_planned = defer_planned(icp, mode); lookup_describe(icp, mode); }
     if (first) SF_TRY(order_lut_prepare(icp));
     if (first == 1) SF_TRY(launch_state_init(icp));
     if (icp->shard) {
@@ -5182,7 +5277,7 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     double *x = reinterpret_cast<double *>(sf_icp_exchange_ptr(icp, nullptr));
     hipStream_t s = icp->ctx->stream;
     // wide scans: the first launches of a pass with one query per lane, as enqueue_align (rows of 256: twice as many)
-    const bool q1 = mode == SF_ICP_P2PLANE && ss.qpl > 1 && icp->fz_step < VERIFY_FROM_SEARCH;
+    const bool q1 = one_per_lane_now(icp, mode, icp->fz_step);
     const int nb = icp->shard ? (q1 ? icp->own_nblocks * ss.qpl : icp->own_nblocks) : (q1 ? ss.nblocks : ss.nblocks_nn);
     const int qpl_now = q1 ? 1 : ss.qpl;
     const uint32_t *off = icp->shard ? icp->own_off.as<uint32_t>() : nullptr;
@@ -5191,7 +5286,7 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
         ProfScope ps(icp, SF_PROF_REDUCE);
         hipLaunchKernelGGL(k_reduce_only<1>, dim3(ss.batch), dim3(SBLK), 0, s, ln.state.as<IcpState>(), ln.partials.as<double>(), nb, x, off, ss.qpl, freeze_bufs(icp, false));
     } else {
-        const bool df = !q1 && defer_now(icp, mode, icp->fz_step);
+        const bool df = mode == SF_ICP_P2PLANE && defer_now(icp, mode, icp->fz_step);
         if (freeze_nn_now(icp, mode)) launch_nn_red_fz(icp, icp->shard, icp->fz_step > icp->fz_from);
         else if (df) launch_nn_red_df(icp);
         else launch_nn_red<2>(icp, icp->shard, q1);
