@@ -302,6 +302,39 @@ int sf_map_cluster_euclidean(sf_map *m, double tolerance, int64_t min_size, int6
  * An empty cloud is SF_OK with zero stats. */
 int sf_cloud_filter_clusters(sf_cloud *c, double tolerance, int64_t min_size, int64_t max_size, float cell, sf_cluster_stats *stats);
 int sf_cloud_keep_largest_cluster(sf_cloud *c, double tolerance, float cell, sf_cluster_stats *stats);
+/* RANSAC plane segmentation and ground removal of a cloud (pcl::SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE,
+ * Open3D segment_plane; EXTENSION, no reference counterpart -- the reference's floor is sf_cloud_remove_floor's z > 0).  The result is
+ * a function of the cloud and the parameters alone (restated in tests/plane_ref_np.py):
+ *   samples     mix = the splitmix64 step; hypothesis h of num_hypotheses samples the indices
+ *               mix(seed + 0x9E3779B97F4A7C15 (3h + j + 1)) mod n, j = 0, 1, 2.
+ *   hypotheses  built on the host in float64, unfused, left to right: N = (p1 - p0) x (p2 - p0), nn = Nx^2 + Ny^2 + Nz^2, N^ = N / sqrt(nn),
+ *               d = -(N^ . p0), rounded to float32 once.  Oriented N^ . axis >= 0 with an axis, else the first non-zero of
+ *               (N^z, N^y, N^x) is positive.  Degenerate (four NaNs): two equal indices, nn not finite or not > 0, or an axis is
+ *               given and |N^ . axis| < axis_min_cos.  The axis is normalised in float64; all zeros mean none.
+ *   score       t = (float)distance_threshold; x is an inlier of (a, b, c, d) iff fabsf(s) < t with s = a x; s = s + b y; s = s + c z;
+ *               s = s + d in float32, unfused.  Non-finite points and NaN planes never match.
+ *   choice      the largest inlier count, on a tie the smallest h.  Below min_inliers no plane is found: found = 0, the plane is
+ *               four zeros, no point is an inlier, and the call returns SF_OK.
+ *   refit       (refine != 0) over the inliers of the best plane: float64 moments of x - c0, c0 = -d (a, b, c); mean m, covariance,
+ *               its smallest eigenvector (the routine of the map normals) signed so that it does not oppose the hypothesis;
+ *               d' = -n' . (c0 + m); rounded to float32.  Fewer than 3 inliers or anything non-finite: the hypothesis stands,
+ *               refined = 0.  The final inliers (n_inliers) are those of the final plane under the score rule.
+ * The same call returns the same bits every time (fixed summation order, integer atomics only).  SF_ERR_INVALID, nothing touched:
+ * num_hypotheses outside 1 .. 4096; a threshold that is not finite and > 0; min_inliers < 3; axis_min_cos outside [0, 1]; an axis
+ * that is not finite; n >= 2^31.  An empty cloud is SF_OK with zero stats and found = 0 (plane_hypotheses: every hypothesis
+ * degenerate, samples -1).  plane_hypotheses, score_planes and segment_plane leave the cloud as it is.  remove_plane compacts in place
+ * like a crop -- the order is kept, sf_cloud_last_indices reports the survivors -- keeping the non-inliers, or the inliers when
+ * keep_inliers != 0, and removes nothing when no plane is found.  profile != 0: device events around the scoring launches (score_ms)
+ * and from the first to the last kernel (total_ms); otherwise both are -1. */
+typedef struct { double distance_threshold; int32_t num_hypotheses, refine; uint64_t seed; int64_t min_inliers;
+                 double axis[3], axis_min_cos; int32_t profile, pad; } sf_plane_params;
+typedef struct { int64_t n_points, n_hypotheses, n_degenerate, best_index, best_count, n_inliers;
+                 int32_t found, refined; float score_ms, total_ms; } sf_plane_stats;
+void sf_plane_default_params(sf_plane_params *p);   /* 0.1 m, 1024, refine 1, seed 0, min_inliers 3, no axis */
+int sf_cloud_plane_hypotheses(sf_cloud *c, const sf_plane_params *p, float *planes /* [H][4] */, int32_t *samples /* [H][3] or NULL */, int64_t *n_degenerate);
+int sf_cloud_score_planes(sf_cloud *c, const float *planes, int64_t n_planes /* 1 .. 4096 */, double distance_threshold, int64_t *counts);
+int sf_cloud_segment_plane(sf_cloud *c, const sf_plane_params *p, float plane[4], uint8_t *inlier /* [n] or NULL */, sf_plane_stats *stats);
+int sf_cloud_remove_plane(sf_cloud *c, const sf_plane_params *p, int keep_inliers, float plane[4], sf_plane_stats *stats);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */
@@ -941,6 +974,10 @@ int sf_test_linalg(sf_ctx *ctx, int op, const double *in, int in_stride, int64_t
 int sf_test_wave_reduce(sf_ctx *ctx, int width /* 1 | 16 | 32 */, const double *in /* [256][width] */, double *out /* [256] */);
 int sf_test_block_reduce(sf_ctx *ctx, int nrec /* 17 | 30 */, const double *in /* [256][nrec] */, double *out /* [32], in and out */);
 int sf_test_reduce_partials(sf_ctx *ctx, int nrec /* 11 | 17 | 24 | 30 */, int nt /* 256 | 1024 */, const double *part /* [nblocks][32] */, int nblocks, double *out /* [32] */);
+
+/* sf_cloud_score_planes with the grid of its scoring kernel capped at max_blocks workgroups (0: the production choice, at most
+ * 65536), so that a small cloud exercises the path where one workgroup takes several tiles. */
+int sf_test_plane_score(sf_cloud *c, const float *planes, int64_t n_planes, double t, int max_blocks, int64_t *counts);
 
 #ifdef __cplusplus
 }

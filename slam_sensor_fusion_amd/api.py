@@ -5,6 +5,7 @@ entry point raises.  Nothing here imports or calls anything under oracle/.
 """
 import atexit
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -83,6 +84,42 @@ class ClusterStats(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class PlaneParams(C.Structure):
+    """sf_plane_params: what a plane segmentation is asked for (sf_plane_default_params: 0.1 m, 1024 hypotheses, refine, seed 0,
+    min_inliers 3, no axis)."""
+    _fields_ = [("distance_threshold", C.c_double), ("num_hypotheses", C.c_int32), ("refine", C.c_int32), ("seed", C.c_uint64), ("min_inliers", C.c_int64),
+                ("axis", C.c_double * 3), ("axis_min_cos", C.c_double), ("profile", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return dict(distance_threshold=float(self.distance_threshold), num_hypotheses=int(self.num_hypotheses), refine=int(self.refine), seed=int(self.seed),
+                    min_inliers=int(self.min_inliers), axis=[float(v) for v in self.axis], axis_min_cos=float(self.axis_min_cos), profile=int(self.profile))
+
+
+class PlaneStats(C.Structure):
+    """sf_plane_stats: what a plane segmentation found (best_index / best_count: the winning hypothesis and its inliers; n_inliers:
+    those of the final plane; score_ms / total_ms: -1 unless profiled)."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_hypotheses", "n_degenerate", "best_index", "best_count", "n_inliers")] + \
+               [("found", C.c_int32), ("refined", C.c_int32), ("score_ms", C.c_float), ("total_ms", C.c_float)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+def _plane_params(distance_threshold, num_hypotheses, refine, seed, min_inliers, axis, max_angle_deg, profile):
+    """The keyword form of the plane calls -> PlaneParams.  The ABI takes the cosine of the angle: it is math.cos's here."""
+    p = PlaneParams()
+    load_library().sf_plane_default_params(C.byref(p))
+    p.distance_threshold, p.num_hypotheses, p.refine = float(distance_threshold), int(num_hypotheses), int(bool(refine))
+    p.seed, p.min_inliers, p.profile = int(seed) & 0xFFFFFFFFFFFFFFFF, int(min_inliers), int(bool(profile))
+    if axis is not None:
+        a = [float(v) for v in np.asarray(axis, dtype=np.float64).reshape(3)]
+        p.axis[0], p.axis[1], p.axis[2] = a
+        p.axis_min_cos = 0.0 if max_angle_deg is None else math.cos(math.radians(float(max_angle_deg)))
+    elif max_angle_deg is not None:
+        raise SlamFusionError("max_angle_deg needs an axis")
+    return p
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
@@ -140,6 +177,12 @@ def load_library():
     lib.sf_test_wave_reduce.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_test_block_reduce.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_test_reduce_partials.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.sf_plane_default_params.restype = None
+    lib.sf_cloud_plane_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_score_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]
+    lib.sf_cloud_segment_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_remove_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_test_plane_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -175,6 +218,14 @@ def _f64(a):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def hook_plane_score(cloud, planes, distance_threshold, max_blocks=0):
+    """Test hook (sf_test_plane_score): Cloud.score_planes with the scoring grid capped at max_blocks workgroups (0: as in production)."""
+    planes = _f32(planes).reshape(-1, 4)
+    counts = np.empty(len(planes), np.int64)
+    _check(cloud.lib.sf_test_plane_score(cloud.h, _p(planes), len(planes), float(distance_threshold), int(max_blocks), _p(counts)))
+    return counts
 
 
 def hook_radix_sort(ctx, keys, vals, end_bit, lead=0, lead_alt=0):
@@ -414,6 +465,41 @@ class Cloud:
         st = ClusterStats()
         _check(self.lib.sf_cloud_keep_largest_cluster(self.h, C.c_double(tolerance), C.c_float(cell), C.byref(st)))
         return st.as_dict()
+
+    def plane_hypotheses(self, num_hypotheses=1024, seed=0, axis=None, max_angle_deg=None):
+        """sf_cloud_plane_hypotheses: the planes a segmentation with these parameters scores -> (planes float32 [H, 4], a degenerate
+        one four NaNs; samples int32 [H, 3], the original indices; the number of degenerate hypotheses)."""
+        p = _plane_params(0.1, num_hypotheses, True, seed, 3, axis, max_angle_deg, False)
+        h = max(int(num_hypotheses), 0)
+        planes, samples, n_deg = np.empty((h, 4), np.float32), np.empty((h, 3), np.int32), C.c_int64()
+        _check(self.lib.sf_cloud_plane_hypotheses(self.h, C.byref(p), _p(planes), _p(samples), C.byref(n_deg)))
+        return planes, samples, n_deg.value
+
+    def score_planes(self, planes, distance_threshold):
+        """sf_cloud_score_planes: the inliers of each plane (a, b, c, d) under the score rule -> int64 [len(planes)]."""
+        planes = _f32(planes).reshape(-1, 4)
+        counts = np.empty(len(planes), np.int64)
+        _check(self.lib.sf_cloud_score_planes(self.h, _p(planes), C.c_int64(len(planes)), C.c_double(distance_threshold), _p(counts)))
+        return counts
+
+    def segment_plane(self, distance_threshold=0.1, num_hypotheses=1024, refine=True, seed=0, min_inliers=3, axis=None, max_angle_deg=None, profile=False):
+        """sf_cloud_segment_plane (pcl::SACSegmentation with SACMODEL_PLANE, or SACMODEL_PERPENDICULAR_PLANE with `axis` and
+        `max_angle_deg`; Open3D segment_plane): the plane with the most points within `distance_threshold` among `num_hypotheses`
+        three-point samples, refitted to its inliers -> (plane float32 [4], inlier mask bool [n], stats dict).  The cloud stays as it
+        is.  No plane with min_inliers points: stats["found"] = 0, the plane is zeros, no inlier."""
+        p = _plane_params(distance_threshold, num_hypotheses, refine, seed, min_inliers, axis, max_angle_deg, profile)
+        plane, inlier, st = np.zeros(4, np.float32), np.zeros(len(self), np.uint8), PlaneStats()
+        _check(self.lib.sf_cloud_segment_plane(self.h, C.byref(p), _p(plane), _p(inlier), C.byref(st)))
+        return plane, inlier.astype(bool), st.as_dict()
+
+    def remove_plane(self, distance_threshold=0.1, num_hypotheses=1024, refine=True, seed=0, min_inliers=3, axis=None, max_angle_deg=None, profile=False,
+                     keep_inliers=False):
+        """sf_cloud_remove_plane: segment_plane, then the inliers are taken out (keep_inliers: everything else is) in place, order
+        kept, `last_indices` reports the survivors -> (plane, stats dict).  Nothing is removed when no plane is found."""
+        p = _plane_params(distance_threshold, num_hypotheses, refine, seed, min_inliers, axis, max_angle_deg, profile)
+        plane, st = np.zeros(4, np.float32), PlaneStats()
+        _check(self.lib.sf_cloud_remove_plane(self.h, C.byref(p), C.c_int(int(bool(keep_inliers))), _p(plane), C.byref(st)))
+        return plane, st.as_dict()
 
     def last_indices(self):
         n = C.c_int64()

@@ -1752,6 +1752,9 @@ extern "C" int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int m
 // ------------------------------------------------------------------ clustering (extension, no reference code)
 #include "sf_cluster.hpp"
 
+// ------------------------------------------------------------------ plane segmentation (extension, no reference code)
+#include "sf_plane.hpp"
+
 extern "C" int sf_map_profile_launches(sf_map *m, int on)
 {
     SF_CHECK(m, SF_ERR_INVALID, "bad arguments");
