@@ -335,6 +335,51 @@ int sf_cloud_plane_hypotheses(sf_cloud *c, const sf_plane_params *p, float *plan
 int sf_cloud_score_planes(sf_cloud *c, const float *planes, int64_t n_planes /* 1 .. 4096 */, double distance_threshold, int64_t *counts);
 int sf_cloud_segment_plane(sf_cloud *c, const sf_plane_params *p, float plane[4], uint8_t *inlier /* [n] or NULL */, sf_plane_stats *stats);
 int sf_cloud_remove_plane(sf_cloud *c, const sf_plane_params *p, int keep_inliers, float plane[4], sf_plane_stats *stats);
+/* Per-label boxes and multi-box removal (extension, no reference code; PCL getMinMax3D / MomentOfInertiaEstimation after
+ * EuclideanClusterExtraction, Open3D get_axis_aligned_bounding_box / get_oriented_bounding_box per cluster).
+ * Membership.  Point i belongs to label l = labels[i] iff 0 <= l < n_labels and the point is finite.  A label outside that range
+ *   (-1 included) counts as n_ignored whatever the point holds; a non-finite point with a label in range counts as n_nonfinite;
+ *   n_points = n_labelled + n_ignored + n_nonfinite.  A label without members: valid = 0, count = 0, every other field zero.
+ * lo, hi: the float32 minimum and maximum per coordinate.  Pivot c0 = ((double)lo + (double)hi) / 2.
+ * Moments: float64 sums S1 of d = (double)x - c0 and S2 of d d^T over the members; mean = c0 + S1 / count,
+ *   cov = S2 / count - (S1 / count)(S1 / count)^T (population; xx xy xz yy yz zz).  The summation order is a function of n and
+ *   the labels alone; no float atomics: the same call returns the same bits every time.
+ * Axes (the columns of the row-major R).  SF_BOX_AABB: the identity, eigenvalues = the variances xx, yy, zz.
+ *   SF_BOX_PCA: the symmetric Jacobi eigen-solve of cov, eigenvalues descending, ties in index order; a0 and a1 each signed so
+ *   that their component of largest magnitude (the first such on a tie) is positive; a2 = a0 x a1.
+ *   SF_BOX_UPRIGHT: u = up normalised in float64 (all zeros: +z); e1 = normalize(u x e_k), k the coordinate of smallest |u_k|
+ *   (the first on a tie), e2 = u x e1; c11, c12, c22 the covariance in (e1, e2); theta = atan2(2 c12, c11 - c22) / 2;
+ *   a0 = cos(theta) e1 + sin(theta) e2 signed as above, a2 = u, a1 = a2 x a0; eigenvalues = the variances along a0, a1, a2.
+ *   A covariance that is not finite: the identity, zero eigenvalues, valid = 2.
+ * center, extent: pmin_k, pmax_k = the minimum and maximum over the members of (d_x a_kx + d_y a_ky) + d_z a_kz in float64,
+ *   unfused; h_k = (pmin_k + pmax_k) / 2; center_i = c0_i + R[3i] h_0 + R[3i+1] h_1 + R[3i+2] h_2, the exact value rounded once
+ *   (evaluated in double-double: the crop subtracts the rounded center, so every further rounding would move the faces against the
+ *   members on them); extent_k = pmax_k - pmin_k.  center, R and extent are the arguments of sf_cloud_crop_obb (extent: full
+ *   lengths); a member on a face may still miss its own box's crop by the one rounding of center: pass a margin of an ulp of it.
+ * SF_ERR_INVALID, nothing touched: n_labels < 0 or > 2^24; n >= 2^31; an unknown mode; an up that is not finite.  An empty cloud
+ * is SF_OK with zero stats and every box invalid.  The cloud is not modified.  profile != 0: device_ms = the device time from
+ * the first to the last kernel (the label upload excluded), otherwise -1.
+ * sf_cloud_cluster_boxes: the labels of sf_map_cluster_euclidean(tolerance, min_size, max_size) on a temporary map of the cloud
+ *   (`cell` as in sf_map_build) never leave the device; boxes [min(n_clusters, cap_boxes)] in label order, bit for bit those of
+ *   sf_cloud_label_boxes given these labels, whatever the cell.  cstats / bstats may be NULL.
+ * sf_cloud_remove_boxes: a point is inside iff it passes sf_cloud_crop_obb's float64 predicate (the same expressions in the same
+ *   order) for at least one of the n_boxes boxes, each with extent_k + 2 margin; a non-finite point is never inside.  Compacts in
+ *   place like a crop -- the order is kept, sf_cloud_last_indices reports the survivors -- keeping the outside points, or the
+ *   inside ones when keep_inside != 0.  n_boxes 0 .. 1024 (0: nothing is inside); a margin that is not finite is SF_ERR_INVALID.
+ *   *n_inside (may be NULL) = the points inside. */
+#define SF_BOX_AABB 0
+#define SF_BOX_PCA 1
+#define SF_BOX_UPRIGHT 2
+typedef struct { int32_t mode, profile; double up[3]; } sf_box_params;
+typedef struct { int64_t count; float lo[3], hi[3]; double mean[3], cov[6];
+                 double center[3], R[9], extent[3], eigenvalues[3]; int32_t valid, pad; } sf_label_box;
+typedef struct { int64_t n_points, n_labelled, n_ignored, n_nonfinite, n_labels, n_valid; float device_ms; int32_t pad; } sf_box_stats;
+int sf_cloud_label_boxes(sf_cloud *c, const int32_t *labels /* host [n] */, int64_t n_labels, const sf_box_params *p,
+                         sf_label_box *boxes /* [n_labels] */, sf_box_stats *stats);
+int sf_cloud_cluster_boxes(sf_cloud *c, double tolerance, int64_t min_size, int64_t max_size, float cell, const sf_box_params *p,
+                           sf_label_box *boxes, int64_t cap_boxes, sf_cluster_stats *cstats, sf_box_stats *bstats);
+int sf_cloud_remove_boxes(sf_cloud *c, const double *center /* [B][3] */, const double *R /* [B][9] */, const double *extent /* [B][3] */,
+                          int64_t n_boxes /* 0 .. 1024 */, double margin, int keep_inside, int64_t *n_inside);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */
@@ -978,6 +1023,13 @@ int sf_test_reduce_partials(sf_ctx *ctx, int nrec /* 11 | 17 | 24 | 30 */, int n
 /* sf_cloud_score_planes with the grid of its scoring kernel capped at max_blocks workgroups (0: the production choice, at most
  * 65536), so that a small cloud exercises the path where one workgroup takes several tiles. */
 int sf_test_plane_score(sf_cloud *c, const float *planes, int64_t n_planes, double t, int max_blocks, int64_t *counts);
+
+/* sf_cloud_label_boxes with the grid of its three segmented passes capped at max_blocks workgroups (0: the production choice, at
+ * most 1024), so that a small cloud exercises the path where one workgroup walks several tiles and carries the open segment
+ * from tile to tile.  The summation order depends on the grid, so the moments differ from the production
+ * call's within their rounding bound (and the axes with them); count, lo, hi, valid and the stats are equal. */
+int sf_test_label_boxes(sf_cloud *c, const int32_t *labels, int64_t n_labels, const sf_box_params *p, int max_blocks,
+                        sf_label_box *boxes, sf_box_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,48 @@ def _plane_params(distance_threshold, num_hypotheses, refine, seed, min_inliers,
     return p
 
 
+BOX_MODES = {"aabb": 0, "pca": 1, "upright": 2}  # SF_BOX_*
+
+
+class BoxParams(C.Structure):
+    """sf_box_params: the axes rule of the per-label boxes (mode: SF_BOX_*; up: all zeros = +z) and the profile switch."""
+    _fields_ = [("mode", C.c_int32), ("profile", C.c_int32), ("up", C.c_double * 3)]
+
+    def as_dict(self):
+        return dict(mode=int(self.mode), profile=int(self.profile), up=[float(v) for v in self.up])
+
+
+class LabelBox(C.Structure):
+    """sf_label_box (256 bytes): one label's members summed up.  center, R (row-major, columns = axes) and extent (full lengths) are
+    the arguments of Cloud.crop_obb; valid: 0 no member, 1, 2 = the covariance was not finite (identity axes)."""
+    _fields_ = [("count", C.c_int64), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("mean", C.c_double * 3), ("cov", C.c_double * 6),
+                ("center", C.c_double * 3), ("R", C.c_double * 9), ("extent", C.c_double * 3), ("eigenvalues", C.c_double * 3), ("valid", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+LABEL_BOX_DTYPE = np.dtype([("count", "<i8"), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("mean", "<f8", (3,)), ("cov", "<f8", (6,)), ("center", "<f8", (3,)),
+                            ("R", "<f8", (3, 3)), ("extent", "<f8", (3,)), ("eigenvalues", "<f8", (3,)), ("valid", "<i4"), ("pad", "<i4")])
+
+
+class BoxStats(C.Structure):
+    """sf_box_stats: what a box call saw (n_points = n_labelled + n_ignored + n_nonfinite; n_valid: the labels with members;
+    device_ms: -1 unless profiled)."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_labelled", "n_ignored", "n_nonfinite", "n_labels", "n_valid")] + \
+               [("device_ms", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_ if name != "pad"}
+
+
+def _box_params(mode, up, profile):
+    """The keyword form of the box calls -> BoxParams (mode: "aabb" | "pca" | "upright" or the SF_BOX_* number)."""
+    p = BoxParams()
+    p.mode, p.profile = (BOX_MODES[mode] if mode in BOX_MODES else int(mode)), int(bool(profile))
+    if up is not None:
+        p.up[0], p.up[1], p.up[2] = [float(v) for v in np.asarray(up, dtype=np.float64).reshape(3)]
+    return p
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
@@ -183,6 +225,10 @@ def load_library():
     lib.sf_cloud_segment_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_cloud_remove_plane.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_test_plane_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p]
+    lib.sf_cloud_label_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_test_label_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_cluster_boxes.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_remove_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -226,6 +272,12 @@ def hook_plane_score(cloud, planes, distance_threshold, max_blocks=0):
     counts = np.empty(len(planes), np.int64)
     _check(cloud.lib.sf_test_plane_score(cloud.h, _p(planes), len(planes), float(distance_threshold), int(max_blocks), _p(counts)))
     return counts
+
+
+def hook_label_boxes(cloud, labels, n_labels=None, mode="pca", up=None, max_blocks=0):
+    """Test hook (sf_test_label_boxes): Cloud.label_boxes with the grid of the segmented passes capped at max_blocks workgroups (0: as
+    in production) -> (boxes, stats dict)."""
+    return cloud._label_boxes(labels, n_labels, mode, up, False, int(max_blocks))
 
 
 def hook_radix_sort(ctx, keys, vals, end_bit, lead=0, lead_alt=0):
@@ -500,6 +552,58 @@ class Cloud:
         plane, st = np.zeros(4, np.float32), PlaneStats()
         _check(self.lib.sf_cloud_remove_plane(self.h, C.byref(p), C.c_int(int(bool(keep_inliers))), _p(plane), C.byref(st)))
         return plane, st.as_dict()
+
+    def _label_boxes(self, labels, n_labels, mode, up, profile, max_blocks):
+        labels = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+        if len(labels) != len(self):
+            raise SlamFusionError("labels must have one entry per point (%d, got %d)" % (len(self), len(labels)))
+        if n_labels is None:
+            n_labels = int(labels.max()) + 1 if len(labels) and labels.max() >= 0 else 0
+        p, st = _box_params(mode, up, profile), BoxStats()
+        boxes = np.zeros(max(int(n_labels), 0), LABEL_BOX_DTYPE)
+        if max_blocks is None:
+            rc = self.lib.sf_cloud_label_boxes(self.h, _p(labels), C.c_int64(int(n_labels)), C.byref(p), _p(boxes), C.byref(st))
+        else:
+            rc = self.lib.sf_test_label_boxes(self.h, _p(labels), C.c_int64(int(n_labels)), C.byref(p), C.c_int(max_blocks), _p(boxes), C.byref(st))
+        _check(rc)
+        return boxes, st.as_dict()
+
+    def label_boxes(self, labels, n_labels=None, mode="pca", up=None, profile=False):
+        """sf_cloud_label_boxes (PCL getMinMax3D / MomentOfInertiaEstimation, Open3D get_axis_aligned_bounding_box /
+        get_oriented_bounding_box, per label): labels int32 [n], a member is a finite point with 0 <= label < n_labels (None: the largest
+        label + 1) -> (structured array [n_labels] of LABEL_BOX_DTYPE: count, lo, hi, mean, cov, center, R, extent, eigenvalues, valid;
+        stats dict).  mode "aabb" | "pca" | "upright" (axes about `up`, None = +z).  The cloud stays as it is."""
+        return self._label_boxes(labels, n_labels, mode, up, profile, None)
+
+    def cluster_boxes(self, tolerance, min_size=1, max_size=0, cell=0.0, mode="pca", up=None):
+        """sf_cloud_cluster_boxes: the boxes of the Euclidean clusters at `tolerance` (Map.cluster_euclidean's labels, which never leave
+        the device) -> (structured array [n_clusters] in label order, cluster stats dict, box stats dict).  The cloud stays as it is."""
+        p, cst, bst = _box_params(mode, up, False), ClusterStats(), BoxStats()
+        args = (self.h, C.c_double(tolerance), C.c_int64(int(min_size)), C.c_int64(int(max_size)), C.c_float(cell), C.byref(p))
+        boxes = np.zeros(min(len(self), 4096), LABEL_BOX_DTYPE)
+        _check(self.lib.sf_cloud_cluster_boxes(*args, _p(boxes), C.c_int64(len(boxes)), C.byref(cst), C.byref(bst)))
+        if cst.n_clusters > len(boxes):                     # more clusters than the first buffer holds: once more with room for all
+            boxes = np.zeros(int(cst.n_clusters), LABEL_BOX_DTYPE)
+            _check(self.lib.sf_cloud_cluster_boxes(*args, _p(boxes), C.c_int64(len(boxes)), C.byref(cst), C.byref(bst)))
+        return boxes[:int(cst.n_clusters)].copy(), cst.as_dict(), bst.as_dict()
+
+    def remove_boxes(self, boxes_or_arrays, margin=0.0, keep_inside=False):
+        """sf_cloud_remove_boxes: takes out the points inside at least one box (keep_inside: everything else), each box grown by
+        `margin` on every side; in place, order kept, `last_indices` reports the survivors -> the number of points inside.
+        boxes_or_arrays: a structured array of label_boxes / cluster_boxes (its valid entries are used) or (center [B, 3], R [B, 3, 3],
+        extent [B, 3]); at most 1024 boxes."""
+        if isinstance(boxes_or_arrays, np.ndarray) and boxes_or_arrays.dtype.names:
+            b = boxes_or_arrays[boxes_or_arrays["valid"] != 0]
+            center, R, extent = b["center"], b["R"], b["extent"]
+        else:
+            center, R, extent = boxes_or_arrays
+        center, R, extent = _f64(center).reshape(-1, 3), _f64(R).reshape(-1, 9), _f64(extent).reshape(-1, 3)
+        if not len(center) == len(R) == len(extent):
+            raise SlamFusionError("center, R and extent must describe the same number of boxes")
+        n_inside = C.c_int64()
+        _check(self.lib.sf_cloud_remove_boxes(self.h, _p(center), _p(R), _p(extent), C.c_int64(len(center)), C.c_double(margin), C.c_int(int(bool(keep_inside))),
+                                              C.byref(n_inside)))
+        return n_inside.value
 
     def last_indices(self):
         n = C.c_int64()

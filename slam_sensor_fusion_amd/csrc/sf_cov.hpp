@@ -95,61 +95,7 @@ __global__ __launch_bounds__(BLK, NN_RED_WAVES) void k_nn_cov(SfGrid g, SfWindow
     }
 }
 
-// ------------------------------------------------------------------ symmetric Jacobi, N x N in registers
-// One two-sided rotation of the pair (P, Q): A <- G^T A G with G's column P = c e_P - s e_Q and column Q = s e_P + c e_Q, the
-// smaller angle of tan 2t = 2 a_PQ / (a_QQ - a_PP) -- the rotation of jacobi_pair above, from two reciprocal square roots.
-// Everything is indexed at compile time (P, Q template parameters, loops unrolled): the matrices stay in registers.
-template <int N, int P, int Q>
-__device__ __forceinline__ bool jacobi_sym_pair(double (&A)[N * N], double (&V)[N * N])
-{
-    const double al = A[P * N + P], be = A[Q * N + Q], ga = A[P * N + Q];
-    if (ga * ga <= (DBL_EPSILON * DBL_EPSILON) * fabs(al * be) || fabs(ga) < 1e-150) return false;
-    const double tau = be - al;
-    const double r = rsqrt_nr(fma(tau, tau, 4.0 * ga * ga));
-    const double c2 = 0.5 + 0.5 * fabs(tau) * r;
-    const double rc = rsqrt_nr(c2);
-    const double c = c2 * rc, s = (tau >= 0 ? ga : -ga) * r * rc;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        if (k != P && k != Q) {
-            const double a = A[k * N + P], b = A[k * N + Q];
-            const double na = fma(c, a, -(s * b)), nb = fma(s, a, c * b);
-            A[k * N + P] = na; A[P * N + k] = na;
-            A[k * N + Q] = nb; A[Q * N + k] = nb;
-        }
-        const double va = V[k * N + P], vb = V[k * N + Q];
-        V[k * N + P] = fma(c, va, -(s * vb));
-        V[k * N + Q] = fma(s, va, c * vb);
-    }
-    const double cs2 = 2.0 * c * s * ga;
-    A[P * N + P] = fma(c * c, al, fma(s * s, be, -cs2));
-    A[Q * N + Q] = fma(s * s, al, fma(c * c, be, cs2));
-    A[P * N + Q] = 0.0; A[Q * N + P] = 0.0;
-    return true;
-}
-
-template <int N, int P, int Q>
-__device__ __forceinline__ bool jacobi_sym_sweep(double (&A)[N * N], double (&V)[N * N])
-{
-    bool any = jacobi_sym_pair<N, P, Q>(A, V);
-    if constexpr (Q + 1 < N) any = jacobi_sym_sweep<N, P, Q + 1>(A, V) || any;
-    else if constexpr (P + 2 < N) any = jacobi_sym_sweep<N, P + 1, P + 2>(A, V) || any;
-    return any;
-}
-
-// A = V diag(A_kk) V^T on return (A symmetric on entry; its off-diagonal is rotated away).  Converges quadratically: 6 x 6
-// takes 5-7 sweeps (8 with clustered eigenvalues, 4 for 3 x 3: tests/test_gpu_linalg_direct.py asserts <= 12), the cap is never
-// the reason to stop.  Returns the number of sweeps that rotated.
-template <int N>
-__device__ __forceinline__ int jacobi_sym(double (&A)[N * N], double (&V)[N * N])
-{
-#pragma unroll
-    for (int i = 0; i < N * N; ++i) V[i] = (i / N == i % N) ? 1.0 : 0.0;
-    int sweep = 0;
-    for (; sweep < 24; ++sweep)
-        if (!jacobi_sym_sweep<N, 0, 1>(A, V)) break;
-    return sweep; // (24: the cap stopped it)
-}
+// (jacobi_sym<N>: sf_jacobi.hpp, included by sf_icp.hip beside rsqrt_nr)
 
 __device__ __forceinline__ double recip_nr(double x) // 1 / x within 5 ulp for x in rsqrt_nr's domain (normal, positive, finite): no divide expansion on the one working lane
 {

@@ -84,21 +84,8 @@ __device__ __forceinline__ void mat4_mul(const double A[16], const double B[16],
     for (int i = 0; i < 16; ++i) C[i] = R[i];
 }
 
-// 1 / sqrt(x) for NORMAL x in [DBL_MIN, 1e300]: the hardware estimate and two Newton steps, within 2 ulp of the exact
-// value over that whole range (measured 2.0 ulp; recip_nr = its square: within 5 ulp, measured 4.0).  Outside the
-// domain -- 0, subnormals, inf, negative x, NaN -- the estimate is inf / 0 / NaN and the Newton steps make NaN of inf * 0:
-// every caller guards (svd3 by n2 > 1e-300, jacobi_pair / jacobi_sym_pair by their skip tests, k_cov_solve by its eigenvalue
-// floor and by W > 0).
-// The solve runs on ONE lane while the rest of its workgroup -- on the per-scan path the whole grid -- waits, so the
-// float64 divide / sqrt expansions (a few dozen dependent instructions each) are what an iteration's controller costs:
-// measured 6.2 us per controller step with divides and square roots, 3.2-4.0 us with this.
-__device__ __forceinline__ double rsqrt_nr(double x)
-{
-    double y = __builtin_amdgcn_rsq(x);
-    y = y * fma(-0.5 * x * y, y, 1.5);
-    y = y * fma(-0.5 * x * y, y, 1.5);
-    return y;
-}
+// rsqrt_nr (and the symmetric Jacobi of k_cov_solve, sf_cov.hpp): shared with sf_map.hip
+#include "sf_jacobi.hpp"
 
 // One Hestenes rotation of columns P, Q (the smaller angle): with al = |u_P|^2, be = |u_Q|^2, ga = u_P . u_Q,
 // cos 2t = |be - al| / w, sin 2t = 2 ga sgn(be - al) / w, w = sqrt((be - al)^2 + 4 ga^2); c = sqrt((1 + cos 2t) / 2),

@@ -1755,6 +1755,9 @@ extern "C" int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int m
 // ------------------------------------------------------------------ plane segmentation (extension, no reference code)
 #include "sf_plane.hpp"
 
+// ------------------------------------------------------------------ per-label boxes, multi-box removal (extension, no reference code)
+#include "sf_box.hpp"
+
 extern "C" int sf_map_profile_launches(sf_map *m, int on)
 {
     SF_CHECK(m, SF_ERR_INVALID, "bad arguments");
