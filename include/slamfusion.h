@@ -1031,6 +1031,22 @@ int sf_test_plane_score(sf_cloud *c, const float *planes, int64_t n_planes, doub
 int sf_test_label_boxes(sf_cloud *c, const int32_t *labels, int64_t n_labels, const sf_box_params *p, int max_blocks,
                         sf_label_box *boxes, sf_box_stats *stats);
 
+/* The launch schedule of an O3D_P2P / P2PLANE alignment (csrc/sf_schedule.hpp): the form launch k takes under
+ * each of `rows` configurations.  Host code alone -- make_schedule, launches and step_of, the functions every driver of the library
+ * dispatches on -- so it needs no context and no device.
+ *   in [rows][SF_TEST_SCHEDULE_IN]:   mode (SF_ICP_O3D_P2P | SF_ICP_P2PLANE), iterations K, queries per lane (1 | 2), sharded,
+ *     enqueued whole (1) or stepped (0), neighbour reuse, window kind of the map, robust kernel on, frozen pairs wanted,
+ *     from_launch, deferred search, neighbour table consulted, first launch that consults it, learnt first look-up launch, queries
+ *     sorted by tile
+ *   out[rows][SF_TEST_SCHEDULE_OUT]:  launches of the alignment; of launch k: its form (0 search, 1 tile search, 2 deferring,
+ *     3 freeze launch, 4 frozen, few workgroups), one query per lane, the solve takes the freeze state, the solve may ask for a
+ *     freeze launch, the deferred rows are added, the launch index from which k_nn_red_df first tries to verify a whole wave; of the
+ *     schedule: frozen pairs on, first look-up launch, first deferring launch (both from_launch: none)
+ * k is not checked against the launch count.  SF_ERR_INVALID: rows < 0, or a NULL array with rows > 0. */
+#define SF_TEST_SCHEDULE_IN 15
+#define SF_TEST_SCHEDULE_OUT 10
+int sf_test_launch_schedule(const int32_t *in, int64_t rows, int k, int32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

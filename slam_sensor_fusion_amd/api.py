@@ -229,6 +229,7 @@ def load_library():
     lib.sf_test_label_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_cloud_cluster_boxes.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sf_cloud_remove_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p]
+    lib.sf_test_launch_schedule.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     _lib = lib
     return lib
 
@@ -243,7 +244,7 @@ def kernel_source_hash():
     carry the hash of the build their counters were taken on; bench.py only quotes them while it still matches."""
     import hashlib
     h = hashlib.sha256()
-    for name in ("sf_icp.hip", "sf_nn_red_body.inc", "sf_nn.hpp", "sf_tile.hpp", "sf_order.hpp", "sf_common.hpp"):
+    for name in ("sf_icp.hip", "sf_nn_red_body.inc", "sf_nn.hpp", "sf_tile.hpp", "sf_order.hpp", "sf_common.hpp", "sf_schedule.hpp"):
         with open(os.path.join(_HERE, "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
@@ -264,6 +265,20 @@ def _f64(a):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+SCHEDULE_INPUTS = ("mode", "K", "qpl", "sharded", "whole", "reuse", "window", "robust", "wanted", "fz_from", "defer", "table", "nbr_from", "lk_min", "tile_on")
+SCHEDULE_OUTPUTS = ("launches", "nn", "one_per_lane", "solve_takes_freeze_state", "ask_freeze", "deferred_rows", "attempt_from", "fz", "lookup_first", "defer_first")
+NN_SEARCH, NN_TILE_SEARCH, NN_DEFERRING, NN_FREEZE, NN_FROZEN_FEW = range(5)
+
+
+def hook_launch_schedule(configs, k):
+    """Test hook (sf_test_launch_schedule): configs[rows][SCHEDULE_INPUTS] -> int32 [rows][SCHEDULE_OUTPUTS], the form of launch k
+    under each configuration.  Host code alone: needs no device."""
+    configs = np.ascontiguousarray(configs, dtype=np.int32).reshape(-1, len(SCHEDULE_INPUTS))
+    out = np.empty((len(configs), len(SCHEDULE_OUTPUTS)), np.int32)
+    _check(load_library().sf_test_launch_schedule(_p(configs), len(configs), int(k), _p(out)))
+    return out
 
 
 def hook_plane_score(cloud, planes, distance_threshold, max_blocks=0):

@@ -30,6 +30,7 @@
 #include "sf_tile.hpp"
 #include "sf_order.hpp"
 #include "sf_p2p.hpp"
+#include "sf_schedule.hpp"
 
 #include <cfloat>
 #include <cstdlib>
@@ -482,13 +483,9 @@ __global__ void k_state_init(IcpState *__restrict__ st, const double *__restrict
 // the neighbour reuse most launches of an alignment only verify, and a verifying wave is
 // vector-issue bound with the record reduction (~160 of its ~390 instructions) the largest item:
 // Q = 2 halves that per query.
-#ifndef SF_WIDE_QPL
-#define SF_WIDE_QPL 2
-#endif
 constexpr int64_t WIDE_SCAN_POINTS = 131072;
 constexpr int64_t WIDE_AUTO_POINTS = 65536; // see sf_icp::wide_auto
-constexpr int VERIFY_FROM_SEARCH = 4; // wide scans WITHOUT a neighbour table: from the fifth launch of an alignment on a wave first tries to verify all its queries at once
-                                      // (with a table the look-up launches start earlier, at the first launch that consults it: lookup_form / defer_first)
+using sf::VERIFY_FROM_SEARCH;
 #ifndef NN_RED_WAVES
 #define NN_RED_WAVES 4
 #endif
@@ -3112,21 +3109,22 @@ struct sf_icp {
     // it is unchanged; sf_map stamps every build / normals pass with a process-unique generation, DevBuf counts its
     // reallocations (epoch).
     struct GraphKey {
-        int mode = -1, iters = -1, batch = -1, window = -1, ordered = -1, reuse = -1, robust_kind = -1, cov_on = -1;
+        int batch = -1, ordered = -1, robust_kind = -1, cov_on = -1;
+        sf::Schedule sched; // which launches the list holds (mode, iterations, window kind and reuse are fields of it)
         int64_t n = -1;
         const void *map = nullptr;
         uint64_t map_generation = 0, epochs = 0;
-        uint64_t nbr_stamp = 0; // the neighbour table this alignment consults (0: none), its address and the first launch that does
+        uint64_t nbr_stamp = 0; // the neighbour table this alignment consults (0: none) and its address (the first launch that does: sched.nbr_from)
         const void *nbr = nullptr;
-        int nbr_from = 0;
-        int defer_first = -1; // the first deferring launch (look-up launches: defer_first())
-        float max_corr = 0, accept = 0, eps = 0;
+        float max_corr = 0, accept = 0, eps = 0, guard_scale = 0, guard_min = 0, guard_max = 0; // IcpParams and FreezeParams as the kernels take them: by value, each field itself
+        int max_tries = 0;
         double robust_k = 0;
         double cov_prm[5] = {0, 0, 0, 0, 0};
         bool operator==(const GraphKey &o) const
         {
-            return mode == o.mode && iters == o.iters && batch == o.batch && window == o.window && ordered == o.ordered && reuse == o.reuse && n == o.n && map == o.map &&
-                   map_generation == o.map_generation && epochs == o.epochs && nbr_stamp == o.nbr_stamp && nbr == o.nbr && nbr_from == o.nbr_from && defer_first == o.defer_first && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
+            return batch == o.batch && ordered == o.ordered && sched == o.sched && n == o.n && map == o.map && map_generation == o.map_generation && epochs == o.epochs &&
+                   nbr_stamp == o.nbr_stamp && nbr == o.nbr && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
+                   guard_scale == o.guard_scale && guard_min == o.guard_min && guard_max == o.guard_max && max_tries == o.max_tries &&
                    robust_kind == o.robust_kind && robust_k == o.robust_k && cov_on == o.cov_on && std::memcmp(cov_prm, o.cov_prm, sizeof(cov_prm)) == 0;
         }
     };
@@ -3138,6 +3136,8 @@ struct sf_icp {
         std::vector<double> inits;
         int src_set = 0;          // the source set it read, and that set's version then: a redo after a barrier timeout aligns THAT source
         uint64_t src_version = 0;
+        sf::Schedule sched;       // its launches, as enqueued (zeros: the single launch): what the drivers dispatch on and the statistics describe
+        int64_t lk_waves = 0;     // the waves of one of its two-queries-per-lane launches (freeze_learn_schedule)
     };
     // Consecutive asynchronous alignments of the launch list overlap: an alignment's last launches (frozen pairs: fourteen 16 us
     // kernels on an otherwise idle device) run under the next one's searching launches.  Two LANES take turns; each has its own
@@ -3240,11 +3240,7 @@ struct sf_icp {
     int64_t nbr_stats_first = 0;    // nn_stats slot of the last alignment's first launch (sf_icp_neighbour_stats)
     uint64_t mark_nbr_stamp = 0;
     int defer = 1;                  // sf_icp_set_defer_search: the verifying launches of the frozen-pairs schedule list their stragglers for a dense pass (k_nn_red_df)
-    bool df_planned = false;        // the last alignment's launch list held a deferring launch (fz_from as it stood THEN: a fetch may re-learn it)
-    int lk_first = -1, lk_launches = 0; // the last alignment's look-up launches (lookup_form): the first one's index and how many (sf_icp_lookup_launch_stats)
-    int64_t lk_waves = 0;           // and the waves of one of them
     int lk_min = 0;                 // no look-up launch before this index: learnt with fz_from (freeze_learn_schedule), 0 while from_launch is pinned
-    bool step_nbr = false;          // stepping: the alignment begun with first != 0 consults the neighbour table
     int64_t nn_stats_used = 0;
     static constexpr int64_t NN_STATS_CAP = 1024;
     // robust kernel of P2PLANE (sf_icp_set_robust_kernel): read at enqueue, passed to the kernels by value
@@ -3358,10 +3354,6 @@ bool tile_wanted(const sf_icp *icp, int mode)
     if (ss.qpl == 1) return false; // scans the single-launch kernels can take keep their summation order (and their launch list)
     return icp->tile_mode == 2 || ss.n * ss.batch >= TILE_AUTO_MIN_QUERIES;
 }
-
-// launches of an alignment that run tile by tile: those in which nearly every query searches -- all of them with the neighbour
-// reuse off, the first VERIFY_FROM_SEARCH with it on (afterwards whole waves certify and k_nn_red streams the cache)
-bool tile_launch(const sf_icp *icp, int k) { return icp->tile_on && (!icp->reuse || k < VERIFY_FROM_SEARCH); }
 
 // The key table of the attached index (k_order_lut_*), (re)built when the index has changed.  Enqueued on the context's stream
 // BEFORE an alignment takes a lane: the lanes order themselves behind the context's stream whenever the target changes
@@ -3673,22 +3665,51 @@ void prof_collect(sf_icp *icp)
     icp->ev_used = 0;
 }
 
-int defer_first(const sf_icp *icp, int mode);
+// cur().meta <- the schedule of the alignment being enqueued, from the configuration as it stands now: behind nbr_prepare (a table
+// moves the first deferring launch), order_queries (tile_on) and, sharded, shard_build (own_total feeds the size rule).  The drivers,
+// the graph key, the statistics and the fetch read that copy; nothing derives it a second time.  whole: enqueue_align | the stepping drivers
+void schedule_describe(sf_icp *icp, int mode, bool whole)
+{
+    const SrcSet &ss = icp->src();
+    sf::Schedule in;
+    in.mode = mode; in.K = icp->prm.num_iters; in.qpl = ss.qpl; in.sharded = icp->shard; in.whole = whole; in.reuse = icp->reuse; in.window = icp->map->window.kind;
+    in.robust = robust_on(icp, mode); in.fz_from = icp->fz_from; in.defer = icp->defer != 0; in.table = icp->nbr_active; in.nbr_from = icp->nbr_active ? icp->nbr_from : -1;
+    in.lk_min = icp->lk_min; in.tile_on = icp->tile_on;
+    // a frozen launch costs one wave's chain of round trips (16 us) + the solve, whatever the batch: for a small batch a verifying launch is cheaper (200 k-point
+    // scans, ms per alignment without / with: one scan 0.39 / 0.45, four 0.77 / 0.75, eight 1.07 / 0.97, sixteen 1.68 / 1.42); sharded: a rank's own queries count
+    in.wanted = icp->freeze == 2 || (icp->freeze == 1 && (icp->shard ? icp->own_total : ss.n * ss.batch) >= FREEZE_AUTO_MIN_QUERIES);
+    icp->cur().meta.sched = sf::make_schedule(in);
+    icp->cur().meta.lk_waves = (int64_t)ss.batch * ss.nblocks_nn * (BLK / 64);
+}
+
+// rows of 256 * (queries per lane) queries that a launch writes per scan and its solve sums
+int slab_rows(const sf_icp *icp, bool sharded, bool one_per_lane)
+{
+    if (sharded) return one_per_lane ? icp->own_nblocks * icp->src().qpl : icp->own_nblocks;
+    return one_per_lane ? icp->src().nblocks : icp->src().nblocks_nn;
+}
+
+// the statistics slot of the next profiled launch (nullptr: not profiling, or the counters are full)
+uint32_t *nn_stats_slot(sf_icp *icp)
+{
+    if (!icp->profiling || !icp->nn_stats.p || icp->nn_stats_used >= sf_icp::NN_STATS_CAP) return nullptr;
+    return icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
+}
 
 sf_icp::GraphKey graph_key_now(const sf_icp *icp, int mode)
 {
     const Lane &ln = icp->cur(); const SrcSet &ss = icp->src();
     sf_icp::GraphKey k;
-    k.mode = mode; k.iters = icp->prm.num_iters; k.batch = ss.batch; k.window = icp->map->window.kind; k.ordered = (int)icp->ordered | ((int)icp->tile_on << 1); k.reuse = (int)icp->reuse | (icp->freeze << 1) | (icp->fz_from << 3) | (icp->defer << 16);
+    k.batch = ss.batch; k.ordered = (int)icp->ordered; k.sched = ln.meta.sched;
     k.n = (mode == SF_ICP_REF_CPP && ss.batch == 1) ? -ss.n_cap : ss.n; // REF_CPP, one scan: any count of the same capacity replays
     k.map = (const void *)icp->map;
     k.map_generation = icp->map->generation;
-    if (icp->nbr_active) { k.nbr_stamp = icp->map->nbr_stamp; k.nbr = icp->map->nbr.p; k.nbr_from = icp->nbr_from; }
-    k.defer_first = defer_first(icp, mode);
+    if (icp->nbr_active) { k.nbr_stamp = icp->map->nbr_stamp; k.nbr = icp->map->nbr.p; }
     k.robust_kind = robust_on(icp, mode) ? icp->robust_kind : SF_ROBUST_NONE; k.robust_k = robust_on(icp, mode) ? icp->robust_k : 0.0; // (passed by value to the robust kernels)
     k.cov_on = icp->cov_on;
     if (icp->cov_on) { const double cp[5] = {icp->cov_arg.sensor_sigma, icp->cov_arg.thr_t, icp->cov_arg.thr_r, icp->cov_arg.infl_t, icp->cov_arg.infl_r}; std::memcpy(k.cov_prm, cp, sizeof(cp)); }
-    k.max_corr = icp->prm.max_corr; k.accept = icp->prm.accept; k.eps = icp->prm.eps + icp->fz_prm.guard_scale * 1.0e-3f + icp->fz_prm.guard_min + icp->fz_prm.guard_max + (float)icp->fz_prm.max_tries; // (the freeze parameters travel by value too)
+    k.max_corr = icp->prm.max_corr; k.accept = icp->prm.accept; k.eps = icp->prm.eps;
+    k.guard_scale = icp->fz_prm.guard_scale; k.guard_min = icp->fz_prm.guard_min; k.guard_max = icp->fz_prm.guard_max; k.max_tries = icp->fz_prm.max_tries; // (k_reduce_solve_fz takes them by value)
     const sf::DevBuf *bufs[] = {&ss.X0, &ss.X0r, &ln.X, &ln.Xq, &ln.qcache, &ln.corr, &ln.state, &ln.partials, &icp->d_box, &ss.d_boxes, &ss.n_dev,
                                 &icp->map->pts4, &icp->map->nrm4, &icp->map->cell_start, &icp->map->d_window, &ln.fz_state, &ln.fz_part, &ln.fz_cnt, &ln.fz_ids, &ln.fz_all, &ln.df_cnt, &ln.df_ids, &ln.df_part, &ln.df_stat, &ln.tseg, &ln.tile_stats, &ln.cov_part, &ln.cov_out};
     k.epochs = (uint64_t)ss.plane;
@@ -3739,7 +3760,7 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    const int nb = sharded ? (one_per_lane ? icp->own_nblocks * ss.qpl : icp->own_nblocks) : (one_per_lane ? ss.nblocks : ss.nblocks_nn);
+    const int nb = slab_rows(icp, sharded, one_per_lane);
     const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), blk(BLK); // see the XCD mapping in k_nn_red
     const float *x = queries(icp, 0), *y = queries(icp, 1), *z = queries(icp, 2);
     const IcpState *st = ln.state.as<IcpState>();
@@ -3747,8 +3768,7 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
     const float thr = o3d_thr(icp);
     hipStream_t s = icp->ctx->stream;
     ProfScope ps(icp);
-    uint32_t *stats = nullptr;
-    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
+    uint32_t *stats = nn_stats_slot(icp);
     const bool win = m->window.kind != 0;
     if (MODE == 2 && robust_on(icp, MODE)) {
         const RobustArg rk = robust_arg(icp);
@@ -3786,14 +3806,14 @@ void launch_tile_search(sf_icp *icp, bool one_per_lane)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    const int nb = one_per_lane ? ss.nblocks : ss.nblocks_nn;
+    const int nb = slab_rows(icp, false, one_per_lane);
     const float *x = queries(icp, 0), *y = queries(icp, 1), *z = queries(icp, 2);
     const IcpState *st = ln.state.as<IcpState>();
     const float thr = o3d_thr(icp);
     hipStream_t s = icp->ctx->stream;
     ProfScope ps(icp);
     unsigned long long *stats = icp->profiling ? ln.tile_stats.as<unsigned long long>() : nullptr;
-    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) icp->nn_stats_used++; // (keeps the per-launch statistics slots of k_nn_red aligned with the launch list)
+    nn_stats_slot(icp); // (keeps the per-launch statistics slots of k_nn_red aligned with the launch list)
     const unsigned tgrid = (unsigned)((icp->tiles.ntiles + 7) & ~7);
     hipLaunchKernelGGL((k_tile_search<MODE>), dim3(tgrid), dim3(sf::TILE_BLK), 0, s, m->grid, icp->tiles, x, y, z, (int)ss.n, ss.batch, st, thr, ln.tseg.as<uint32_t>(),
                        ln.qcache.as<float4>(), icp->cache_n, (int)icp->reuse, stats);
@@ -3804,20 +3824,7 @@ void launch_tile_search(sf_icp *icp, bool one_per_lane)
         hipLaunchKernelGGL((k_red_cached<MODE, SF_WIDE_QPL>), grid, blk, 0, s, x, y, z, (int)ss.n, st, thr, ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n);
 }
 
-// frozen pairs: P2PLANE launch list of wide scans with the neighbour reuse on, whole map; sharded: each rank freezes its own
-// owned queries (what it contributes to the all-reduced record is the same sum either way)
-bool freeze_on(const sf_icp *icp, int mode)
-{
-    const SrcSet &ss = icp->src();
-    // a frozen launch costs one wave's chain of round trips (16 us) + the solve, whatever the batch: for a small batch a verifying
-    // launch is cheaper than that (200 k-point scans, ms per alignment without / with: one scan 0.39 / 0.45, four 0.77 / 0.75,
-    // eight 1.07 / 0.97, sixteen 1.68 / 1.42)
-    const int64_t nq = icp->shard ? icp->own_total : ss.n * ss.batch;
-    const bool wanted = icp->freeze == 2 || (icp->freeze == 1 && nq >= FREEZE_AUTO_MIN_QUERIES);
-    return mode == SF_ICP_P2PLANE && wanted && !robust_on(icp, mode) && icp->reuse && ss.qpl == SF_WIDE_QPL && icp->map->window.kind == 0 && icp->prm.num_iters > icp->fz_from + 1 &&
-           icp->fz_from >= VERIFY_FROM_SEARCH;
-}
-
+// the buffers of the frozen-pairs schedule (Schedule::fz; sharded: what a rank contributes to the all-reduced record is the same sum either way)
 int freeze_alloc(sf_icp *icp)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
@@ -3870,39 +3877,7 @@ DeferBufs defer_bufs(sf_icp *icp)
 // Configuration alone decides, as for the table itself; without a table the schedule is what it was.
 // lk_min: like fz_from, the schedule of the NEXT alignment learns from the one fetched (freeze_learn_schedule) -- a look-up launch
 // in which many waves exceed the cap is slower than the launch it replaces, and the first look-up launch moves behind it.
-// -> the first look-up launch of the alignment, fz_from when it has none
-int lookup_first(const sf_icp *icp, int mode)
-{
-    if (!freeze_on(icp, mode) || icp->defer == 0 || icp->shard || !icp->nbr_active || icp->nbr_from < 1) return icp->fz_from;
-    return std::min(icp->fz_from, std::max(icp->nbr_from, icp->lk_min));
-}
-
-bool lookup_form(const sf_icp *icp, int mode) { return lookup_first(icp, mode) < icp->fz_from; }
-
-// the first deferring launch of the alignment; the launches from it up to fz_from - 1 defer (fz_from: none does)
-int defer_first(const sf_icp *icp, int mode)
-{
-    if (!freeze_on(icp, mode) || icp->defer == 0 || icp->shard) return icp->fz_from;
-    const int last = icp->fz_from - 1 >= VERIFY_FROM_SEARCH ? icp->fz_from - 1 : icp->fz_from; // (the deferring launch of the schedule without a table)
-    return std::min(lookup_first(icp, mode), last);
-}
-
-bool defer_now(const sf_icp *icp, int mode, int k) { return k >= defer_first(icp, mode) && k < icp->fz_from; }
-
-bool defer_planned(const sf_icp *icp, int mode) { return defer_first(icp, mode) < icp->fz_from; }
-
-// one query per lane: a wide scan's launches while nearly every query searches, unless the launch is a look-up launch
-bool one_per_lane_now(const sf_icp *icp, int mode, int k) { return mode == SF_ICP_P2PLANE && icp->src().qpl > 1 && k < VERIFY_FROM_SEARCH && !defer_now(icp, mode, k); }
-
-// what sf_icp_lookup_launch_stats reports of the alignment being enqueued
-void lookup_describe(sf_icp *icp, int mode)
-{
-    const bool on = !icp->last_fused && lookup_form(icp, mode);
-    icp->lk_first = on ? lookup_first(icp, mode) : -1;
-    icp->lk_launches = on ? icp->fz_from - icp->lk_first : 0;
-    icp->lk_waves = (int64_t)icp->src().batch * icp->src().nblocks_nn * (BLK / 64);
-}
-
+// Which launches these are: sf_schedule.hpp (Schedule::defer_first, Schedule::lookup_first).
 void launch_nn_deferred(sf_icp *icp, uint32_t *stats)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
@@ -3912,18 +3887,16 @@ void launch_nn_deferred(sf_icp *icp, uint32_t *stats)
 }
 
 // launch_nn_red<2> of a wide scan's two-queries-per-lane launch with the deferral, and its dense pass: one profiled launch
-void launch_nn_red_df(sf_icp *icp)
+void launch_nn_red_df(sf_icp *icp, int attempt_from)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
     const int nb = ss.nblocks_nn;
     const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), blk(BLK);
     ProfScope ps(icp);
-    uint32_t *stats = nullptr;
-    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) stats = icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
+    uint32_t *stats = nn_stats_slot(icp);
     hipLaunchKernelGGL((k_nn_red_df<SF_WIDE_QPL>), grid, blk, 0, icp->ctx->stream, grid_for(icp), m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(),
-                       o3d_thr(icp), ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp),
-                       lookup_form(icp, SF_ICP_P2PLANE) ? lookup_first(icp, SF_ICP_P2PLANE) : VERIFY_FROM_SEARCH);
+                       o3d_thr(icp), ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n, stats, defer_bufs(icp), attempt_from);
     launch_nn_deferred(icp, stats);
 }
 
@@ -3932,7 +3905,7 @@ void launch_nn_red_fz(sf_icp *icp, bool sharded, bool few)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     sf_map *m = icp->map;
-    const int nb = sharded ? icp->own_nblocks : ss.nblocks_nn;
+    const int nb = slab_rows(icp, sharded, false);
     const dim3 grid_full((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), grid_few((unsigned)FZ_FEW, (unsigned)ss.batch), blk(BLK);
     ProfScope ps(icp);
     FzArgs A;
@@ -3945,8 +3918,7 @@ void launch_nn_red_fz(sf_icp *icp, bool sharded, bool few)
     A.own_off = icp->own_off.as<uint32_t>();
     A.qcache = ln.qcache.as<float4>();
     A.cache_n = icp->cache_n;
-    A.stats = nullptr;
-    if (icp->profiling && icp->nn_stats.p && icp->nn_stats_used < sf_icp::NN_STATS_CAP) A.stats = icp->nn_stats.as<uint32_t>() + NN_STATS_PER * NN_STATS_SHARDS * icp->nn_stats_used++;
+    A.stats = nn_stats_slot(icp);
     A.fz = ln.fz_state.as<FreezeState>();
     A.mom_part = ln.fz_part.as<double>();
     A.act_cnt = ln.fz_cnt.as<uint32_t>();
@@ -3962,14 +3934,23 @@ void launch_nn_red_fz(sf_icp *icp, bool sharded, bool few)
     }
 }
 
-// the stepping paths (sharded loop, sf_icp_step_begin / _end): which launch of the pass this is
-bool freeze_nn_now(const sf_icp *icp, int mode) { return freeze_on(icp, mode) && icp->fz_step >= icp->fz_from; }
-bool freeze_solve_now(const sf_icp *icp, int mode) { return freeze_on(icp, mode) && icp->fz_step + 1 >= icp->fz_from; }
-int freeze_start_pass(sf_icp *icp, int mode)
+// the NN launch of a step in the form its schedule gives it: every driver's launches go through here
+template <int MODE>
+void launch_nn(sf_icp *icp, const sf::LaunchStep &step, bool sharded)
+{
+    if (step.frozen()) launch_nn_red_fz(icp, sharded, step.nn == sf::NN_FROZEN_FEW);
+    else if (step.nn == sf::NN_DEFERRING) launch_nn_red_df(icp, step.attempt_from);
+    else if (step.nn == sf::NN_TILE_SEARCH) launch_tile_search<MODE>(icp, step.one_per_lane);
+    else launch_nn_red<MODE>(icp, sharded, step.one_per_lane);
+}
+
+// the stepping paths (sharded loops, sf_icp_step_begin / _end) start or resume a pass: launch fz_step = 0 of a schedule built anew
+int step_start_pass(sf_icp *icp, int mode)
 {
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     icp->fz_step = 0;
-    if (!freeze_on(icp, mode)) return SF_OK;
+    schedule_describe(icp, mode, false);
+    if (!ln.meta.sched.fz) return SF_OK;
     SF_TRY(freeze_alloc(icp));
     hipLaunchKernelGGL(k_fz_init, dim3(nblk(ss.batch, 64)), dim3(64), 0, icp->ctx->stream, ln.fz_state.as<FreezeState>(), ss.batch, ln.df_stat.as<uint32_t>());
     return SF_OK;
@@ -4059,38 +4040,25 @@ int enqueue_align(sf_icp *icp, int mode)
     hipStream_t s = icp->ctx->stream;
     IcpState *st = ln.state.as<IcpState>();
     double *part = ln.partials.as<double>();
+    const sf::Schedule &sched = ln.meta.sched; // (REF_CPP below keeps its own list)
     const int K = icp->prm.num_iters;
     const int B = ss.batch;
     const int n = (int)ss.n;
     if (mode == SF_ICP_O3D_P2P) {
-        for (int k = 0; k <= K; ++k) {
-            if (tile_launch(icp, k)) launch_tile_search<1>(icp, false);
-            else launch_nn_red<1>(icp);
+        for (int k = 0; k < sf::launches(sched); ++k) {
+            launch_nn<1>(icp, sf::step_of(sched, k), false);
             hipLaunchKernelGGL(k_reduce_solve<1>, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks_nn, n, k, K, ss.d_boxes.as<ScanBox>());
         }
     } else if (mode == SF_ICP_P2PLANE) {
-        const bool fz = freeze_on(icp, mode);
-        if (fz) { // (buffers: freeze_alloc, before any capture)
-            hipLaunchKernelGGL(k_fz_init, dim3(nblk(B, 64)), dim3(64), 0, s, ln.fz_state.as<FreezeState>(), B, ln.df_stat.as<uint32_t>());
-        }
-        // wide scans: the first launches -- nearly every query searches -- run one query per lane (fewer registers: measured
-        // 929, 804, 508, 414 against 954, 836, 539, 439 us); from the launch in which waves start to certify whole, two
-        const bool wide = ss.qpl > 1 && !icp->shard;
-        for (int k = 0; k < K; ++k) {
-            const bool df = defer_now(icp, mode, k); // (a look-up launch of a table alignment, or the last launch before the freeze launch)
-            const bool q1 = wide && k < VERIFY_FROM_SEARCH && !df; // (the same schedule with the reuse off: it is part of the summation order, and reuse on == off bit for bit)
-            if (fz && k >= icp->fz_from) launch_nn_red_fz(icp, false, k > icp->fz_from);
-            else if (df) launch_nn_red_df(icp);
-            else if (tile_launch(icp, k)) launch_tile_search<2>(icp, q1);
-            else launch_nn_red<2>(icp, false, q1);
-            if (fz && (df || k + 1 >= icp->fz_from)) // (after a one-query-per-lane launch too: an ordinary record of twice as many rows, and the solve may ask for the freeze launch;
-                                                      // behind every deferring launch: the deferred rows are added here.  Only the solve before fz_from asks for a freeze)
-                hipLaunchKernelGGL(k_reduce_solve_fz, dim3(B), dim3(RBLK), 0, s, st, part, q1 ? ss.nblocks : ss.nblocks_nn, n, K, ss.d_boxes.as<ScanBox>(), freeze_bufs(icp, true, df),
-                                   icp->fz_prm, (int)(k + 1 >= icp->fz_from && k + 2 < K));
-            else if (q1)
-                hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks, n, k, K, ss.d_boxes.as<ScanBox>());
+        if (sched.fz) hipLaunchKernelGGL(k_fz_init, dim3(nblk(B, 64)), dim3(64), 0, s, ln.fz_state.as<FreezeState>(), B, ln.df_stat.as<uint32_t>()); // (buffers: freeze_alloc, before any capture)
+        for (int k = 0; k < sf::launches(sched); ++k) {
+            const sf::LaunchStep step = sf::step_of(sched, k);
+            const int nb = slab_rows(icp, false, step.one_per_lane);
+            launch_nn<2>(icp, step, false);
+            if (step.solve_takes_freeze_state || step.deferred_rows) // (it also adds the deferred rows, so it runs behind EVERY deferring launch; it asks from the solve before fz_from on)
+                hipLaunchKernelGGL(k_reduce_solve_fz, dim3(B), dim3(RBLK), 0, s, st, part, nb, n, K, ss.d_boxes.as<ScanBox>(), freeze_bufs(icp, true, step.deferred_rows), icp->fz_prm, step.ask_freeze);
             else
-                hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, ss.nblocks_nn, n, k, K, ss.d_boxes.as<ScanBox>());
+                hipLaunchKernelGGL(k_reduce_solve<2>, dim3(B), dim3(RBLK), 0, s, st, part, nb, n, k, K, ss.d_boxes.as<ScanBox>());
         }
     } else {
         SF_TRY(ln.X.reserve(sizeof(float) * 3 * (size_t)std::max<int64_t>(ss.plane, 1)));
@@ -4641,7 +4609,7 @@ extern "C" int sf_icp_defer_stats(sf_icp *icp, int64_t out[2])
 {
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
     out[0] = out[1] = 0;
-    if (!icp->df_planned || !icp->cur().df_stat.p) return SF_OK; // (not freeze_on() as it is NOW: sf_icp_fetch_results may have moved fz_from since)
+    if (!icp->cur().meta.sched.deferring() || !icp->cur().df_stat.p) return SF_OK; // (the schedule as enqueued: sf_icp_fetch_results may have moved fz_from since)
     uint32_t h[2] = {0u, 0u};
     SF_HIP(hipMemcpyAsync(h, icp->cur().df_stat.p, sizeof(h), hipMemcpyDeviceToHost, icp->ctx->stream));
     SF_HIP(hipStreamSynchronize(icp->ctx->stream));
@@ -4655,13 +4623,14 @@ extern "C" int sf_icp_lookup_launch_stats(sf_icp *icp, int64_t out[4])
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
     out[0] = out[1] = out[2] = 0;
     out[3] = -1;
-    if (icp->lk_launches <= 0) return SF_OK; // (as recorded when the alignment was enqueued)
+    const sf::Schedule &sched = icp->cur().meta.sched; // (as the alignment was enqueued)
+    if (sched.lookup_launches() <= 0) return SF_OK;
     int64_t df[2];
     SF_TRY(sf_icp_defer_stats(icp, df)); // with a table every deferring launch is a look-up launch
-    out[0] = icp->lk_launches;
+    out[0] = sched.lookup_launches();
     out[1] = df[0];
     out[2] = df[1];
-    out[3] = icp->lk_first;
+    out[3] = sched.lookup_first;
     return SF_OK;
 }
 
@@ -4680,25 +4649,26 @@ namespace {
 // scans froze at launch 12 and the six launches before cost more than the frozen ones saved (-8 %).  Scans that follow each
 // other converge alike, so the schedule of the NEXT alignment starts asking where this one froze: fz_from = the launch by
 // which every scan that froze had frozen, never earlier than the default; an alignment that froze nothing pushes it out of
-// reach (freeze_on), and every FZ_PROBE_EVERY-th fetched alignment starts again from the default.
+// reach (Schedule::fz needs K > fz_from + 1), and every FZ_PROBE_EVERY-th fetched alignment starts again from the default.
 constexpr int FZ_FROM_DEFAULT = 5, FZ_PROBE_EVERY = 32;
 void freeze_learn_schedule(sf_icp *icp)
 {
+    const sf::Schedule &sched = icp->cur().meta.sched; // of the alignment fetched, as it was enqueued: src() may be the next batch's by now
     if (!icp->fz_from_auto || icp->last_fused || icp->shard || icp->last_mode != SF_ICP_P2PLANE) return;
-    const int K = icp->prm.num_iters;
+    const int K = sched.K;
     if (++icp->fz_fetches >= FZ_PROBE_EVERY) { icp->fz_fetches = 0; icp->fz_from = FZ_FROM_DEFAULT; icp->lk_min = 0; return; }
-    if (!freeze_on(icp, icp->last_mode)) return; // (nothing was tried: nothing learnt)
+    if (!sched.fz) return; // (nothing was tried: nothing learnt)
     // Look-up launches (round 9): with priors decimetres off the early ones still move the pose too far for the table -- waves with
     // more than the cap left search in place after a wasted attempt, and the launch is slower than the searching launch it replaced
     // (tools/city_bench.py, 0.3 m / 1.5 degrees: launch index 2 644 -> 813 us).  A launch without capped waves gained a tenth, so
     // the form stops paying somewhere near one capped wave in six: the next alignment starts its look-up launches behind the last
     // one that had more than one in eight.  (Only later, never earlier: a launch that did not run this way counted nothing; the
     // probe above starts over.)
-    if (icp->lk_launches > 0 && icp->cur().df_stat.p) {
+    if (sched.lookup_launches() > 0 && icp->cur().df_stat.p) {
         uint32_t h[2 + DF_STAT_LAUNCHES];
         if (hipMemcpy(h, icp->cur().df_stat.p, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) { // (the stream has drained: states_to_host)
-            for (int k = icp->lk_first; k < icp->lk_first + icp->lk_launches && k < DF_STAT_LAUNCHES - 1; ++k)
-                if ((int64_t)h[2 + k] * 8 > icp->lk_waves) icp->lk_min = std::max(icp->lk_min, k + 1);
+            for (int k = sched.lookup_first; k < sched.fz_from && k < DF_STAT_LAUNCHES - 1; ++k)
+                if ((int64_t)h[2 + k] * 8 > icp->cur().meta.lk_waves) icp->lk_min = std::max(icp->lk_min, k + 1);
         }
     }
     int latest = -1, never = 0;
@@ -4739,8 +4709,9 @@ extern "C" int sf_icp_freeze_stats(sf_icp *icp, int64_t out[5])
     SF_CHECK(icp && out, SF_ERR_INVALID, "bad arguments");
     Lane &ln = icp->cur(); SrcSet &ss = icp->src();
     for (int i = 0; i < 5; ++i) out[i] = 0;
-    if (!freeze_on(icp, icp->last_mode) || icp->last_fused || !ln.fz_state.p || ss.batch <= 0) return SF_OK;
-    std::vector<FreezeState> h((size_t)ss.batch);
+    const int nb = ln.meta.valid && ln.meta.batch > 0 && !icp->shard ? ln.meta.batch : ss.batch; // (the alignment as it was enqueued, like its schedule: sf_icp_fetch_results)
+    if (!ln.meta.sched.fz || icp->last_fused || !ln.fz_state.p || nb <= 0) return SF_OK;
+    std::vector<FreezeState> h((size_t)nb);
     SF_HIP(hipMemcpyAsync(h.data(), ln.fz_state.p, sizeof(FreezeState) * h.size(), hipMemcpyDeviceToHost, icp->ctx->stream));
     SF_HIP(hipStreamSynchronize(icp->ctx->stream));
     for (const FreezeState &f : h) {
@@ -4897,6 +4868,7 @@ void lane_describe(sf_icp *icp, int mode, bool cov)
     sf_icp::LaneMeta &M = icp->cur().meta;
     M.valid = true; M.cov = cov; M.batch = icp->src().batch; M.mode = mode;
     M.inits = icp->inits; M.src_set = icp->src_set; M.src_version = icp->src_version;
+    M.sched = sf::Schedule{}; M.lk_waves = 0; // (schedule_describe, once the queries are ordered; the single launch has none)
 }
 
 // The stepping and the sharded entry points run on the context's stream in the lane at hand, without a LaneScope.  A source that
@@ -4927,8 +4899,6 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     icp->last_fused = fused_eligible(icp, mode);
     SF_TRY(order_lut_prepare(icp));
     SF_TRY(nbr_prepare(icp, mode));
-    icp->df_planned = !icp->last_fused && defer_planned(icp, mode); // (behind nbr_prepare: a table moves the first deferring launch)
-    lookup_describe(icp, mode);
     icp->nbr_stats_first = icp->nn_stats_used;
     // the launch list takes a lane (see sf_icp::Lane); the single launch, profiled runs and a count left on the device stay on the context's stream
     const bool beside = icp->unfetched; // an alignment of this object is still unfetched: this one may run beside it
@@ -4958,7 +4928,8 @@ extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
     }
     SF_TRY(order_queries(icp, mode)); // plain launches ahead of the (replayed) iteration graph
     if (mode != SF_ICP_REF_CPP) SF_TRY(reuse_reset(icp, ss.n * ss.batch));
-    if (freeze_on(icp, mode)) SF_TRY(freeze_alloc(icp));
+    schedule_describe(icp, mode, true);
+    if (ln.meta.sched.fz) SF_TRY(freeze_alloc(icp));
     // O3D_P2P / P2PLANE take the window by value (it moves with the pose: plain launches then); REF_CPP reads it from device memory
     if (icp->use_graph && !icp->profiling && (icp->map->window.kind == 0 || mode == SF_ICP_REF_CPP)) {
         if (mode == SF_ICP_REF_CPP) { // buffers must exist before capture (and before the key is formed)
@@ -5244,14 +5215,11 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
     icp->last_fused = false;
     if (first) { // (the unsharded stepping path consults the table as the launch list does: the same launches, bit for bit)
         SF_TRY(nbr_prepare(icp, mode));
-        icp->step_nbr = icp->nbr_active;
         icp->nbr_stats_first = icp->nn_stats_used;
-    }
-    icp->nbr_active = icp->step_nbr;
+    } else icp->nbr_active = ln.meta.sched.table != 0; // (as decided when the alignment began)
     icp->map->served = true;
     if (first) SF_TRY(step_adopt_source(icp)); // (sf_icp_align_group and the all-reduce form of sf_icp_align_sharded_async start here too)
     if (first == 1) lane_describe(icp, mode, false);
-    if (first) { icp->df_planned = defer_planned(icp, mode); lookup_describe(icp, mode); }
     if (first) SF_TRY(order_lut_prepare(icp));
     if (first == 1) SF_TRY(launch_state_init(icp));
     if (icp->shard) {
@@ -5260,27 +5228,19 @@ extern "C" int sf_icp_step_begin(sf_icp *icp, int mode, int first)
         SF_TRY(order_queries(icp, mode));
         SF_TRY(reuse_reset(icp, ss.n * ss.batch));
     }
-    if (first) SF_TRY(freeze_start_pass(icp, mode));
+    if (first) SF_TRY(step_start_pass(icp, mode));
     double *x = reinterpret_cast<double *>(sf_icp_exchange_ptr(icp, nullptr));
     hipStream_t s = icp->ctx->stream;
-    // wide scans: the first launches of a pass with one query per lane, as enqueue_align (rows of 256: twice as many)
-    const bool q1 = one_per_lane_now(icp, mode, icp->fz_step);
-    const int nb = icp->shard ? (q1 ? icp->own_nblocks * ss.qpl : icp->own_nblocks) : (q1 ? ss.nblocks : ss.nblocks_nn);
-    const int qpl_now = q1 ? 1 : ss.qpl;
+    const sf::LaunchStep step = sf::step_of(ln.meta.sched, icp->fz_step);
+    const int nb = slab_rows(icp, icp->shard, step.one_per_lane);
     const uint32_t *off = icp->shard ? icp->own_off.as<uint32_t>() : nullptr;
-    if (mode == SF_ICP_O3D_P2P) {
-        launch_nn_red<1>(icp, icp->shard);
-        ProfScope ps(icp, SF_PROF_REDUCE);
-        hipLaunchKernelGGL(k_reduce_only<1>, dim3(ss.batch), dim3(SBLK), 0, s, ln.state.as<IcpState>(), ln.partials.as<double>(), nb, x, off, ss.qpl, freeze_bufs(icp, false));
-    } else {
-        const bool df = mode == SF_ICP_P2PLANE && defer_now(icp, mode, icp->fz_step);
-        if (freeze_nn_now(icp, mode)) launch_nn_red_fz(icp, icp->shard, icp->fz_step > icp->fz_from);
-        else if (df) launch_nn_red_df(icp);
-        else launch_nn_red<2>(icp, icp->shard, q1);
-        ProfScope ps(icp, SF_PROF_REDUCE);
-        hipLaunchKernelGGL(k_reduce_only<2>, dim3(ss.batch), dim3(SBLK), 0, s, ln.state.as<IcpState>(), ln.partials.as<double>(), nb, x, off, qpl_now,
-                           freeze_bufs(icp, freeze_nn_now(icp, mode), df));
-    }
+    const int qpl_now = step.one_per_lane ? 1 : ss.qpl;
+    const FreezeBufs fb = freeze_bufs(icp, step.frozen(), step.deferred_rows); // (the deferred rows enter the record here: the solve behind the exchange takes the summed record alone)
+    if (mode == SF_ICP_O3D_P2P) launch_nn<1>(icp, step, icp->shard);
+    else launch_nn<2>(icp, step, icp->shard);
+    ProfScope ps(icp, SF_PROF_REDUCE);
+    if (mode == SF_ICP_O3D_P2P) hipLaunchKernelGGL(k_reduce_only<1>, dim3(ss.batch), dim3(SBLK), 0, s, ln.state.as<IcpState>(), ln.partials.as<double>(), nb, x, off, qpl_now, fb);
+    else hipLaunchKernelGGL(k_reduce_only<2>, dim3(ss.batch), dim3(SBLK), 0, s, ln.state.as<IcpState>(), ln.partials.as<double>(), nb, x, off, qpl_now, fb);
     SF_HIP(hipGetLastError());
     return SF_OK;
 }
@@ -5293,14 +5253,15 @@ extern "C" int sf_icp_step_end(sf_icp *icp, int mode, int last)
     const double *x = reinterpret_cast<const double *>(sf_icp_exchange_ptr(icp, nullptr));
     hipStream_t s = icp->ctx->stream;
     const int K = icp->prm.num_iters;
+    const sf::LaunchStep step = sf::step_of(ln.meta.sched, icp->fz_step);
     ProfScope ps(icp, SF_PROF_SOLVE);
     if (mode == SF_ICP_O3D_P2P)
         hipLaunchKernelGGL(k_solve_only<1>, dim3(nblk(ss.batch, 64)), dim3(64), 0, s, ln.state.as<IcpState>(), x, (int)ss.n, K, ss.batch, ss.d_boxes.as<ScanBox>(),
                            icp->shard ? icp->own_margin : 0.0f, (FreezeState *)nullptr, icp->fz_prm, 0);
     else
         hipLaunchKernelGGL(k_solve_only<2>, dim3(nblk(ss.batch, 64)), dim3(64), 0, s, ln.state.as<IcpState>(), x, (int)ss.n, K, ss.batch, ss.d_boxes.as<ScanBox>(),
-                           icp->shard ? icp->own_margin : 0.0f, freeze_solve_now(icp, mode) ? ln.fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm,
-                           (int)(icp->fz_step + 2 < K));
+                           icp->shard ? icp->own_margin : 0.0f, step.solve_takes_freeze_state ? ln.fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm,
+                           (int)(icp->fz_step + 2 < K)); // (step.ask_freeze wherever the solve has the state to read it with)
     icp->fz_step += 1;
     SF_HIP(hipGetLastError());
     return SF_OK;
@@ -5352,8 +5313,6 @@ __global__ void k_group_sum(GroupBufs g, int count)
     for (int m = 0; m < g.n; ++m) g.p[m][i] = s;
 }
 
-int sharded_steps(const sf_icp *icp, int mode) { return mode == SF_ICP_O3D_P2P ? icp->prm.num_iters + 1 : icp->prm.num_iters; }
-
 bool any_stale(const sf_icp *icp)
 {
     for (int b = 0; b < icp->src().batch; ++b)
@@ -5376,25 +5335,23 @@ int shard_step_p2p(sf_icp *icp, int mode, int first, const sf::P2pView &view)
     if (first) SF_TRY(order_lut_prepare(icp));
     if (first == 1) SF_TRY(launch_state_init(icp));
     if (first) SF_TRY(shard_build(icp, first == 2));
-    if (first) SF_TRY(freeze_start_pass(icp, mode));
+    if (first) SF_TRY(step_start_pass(icp, mode));
     hipStream_t s = icp->ctx->stream;
     IcpState *st = ln.state.as<IcpState>();
-    const bool q1 = mode == SF_ICP_P2PLANE && ss.qpl > 1 && icp->fz_step < VERIFY_FROM_SEARCH; // as enqueue_align: one query per lane while nearly every query searches
-    const int nb = q1 ? icp->own_nblocks * ss.qpl : icp->own_nblocks, B = ss.batch, K = icp->prm.num_iters, qpl_now = q1 ? 1 : ss.qpl;
-    const bool fz_nn = freeze_nn_now(icp, mode), fz_solve = freeze_solve_now(icp, mode);
-    if (mode == SF_ICP_O3D_P2P) launch_nn_red<1>(icp, true);
-    else if (fz_nn) launch_nn_red_fz(icp, true, icp->fz_step > icp->fz_from);
-    else launch_nn_red<2>(icp, true, q1);
+    const sf::LaunchStep step = sf::step_of(ln.meta.sched, icp->fz_step); // (a sharded schedule never defers)
+    const int nb = slab_rows(icp, true, step.one_per_lane), B = ss.batch, K = icp->prm.num_iters;
+    if (mode == SF_ICP_O3D_P2P) launch_nn<1>(icp, step, true);
+    else launch_nn<2>(icp, step, true);
     {
         ProfScope ps(icp, SF_PROF_REDUCE);
         if (mode == SF_ICP_O3D_P2P) hipLaunchKernelGGL(k_reduce_publish<1>, dim3(B), dim3(SBLK), 0, s, st, ln.partials.as<double>(), nb, icp->own_off.as<uint32_t>(), ss.qpl, view, freeze_bufs(icp, false));
-        else hipLaunchKernelGGL(k_reduce_publish<2>, dim3(B), dim3(SBLK), 0, s, st, ln.partials.as<double>(), nb, icp->own_off.as<uint32_t>(), qpl_now, view, freeze_bufs(icp, fz_nn));
+        else hipLaunchKernelGGL(k_reduce_publish<2>, dim3(B), dim3(SBLK), 0, s, st, ln.partials.as<double>(), nb, icp->own_off.as<uint32_t>(), step.one_per_lane ? 1 : ss.qpl, view, freeze_bufs(icp, step.frozen()));
     }
     {
         ProfScope ps(icp, SF_PROF_COLLECTIVE); // the wait for the peers' records AND the solve
         if (mode == SF_ICP_O3D_P2P) hipLaunchKernelGGL(k_gather_solve<1>, dim3(B), dim3(64), 0, s, st, (int)ss.n, K, ss.d_boxes.as<ScanBox>(), icp->own_margin, view, (FreezeState *)nullptr, icp->fz_prm, 0);
         else hipLaunchKernelGGL(k_gather_solve<2>, dim3(B), dim3(64), 0, s, st, (int)ss.n, K, ss.d_boxes.as<ScanBox>(), icp->own_margin, view,
-                                fz_solve ? ln.fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm, (int)(icp->fz_step + 2 < K));
+                                step.solve_takes_freeze_state ? ln.fz_state.as<FreezeState>() : (FreezeState *)nullptr, icp->fz_prm, (int)(icp->fz_step + 2 < K)); // (as sf_icp_step_end)
     }
     icp->fz_step += 1;
     SF_HIP(hipGetLastError());
@@ -5411,7 +5368,7 @@ extern "C" int sf_icp_align_sharded_async(sf_icp *icp, int mode, sf_comm *comm, 
     SF_CHECK(!icp->cov_on, SF_ERR_STATE, COV_DECLINE_MSG);
     SF_HIP(hipSetDevice(icp->ctx->device));
     SF_TRY(step_adopt_source(icp)); // (before the exchange is sized: shard_step_p2p does not pass sf_icp_step_begin)
-    const int steps = sharded_steps(icp, mode);
+    const int steps = sf::launches(mode, icp->prm.num_iters);
     int rc = SF_OK;
     for (int k = 0; k < steps && rc == SF_OK; ++k) {
         sf::P2pView view;
@@ -5443,7 +5400,7 @@ extern "C" int sf_icp_align_sharded(sf_icp *icp, int mode, sf_comm *comm, sf_icp
     SF_CHECK(out, SF_ERR_INVALID, "out is NULL");
     int first = 1, n_resume = 0;
     if (icp) {
-        const int steps = sharded_steps(icp, mode);
+        const int steps = sf::launches(mode, icp->prm.num_iters);
         for (int attempt = 0; attempt <= steps + 1; ++attempt) { // every resume completes at least one iteration
             SF_TRY(sf_icp_align_sharded_async(icp, mode, comm, first));
             SF_TRY(fetch_states(icp));
@@ -5479,7 +5436,7 @@ extern "C" int sf_icp_align_group(sf_icp **members, int n, int mode, sf_icp_resu
                  SF_ERR_INVALID, "member %d does not match member 0 (context, batch, points per scan, iterations)", m);
     }
     sf_icp *lead = members[0];
-    const int steps = sharded_steps(lead, mode), count = REC_STRIDE * lead->src().batch;
+    const int steps = sf::launches(mode, lead->prm.num_iters), count = REC_STRIDE * lead->src().batch;
     hipStream_t s = lead->ctx->stream;
     int first = 1, n_resume = 0;
     for (int attempt = 0; attempt <= steps + 1; ++attempt) {

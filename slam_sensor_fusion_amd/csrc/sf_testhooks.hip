@@ -3,6 +3,7 @@
 // pcl::VoxelGrid (global_map_frames_manager.cpp:142-146).  The hooks launch exactly sf::radix_sort_pairs<K> /
 // sf::scan_u32<OP> on the context's stream -- no copy of the kernels, no second implementation -- so that a test can
 // compare them with numpy at the sizes, key distributions and pointer alignments the entry points never produce.
+// And the launch schedule of an alignment (sf_schedule.hpp), evaluated on the host alone: sf_test_launch_schedule.
 //
 // Every device array of a run is carved from ONE allocation as [guard | lead | n elements | guard]: a guard is
 // GUARD elements, the front one ends on a 16-byte boundary, `lead` elements displace the first element from it (the
@@ -12,6 +13,7 @@
 #include "sf_common.hpp"
 
 #include "sf_sort.hpp"
+#include "sf_schedule.hpp"
 
 namespace {
 
@@ -102,6 +104,25 @@ extern "C" int sf_test_radix_sort(sf_ctx *ctx, int key_bytes, const void *keys, 
     SF_HIP(hipSetDevice(ctx->device));
     if (key_bytes == 4) return run_sort<uint32_t>(ctx, keys, vals, n, end_bit, lead, lead_alt, keys_out, vals_out, guard_damage);
     return run_sort<uint64_t>(ctx, keys, vals, n, end_bit, lead, lead_alt, keys_out, vals_out, guard_damage);
+}
+
+// the launch schedule (sf_schedule.hpp) row by row: host code alone, no context and no device
+extern "C" int sf_test_launch_schedule(const int32_t *in, int64_t rows, int k, int32_t *out)
+{
+    SF_CHECK((in && out) || rows == 0, SF_ERR_INVALID, "sf_test_launch_schedule: in or out is NULL");
+    SF_CHECK(rows >= 0, SF_ERR_INVALID, "sf_test_launch_schedule: rows %lld < 0", (long long)rows);
+    for (int64_t r = 0; r < rows; ++r) {
+        const int32_t *v = in + r * SF_TEST_SCHEDULE_IN;
+        sf::Schedule s;
+        s.mode = v[0]; s.K = v[1]; s.qpl = v[2]; s.sharded = v[3]; s.whole = v[4]; s.reuse = v[5]; s.window = v[6]; s.robust = v[7]; s.wanted = v[8]; s.fz_from = v[9];
+        s.defer = v[10]; s.table = v[11]; s.nbr_from = v[12]; s.lk_min = v[13]; s.tile_on = v[14];
+        s = sf::make_schedule(s);
+        const sf::LaunchStep st = sf::step_of(s, k);
+        const int32_t o[SF_TEST_SCHEDULE_OUT] = {sf::launches(s), st.nn, st.one_per_lane, st.solve_takes_freeze_state, st.ask_freeze, st.deferred_rows, st.attempt_from,
+                                                 s.fz, s.lookup_first, s.defer_first};
+        std::memcpy(out + r * SF_TEST_SCHEDULE_OUT, o, sizeof(o));
+    }
+    return SF_OK;
 }
 
 extern "C" int sf_test_scan_u32(sf_ctx *ctx, int op, const uint32_t *in, int64_t n, uint32_t carry0, int in_place, uint32_t *out, int64_t *guard_damage)

@@ -1,4 +1,4 @@
-"""Look-up launches (sf_icp_lookup_launch_stats; lookup_form / defer_first in sf_icp.hip): an alignment on the frozen-pairs
+"""Look-up launches (sf_icp_lookup_launch_stats; Schedule::lookup_first / defer_first in csrc/sf_schedule.hpp): an alignment on the frozen-pairs
 schedule that consults the map's neighbour table runs every launch from the first that consults it (sf_icp_set_neighbour_research,
 default 2) up to the launch before from_launch (sf_icp_set_freeze_params, default 5) through k_nn_red_df -- two queries per lane,
 certificate, nearest gap and table first, what they leave to the dense pass k_nn_deferred -- instead of the one-query-per-lane
@@ -271,3 +271,109 @@ def test_the_next_alignment_starts_its_look_up_launches_behind_the_capped_ones(a
         else:
             assert lk2["first"] == -1 or lk2["first"] > 2
             same_result(first, second)
+
+
+# ---------------------------------------------------------------- the schedule as a value (csrc/sf_schedule.hpp)
+def old_key_sum(eps, guard_scale=8.0, guard_min=2.0e-5, guard_max=3.0e-4, max_tries=3):
+    """the one float into which the captured graph's key used to fold the by-value parameters, in float32 as the library added them"""
+    f = np.float32
+    return f(f(f(f(f(eps) + f(f(guard_scale) * f(1.0e-3))) + f(guard_min)) + f(guard_max)) + f(max_tries))
+
+
+def test_a_replay_never_outlives_the_transformation_epsilon(api, ctx, synth, world):
+    """REF_CPP: k_ref_decide takes IcpParams by value inside the captured list.  1e-8 and 1e-7 are one float32 once 3.008 is added."""
+    assert old_key_sum(1e-8) == old_key_sum(1e-7)
+    scan = synth.make_scan(world["map"], 5_000, scan_id=77)[0]
+
+    def new_icp(eps):
+        icp = api.Icp(ctx, 0.5, 30, 1e-4, eps)
+        icp.set_target(world["never"])
+        icp.use_graph(True)
+        icp.set_fused(False)
+        icp.set_source(scan)
+        return icp
+    icp = new_icp(1e-8)
+    before = icp.align("ref_cpp")
+    assert icp.graph_counts()[0] == 1
+    icp.set_transformation_epsilon(1e-7)
+    after = icp.align("ref_cpp")
+    captures = icp.graph_counts()[0]
+    icp.close()
+    fresh = new_icp(1e-7)
+    want = fresh.align("ref_cpp")
+    fresh.close()
+    print("iterations at 1e-8: %d, at 1e-7: %d (fresh object %d); captures %d" % (before["iterations"], after["iterations"], want["iterations"], captures))
+    assert captures == 2
+    bitwise([after], [want])
+    assert after["flags"] == want["flags"] and after["converged"] == want["converged"]
+
+
+def test_a_replay_never_outlives_the_freeze_parameters(api, ctx, world):
+    """P2PLANE, frozen pairs: k_reduce_solve_fz takes FreezeParams by value.  (2e-5, 3e-4) and (1.2e-4, 2e-4) have one float32 sum."""
+    a, b = dict(guard_min=2e-5, guard_max=3e-4, from_launch=5), dict(guard_min=1.2e-4, guard_max=2e-4, from_launch=5)
+    assert old_key_sum(1e-5, guard_min=a["guard_min"], guard_max=a["guard_max"]) == old_key_sum(1e-5, guard_min=b["guard_min"], guard_max=b["guard_max"])
+    icp = make_icp(api, ctx, world["never"], world["scans"], world["inits"], graph=True, params=a)
+    icp.align_batch("p2plane")
+    assert icp.graph_counts()[0] == 1
+    icp.set_freeze_params(**b)
+    after = icp.align_batch("p2plane")
+    captures, fz = icp.graph_counts()[0], icp.freeze_stats()
+    icp.close()
+    want = run(api, ctx, world["never"], world["scans"], world["inits"], graph=True, params=b)
+    print("captures", captures, "freeze", fz, "fresh object", want["fz"])
+    assert captures == 2
+    bitwise(after, want["res"])
+    assert fz == want["fz"] and [r["flags"] for r in after] == [r["flags"] for r in want["res"]]
+
+
+@pytest.mark.parametrize("iters", [6, 20])
+@pytest.mark.parametrize("table", ["never", "always"])
+@pytest.mark.parametrize("defer", [True, False])
+@pytest.mark.parametrize("research", [-1, 1, 2, 3])
+@pytest.mark.parametrize("from_launch", [4, 5, 7])
+def test_stepping_equals_one_shot_over_the_corners_of_the_schedule(api, ctx, world, from_launch, research, defer, table, iters):
+    """the launch list and sf_icp_step_begin / _end read one schedule: the same launches, bit for bit, and the same account of them
+    (tile search off: the stepping drivers have no tile form)"""
+    out = []
+    for stepped in (False, True):
+        icp = make_icp(api, ctx, world[table], world["scans"], world["inits"], iters=iters, research=research, params=dict(from_launch=from_launch))
+        icp.set_defer_search(defer)
+        icp.set_tile_search(False)
+        if stepped:
+            for k in range(iters):
+                icp.step_begin("p2plane", first=1 if k == 0 else 0)
+                icp.step_end("p2plane", last=(k == iters - 1))
+            res = icp.fetch_results()
+        else:
+            res = icp.align_batch("p2plane")
+        out.append(dict(res=res, df=icp.defer_stats(), lk=icp.lookup_launch_stats(), fz=icp.freeze_stats()))
+        icp.close()
+    one, stepped = out
+    print("lookup", one["lk"], "defer", one["df"], "freeze", one["fz"])
+    bitwise(one["res"], stepped["res"])
+    assert [r["flags"] for r in one["res"]] == [r["flags"] for r in stepped["res"]]
+    assert one["df"] == stepped["df"] and one["lk"] == stepped["lk"] and one["fz"] == stepped["fz"]
+
+
+def test_the_statistics_describe_the_alignment_that_was_enqueued(api, ctx, world):
+    """two lanes: the next batch's source (another batch size: one scan) goes ahead into the other source set while the alignment is
+    unfetched -- its statistics stay those of its own schedule, and the next alignment is what it is alone"""
+    prm = dict(from_launch=5)   # (pinned: the next alignment does not start from a schedule learnt here)
+    alone = run(api, ctx, world["always"], world["scans"], world["inits"], params=prm)
+    next_alone = run(api, ctx, world["always"], world["scans"][:1], world["inits"][:1], params=prm)
+    icp = make_icp(api, ctx, world["always"], world["scans"], world["inits"], params=prm)
+    icp.set_pipeline(True)
+    icp.align_batch_async("p2plane")
+    icp.set_source_batch(world["scans"][:1])
+    icp.set_initial_batch(world["inits"][:1])
+    res = icp.fetch_results()
+    got = dict(df=icp.defer_stats(), lk=icp.lookup_launch_stats(), fz=icp.freeze_stats())
+    nxt = icp.align_batch("p2plane")
+    got_next = dict(df=icp.defer_stats(), lk=icp.lookup_launch_stats(), fz=icp.freeze_stats())
+    icp.close()
+    print("enqueued", got, "| next", got_next)
+    assert len(res) == 3 and alone["lk"]["launches"] == 3
+    bitwise(res, alone["res"])
+    assert got["df"] == alone["df"] and got["lk"] == alone["lk"] and got["fz"] == alone["fz"]
+    bitwise(nxt, next_alone["res"])
+    assert got_next == {k: next_alone[k] for k in ("df", "lk", "fz")}
