@@ -239,12 +239,30 @@ def voxel_merge_min_points(n=-1):
     return int(load_library().sf_cloud_voxel_merge_min_points(C.c_int64(n)))
 
 
+def kernel_sources():
+    """sf_icp.hip and every file of csrc/ it reaches through #include "..." lines (followed through the files found), sorted
+    by name: what the translation unit of the dominant kernel is compiled from.  A quoted name that is no file of csrc/ is
+    passed over (the public header lives in include/); tests/test_schedule_rule.py holds the result against the compiler's own list."""
+    import re
+    csrc = os.path.join(_HERE, "csrc")
+    found, todo = set(), ["sf_icp.hip"]
+    while todo:
+        name = todo.pop()
+        if name in found or not os.path.isfile(os.path.join(csrc, name)):
+            continue
+        found.add(name)
+        with open(os.path.join(csrc, name), "r", encoding="utf-8", errors="replace") as f:
+            todo += re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', f.read(), re.M)
+    return sorted(found)
+
+
 def kernel_source_hash():
-    """sha256[:16] of the sources the dominant kernel (k_nn_red / k_ref_nn) is compiled from.  profiles/*_traffic.json
-    carry the hash of the build their counters were taken on; bench.py only quotes them while it still matches."""
+    """sha256[:16] of the sources the dominant kernel (k_nn_red / k_ref_nn) is compiled from (kernel_sources).
+    profiles/*_traffic.json carry the hash of the build their counters were taken on; bench.py only quotes them while it
+    still matches."""
     import hashlib
     h = hashlib.sha256()
-    for name in ("sf_icp.hip", "sf_nn_red_body.inc", "sf_nn.hpp", "sf_tile.hpp", "sf_order.hpp", "sf_common.hpp", "sf_schedule.hpp"):
+    for name in kernel_sources():
         with open(os.path.join(_HERE, "csrc", name), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

@@ -38,6 +38,7 @@
 #include <vector>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 namespace {
 
@@ -3056,576 +3057,11 @@ __global__ __launch_bounds__(BLK) void k_icp_fused_rob(SfGrid g, SfWindow w, con
 } // namespace
 
 // ==================================================================== host side
-struct sf_icp {
-    sf_ctx *ctx = nullptr;
-    IcpParams prm{};
-    int debug = 0;
-    int64_t cache_n = 0;     // entries per array of the lane's qcache
-    bool reuse = true;       // sf_icp_set_nn_reuse
-    int order = SF_ORDER_AUTO;
-    bool ordered = false;    // this alignment reads Xq
-    std::vector<double> inits; // batch * 16
-    double *h_inits = nullptr;          // pinned staging of the batch's initial transforms
-    size_t h_inits_cap = 0;
-    hipEvent_t inits_ev = nullptr;      // recorded after the staging buffer's last copy
-    bool inits_ev_pending = false;
-    // target
-    sf_map *map = nullptr;
-    sf_map *own_map = nullptr;
-    sf_cloud *own_cloud = nullptr;
-    // device state
-    sf::DevBuf xchg_own;
-    void *xchg = nullptr;
-    int64_t xchg_bytes = 0;
-    int64_t wide_from = WIDE_SCAN_POINTS; // sf_icp_set_wide_scan_points: scans above this many points take two queries per lane (and may freeze)
-    bool wide_auto = true;   // no explicit limit: scans above WIDE_AUTO_POINTS are wide too when the batch is beyond every single-launch kernel (set_source_common)
-    std::vector<IcpState> h_state;
-    // sharding
-    bool shard = false;
-    float xlo = 0, xhi = 0;
-    sf::DevBuf own_idx, own_blk, own_count, own_off, own_keep; // sharded path: owned-query compaction (own_keep: the screening ballots, 1 bit per point)
-    std::vector<uint32_t> h_own;                      // host copy of counts / offsets
-    int64_t own_total = 0;                            // owned-query candidates of this rank (all scans)
-    float own_margin = 1.0f;                          // sf_icp_set_shard_margin
-    int own_nblocks = 1;                              // workgroups per scan on the sharded path (largest scan)
-    sf::DevBuf d_box;                        // sf::MinMaxDev: bounding box of the source batch (finite points), left on the device
-    int last_mode = 0;
-    // REF_CPP in one launch (k_ref_fused)
-    bool fused = true;       // sf_icp_set_fused
-    bool last_fused = false; // the last alignment ran as the single launch
-    sf::DevBuf bar;          // per scan: {arrival counter, departure counter} of the grid barrier
-    int fused_limit[4] = {-1, -1, -1, -1}; // per mode, [3] P2PLANE under a robust kernel: workgroups that are certainly resident together (-1: not asked yet)
-    double fused_share = 0.0; // share of the device the single-launch grid in flight holds in the ledger (0: none)
-    int64_t fused_redone = 0; // alignments redone through the launch list after a barrier gave up
-    bool inject_timeout = false; // test hook (sf_icp_test_inject_barrier_timeout): treat the next single-launch alignment as timed out
-    int64_t fused_launches = 0;
-    IcpState *h_pin = nullptr; // pinned, device-visible: the single-launch forms write the final states here themselves (no copy back)
-    size_t h_pin_cap = 0;
-    // graph
-    bool use_graph = false;
-    int64_t graph_captures = 0, graph_replays = 0; // sf_icp_graph_counts
-    // everything a captured launch list bakes in: kernel arguments passed by value (thresholds, IcpParams, the
-    // SfGrid geometry and pointers) and the addresses of this object's buffers.  A replay is only valid while all of
-    // it is unchanged; sf_map stamps every build / normals pass with a process-unique generation, DevBuf counts its
-    // reallocations (epoch).
-    struct GraphKey {
-        int batch = -1, ordered = -1, robust_kind = -1, cov_on = -1;
-        sf::Schedule sched; // which launches the list holds (mode, iterations, window kind and reuse are fields of it)
-        int64_t n = -1;
-        const void *map = nullptr;
-        uint64_t map_generation = 0, epochs = 0;
-        uint64_t nbr_stamp = 0; // the neighbour table this alignment consults (0: none) and its address (the first launch that does: sched.nbr_from)
-        const void *nbr = nullptr;
-        float max_corr = 0, accept = 0, eps = 0, guard_scale = 0, guard_min = 0, guard_max = 0; // IcpParams and FreezeParams as the kernels take them: by value, each field itself
-        int max_tries = 0;
-        double robust_k = 0;
-        double cov_prm[5] = {0, 0, 0, 0, 0};
-        bool operator==(const GraphKey &o) const
-        {
-            return batch == o.batch && ordered == o.ordered && sched == o.sched && n == o.n && map == o.map && map_generation == o.map_generation && epochs == o.epochs &&
-                   nbr_stamp == o.nbr_stamp && nbr == o.nbr && max_corr == o.max_corr && accept == o.accept && eps == o.eps &&
-                   guard_scale == o.guard_scale && guard_min == o.guard_min && guard_max == o.guard_max && max_tries == o.max_tries &&
-                   robust_kind == o.robust_kind && robust_k == o.robust_k && cov_on == o.cov_on && std::memcmp(cov_prm, o.cov_prm, sizeof(cov_prm)) == 0;
-        }
-    };
-    // what a lane's last alignment was (sf_icp_fetch_previous reads prev()'s states with prev()'s description)
-    struct LaneMeta {
-        bool valid = false;
-        bool cov = false; // it ran with the covariance switch on: cov_out of its lane holds its sf_icp_covariance entries
-        int batch = 0, mode = 0;
-        std::vector<double> inits;
-        int src_set = 0;          // the source set it read, and that set's version then: a redo after a barrier timeout aligns THAT source
-        uint64_t src_version = 0;
-        sf::Schedule sched;       // its launches, as enqueued (zeros: the single launch): what the drivers dispatch on and the statistics describe
-        int64_t lk_waves = 0;     // the waves of one of its two-queries-per-lane launches (freeze_learn_schedule)
-    };
-    // Consecutive asynchronous alignments of the launch list overlap: an alignment's last launches (frozen pairs: fourteen 16 us
-    // kernels on an otherwise idle device) run under the next one's searching launches.  Two LANES take turns; each has its own
-    // stream and its own copy of everything an alignment writes.  cur() = lanes[lane] is the lane of the latest alignment, prev()
-    // the other; taking turns is `lane ^= 1`, so a lane's allocations -- and the graph captured over them -- never move.
-    // Ordering (LaneScope): a lane starts after the context's stream as it stood when the inputs -- source, initial poses,
-    // target -- last changed, and the context's stream waits for every alignment right after it is enqueued, so whatever the caller
-    // enqueues next (a fetch, an upload, a map rebuild) is ordered behind it as before; only back-to-back alignments of unchanged
-    // inputs run side by side.  Same kernels, same data, same results (tests/test_gpu_pipeline.py).
-    struct Lane {
-        sf::DevBuf X;            // SoA: x[B*n], y[B*n], z[B*n] (REF_CPP: the moving points)
-        sf::DevBuf qcache;       // neighbour reuse, two float4 arrays of cache_n entries: (neighbour, its index), (neighbour's normal, E) -- O3D_P2P: the second array holds E alone, as floats
-        sf::DevBuf Xq, qkeys, qkeys2, qidx, qidx2; // cell-ordered copy of X0 and the sort's buffers
-        sf::DevBuf corr;         // float4 [B*n] (REF_CPP): a point's target (x, y, z, sorted position or -1 = dead)
-        sf::DevBuf state, d_inits, partials;
-        sf::DevBuf fz_state, fz_part, fz_cnt, fz_ids, fz_all; // frozen pairs (k_nn_red_fz)
-        sf::DevBuf df_cnt, df_ids, df_part, df_stat;          // deferred search (k_nn_red_df)
-        sf::DevBuf qtkey, tseg, tile_stats; // tile search: tile key of every ordered query; per (tile, scan) segment starts; counters
-        sf::DevBuf cov_part, cov_out;       // pose covariance (sf_cov.hpp): the rows and the result
-        hipGraphExec_t graph_exec = nullptr;
-        GraphKey graph_key;
-        std::vector<double> inits_uploaded; // what d_inits holds (the copy is skipped while nothing changed)
-        uint32_t d_inits_epoch = 0xffffffffu;
-        hipStream_t stream = nullptr;
-        hipEvent_t done = nullptr; // the end of the lane's last alignment, whatever stream it ran on
-        bool used = false;         // `done` has been recorded
-        // started: recorded on the lane's stream when its latest alignment begins (behind everything it waits for).  A source written
-        // ahead starts its upload behind the START of the alignment on the other lane: two uploads issued back to back -- the host
-        // fetched two results that became ready together -- would otherwise share the link, end together and let both alignments
-        // start together, a lockstep in which nothing overlaps (measured: upload + upload, then alignment + alignment, for good).
-        hipEvent_t started = nullptr;
-        bool started_rec = false;
-        LaneMeta meta;
-    } lanes[2];
-    int lane = 0;                 // index of cur()
-    Lane &cur() { return lanes[lane]; }
-    const Lane &cur() const { return lanes[lane]; }
-    Lane &prev() { return lanes[lane ^ 1]; }
-    // Two SOURCE SETS: srcs[src_set] = src() is the set at hand, the one the next alignment reads and sf_icp_set_source* writes.  A
-    // source set while an alignment of this object is still unfetched goes into the OTHER set (`src_set ^= 1` first), the one that
-    // alignment does not read, on the stream of the lane the next alignment will take, so the next batch's upload / conversion runs
-    // beside the alignment in flight instead of behind it (SrcScope).  Per set an event marks the end of the last alignment that
-    // read it; `src_ready` the end of the last upload that ran on a lane's stream.
-    struct SrcSet {
-        sf::DevBuf X0;           // SoA: x[B*n], y[B*n], z[B*n]
-        sf::DevBuf X0r;          // the same points as float4 records (gather source of the query ordering)
-        sf::DevBuf stage;        // persistent upload staging of sf_icp_set_source* (AoS)
-        sf::DevBuf d_boxes, d_box_parts; // ScanBox per scan (motion bound of the reuse certificate, owned-array margin), and the partial boxes of their reduction
-        sf::DevBuf n_dev;        // the point count in device memory (single-scan REF_CPP kernels read it)
-        int64_t n = 0;           // points per scan
-        int64_t n_cap = 0;       // single scan: n rounded up (launch geometry of the REF_CPP kernels)
-        int64_t plane = 0;       // component stride of the SoA arrays X0 / X / Xq
-        int batch = 0;
-        int nblocks = 0;         // workgroups of 256 points covering a scan (REF_CPP kernels, owned-query compaction)
-        int nblocks_nn = 0;      // k_nn_red workgroups per scan = slab rows (256 * qpl queries each)
-        int qpl = 1;             // queries per lane of k_nn_red: 1 up to wide_from points per scan, SF_WIDE_QPL beyond (part of the summation order)
-        bool have_source = false;
-        bool n_on_device = false; // sf_icp_set_source_scan: n is an upper bound, the count itself is in n_dev (single scan, REF_CPP)
-        hipEvent_t used = nullptr; // the end of the last alignment that read this set
-        bool used_rec = false;
-    } srcs[2];
-    int src_set = 0;              // index of src()
-    SrcSet &src() { return srcs[src_set]; }
-    const SrcSet &src() const { return srcs[src_set]; }
-    hipEvent_t src_ready = nullptr;
-    bool src_ahead = false;       // src() was written on a lane's stream (src_ready) and no alignment has been ordered behind it yet
-    hipEvent_t unmarked_ev = nullptr;
-    bool src_unmarked_use = false; // an alignment read a source set before the lanes' events existed (the per-scan path never creates them): the first source written ahead waits for the context's stream instead
-    bool prev_ok = false;         // the alignment before the latest one ran on prev() and has not been overwritten or fetched
-    std::vector<IcpState> h_prev;
-    sf::DevBuf order_lut;         // k_order_lut_*: histogram (uint32) and key table (uint16) over the walk order of the attached index
-    uint64_t order_lut_gen = 0;   // sf_map::generation the table was built for
-    int order_lut_shift = 0, order_lut_on = 1; // order_lut_on: SF_ORDER_LUT=0 in the environment switches the table off (A/B runs)
-    int pipeline = 1;             // sf_icp_set_pipeline: 0 = every alignment on the context's stream
-    hipEvent_t main_mark = nullptr;
-    bool unfetched = false;       // an alignment has been enqueued since the last fetch (the next one may run beside it)
-    bool mark_valid = false;      // main_mark stands for the inputs as described by the fields below
-    uint64_t src_version = 0, mark_src_version = 0, mark_map_generation = 0;
-    const void *mark_map = nullptr;
-    SfWindow mark_window{};
-    // profiling
-    bool profiling = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
-    int64_t prof_launches = 0;
-    double prof_ms = 0;
-    std::vector<float> prof_each;   // duration of every profiled launch, in launch order
-    std::vector<int> ev_kind;       // SF_PROF_* of every event pair
-    std::vector<float> prof_phase[SF_PROF_KINDS]; // sharded path: durations of the other phases, in order
-    sf::DevBuf nn_stats;            // per profiled k_nn_red launch: {queries that searched, waves that searched}
-    // frozen pairs (k_nn_red_fz)
-    int freeze = 1;                 // sf_icp_set_freeze: 0 off, 1 when the batch is large enough to gain (FREEZE_AUTO_MIN_QUERIES), 2 always
-    FreezeParams fz_prm{8.0f, 2.0e-5f, 3.0e-4f, 3};
-    int fz_from = 5;                // launch index of the first launch that may be a freeze launch
-    bool fz_from_auto = true;       // learnt from the last fetched alignment (sf_icp_fetch_results); sf_icp_set_freeze_params fixes it
-    int fz_fetches = 0;             // fetched alignments since fz_from was last reset to its default (every FZ_PROBE_EVERY-th starts over)
-    int fz_step = 0;                // stepping paths: launches since the pass began
-    int nbr_from = SF_NBR_FROM;     // sf_icp_set_neighbour_research: first launch index that consults the map's neighbour table (negative: off)
-    bool nbr_active = false;        // the alignment being enqueued consults it (nbr_prepare)
-    int64_t nbr_stats_first = 0;    // nn_stats slot of the last alignment's first launch (sf_icp_neighbour_stats)
-    uint64_t mark_nbr_stamp = 0;
-    int defer = 1;                  // sf_icp_set_defer_search: the verifying launches of the frozen-pairs schedule list their stragglers for a dense pass (k_nn_red_df)
-    int lk_min = 0;                 // no look-up launch before this index: learnt with fz_from (freeze_learn_schedule), 0 while from_launch is pinned
-    int64_t nn_stats_used = 0;
-    static constexpr int64_t NN_STATS_CAP = 1024;
-    // robust kernel of P2PLANE (sf_icp_set_robust_kernel): read at enqueue, passed to the kernels by value
-    int robust_kind = SF_ROBUST_NONE;
-    double robust_k = 0.0;
-    // pose covariance (sf_cov.hpp): read at enqueue, passed to the kernels by value; the rows and the result live per lane
-    int cov_on = 0;
-    CovArg cov_arg{0.0, 0.0, 0.0, 0.0, 0.0};
-    bool prev_cov_ok = false; // sf_icp_fetch_covariance_previous has something to read (set with prev_ok, cleared by its own fetch)
-    // tile search (sf_tile.hpp): the searching launches of large batches
-    int tile_mode = 0;              // sf_icp_set_tile_search: 0 off, 1 when the batch is large enough to gain (TILE_AUTO_MIN_QUERIES), 2 whenever possible
-    bool tile_on = false;           // this alignment's queries are sorted by tile and its searching launches run k_tile_search
-    sf::SfTiles tiles{};
-};
+#include "sf_icp_object.hpp"
+#include "sf_icp_order_host.hpp"
+#include "sf_icp_pipeline.hpp"
 
 namespace {
-
-using Lane = sf_icp::Lane;
-using SrcSet = sf_icp::SrcSet;
-float *soa(sf::DevBuf &b, int64_t total, int axis) { return b.as<float>() + (size_t)axis * (size_t)total; }
-// the query arrays this alignment walks: the cell-ordered copy or the scans as given
-const float *queries(sf_icp *icp, int axis)
-{
-    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
-    if (icp->shard) return soa(ln.Xq, icp->own_total, axis); // compact, cell-ordered owned queries (shard_build)
-    return soa(icp->ordered ? ln.Xq : ss.X0, ss.plane, axis);
-}
-
-int fused_capacity(sf_icp *icp, int mode, bool robust = false); // (workgroups the single-launch kernels keep resident; defined with them)
-
-// this alignment's pairs are weighted (P2PLANE only; the other modes ignore the setting)
-bool robust_on(const sf_icp *icp, int mode) { return mode == SF_ICP_P2PLANE && icp->robust_kind != SF_ROBUST_NONE; }
-RobustArg robust_arg(const sf_icp *icp) { return RobustArg{icp->robust_kind, icp->robust_k}; }
-
-// AUTO orders when there is enough work for the order to pay for the sort.  Measured, 200 k-point
-// scans, 20 iterations: 1 scan in flight +1.5 % (break-even), 2: +8 %, 4: +32 %, 32: +65 %
-constexpr int64_t ORDER_AUTO_MIN_QUERIES = 300000;
-
-// the cells the walk order (order_cell) spans, and the bits that number them
-struct OrderSpan { uint64_t cells; int bits; };
-OrderSpan order_span(const SfGrid &g)
-{
-    const uint64_t ny_pad = ((uint64_t)g.dim[1] + ORDER_YBLK - 1) / ORDER_YBLK * ORDER_YBLK; // order_cell pads y to whole blocks
-    OrderSpan sp{(uint64_t)g.dim[0] * ny_pad * (uint64_t)g.dim[2], 0};
-    while (sp.bits < 63 && (1ull << sp.bits) < sp.cells) ++sp.bits;
-    return sp;
-}
-
-// key = position of the query's cell in the walk order, shifted down to the bits the sort takes (sf::ORD_KEY_BITS)
-int order_key_shift(const SfGrid &g) { return std::max(0, order_span(g).bits - sf::ORD_KEY_BITS); }
-
-// neighbour reuse starts empty at every alignment (a zero bound certifies nothing)
-int reuse_reset(sf_icp *icp, int64_t count)
-{
-    if (!icp->reuse && !icp->tile_on) return SF_OK; // (tile launches hand their pairs to k_red_cached through the cache arrays)
-    const size_t c = (size_t)std::max<int64_t>(count, 1);
-    // nothing is cleared: a scan's entries count only once IcpState::cache_live says they have been written (every lane
-    // writes its entry in the first launch after a start or a rebuild of the owned arrays)
-    SF_TRY(icp->cur().qcache.reserve(sizeof(float4) * 2 * c));
-    icp->cache_n = (int64_t)c;
-    return SF_OK;
-}
-
-// ---- tile search: which alignments, which tiles
-// The searching launches of a batch go tile by tile when there is enough work to amortise staging every tile that holds a
-// query and the second sorting pass (measured break-even: TILE_AUTO_MIN_QUERIES), on the whole map (no window), unsharded,
-// with the queries ordered.  Tile shape: cells per axis such that the staged region (core + 2 cells all round) holds about
-// 3/4 of TILE_PCAP points at the map's mean density -- 8 x 8 x 4 cells at the metric configuration (0.25 m cells, 1.5 points
-// per cell: 12 x 12 x 8 = 1 152 staged cells, ~1 700 points) -- within the limits of the LDS tables.
-constexpr int64_t TILE_AUTO_MIN_QUERIES = 2000000;
-bool tile_plan(const SfGrid &g, sf::SfTiles *out)
-{
-    const double ncell = (double)g.dim[0] * (double)g.dim[1] * (double)g.dim[2];
-    if (g.n <= 0 || ncell <= 0) return false;
-    const double density = (double)g.n / ncell; // points per cell (empty space included: an upper-bound-free mean; denser tiles fall back one by one)
-    int tc[3] = {8, 8, 4};
-    auto region_cells = [&](const int *c) { return (double)(c[0] + 2 * sf::TILE_HALO) * (c[1] + 2 * sf::TILE_HALO) * (c[2] + 2 * sf::TILE_HALO); };
-    auto fits_tables = [&](const int *c) { return c[0] + 2 * sf::TILE_HALO <= sf::TILE_RX_MAX && (c[1] + 2 * sf::TILE_HALO) * (c[2] + 2 * sf::TILE_HALO) <= sf::TILE_ROWS_MAX; };
-    const double budget = 0.75 * sf::TILE_PCAP;
-    while (region_cells(tc) * density > budget) { // shrink the longest axis
-        int a = tc[0] >= tc[1] && tc[0] >= tc[2] ? 0 : (tc[1] >= tc[2] ? 1 : 2);
-        if (tc[a] <= 2) return false; // too dense for any tile: the global index
-        tc[a] /= 2;
-    }
-    for (;;) { // grow the shortest axis while there is room (sparse maps)
-        int a = tc[2] <= tc[1] && tc[2] <= tc[0] ? 2 : (tc[1] <= tc[0] ? 1 : 0);
-        int t2[3] = {tc[0], tc[1], tc[2]};
-        t2[a] *= 2;
-        if (!fits_tables(t2) || region_cells(t2) * density > budget) break;
-        tc[0] = t2[0]; tc[1] = t2[1]; tc[2] = t2[2];
-    }
-    if (!fits_tables(tc)) return false;
-    sf::SfTiles tl;
-    int64_t nt = 1;
-    for (int a = 0; a < 3; ++a) {
-        tl.tc[a] = tc[a];
-        tl.nt[a] = (g.dim[a] + tc[a] - 1) / tc[a];
-        nt *= tl.nt[a];
-    }
-    if (nt >= (int64_t)TILE_KEY_NONE) return false;
-    tl.ntiles = (int)nt;
-    *out = tl;
-    return true;
-}
-
-bool tile_wanted(const sf_icp *icp, int mode)
-{
-    const SrcSet &ss = icp->src();
-    // (k_red_cached sums unit weights: under a robust kernel the searching launches stay with k_nn_red_rob)
-    if (icp->tile_mode == 0 || robust_on(icp, mode) || icp->shard || icp->map->window.kind != 0 || (mode != SF_ICP_P2PLANE && mode != SF_ICP_O3D_P2P)) return false;
-    if (ss.qpl == 1) return false; // scans the single-launch kernels can take keep their summation order (and their launch list)
-    return icp->tile_mode == 2 || ss.n * ss.batch >= TILE_AUTO_MIN_QUERIES;
-}
-
-// The key table of the attached index (k_order_lut_*), (re)built when the index has changed.  Enqueued on the context's stream
-// BEFORE an alignment takes a lane: the lanes order themselves behind the context's stream whenever the target changes
-// (LaneScope), so both see the finished table.
-constexpr int ORDER_LUT_BINS = (1 << ORDER_LUT_LOG2) + 1;
-int order_lut_prepare(sf_icp *icp)
-{
-    if (!icp->order_lut_on || !icp->map || !icp->map->built) return SF_OK;
-    const SfGrid &g = icp->map->grid;
-    if (g.n <= 0 || (icp->order_lut.p && icp->order_lut_gen == icp->map->generation)) return SF_OK;
-    const OrderSpan sp = order_span(g);
-    icp->order_lut_shift = std::max(0, sp.bits - ORDER_LUT_LOG2);
-    const int nbins = (int)(sp.cells >> icp->order_lut_shift) + 1;
-    SF_TRY(icp->order_lut.reserve(sizeof(uint32_t) * (size_t)ORDER_LUT_BINS + sizeof(uint16_t) * (size_t)ORDER_LUT_BINS));
-    uint32_t *hist = icp->order_lut.as<uint32_t>();
-    uint16_t *lut = reinterpret_cast<uint16_t *>(hist + ORDER_LUT_BINS);
-    hipStream_t st = icp->ctx->stream;
-    SF_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)ORDER_LUT_BINS, st));
-    hipLaunchKernelGGL(k_order_lut_hist, dim3(nblk(g.n)), dim3(256), 0, st, g, icp->order_lut_shift, hist);
-    hipLaunchKernelGGL(k_order_lut_make, dim3(1), dim3(1024), 0, st, hist, nbins, (uint32_t)g.n, lut);
-    SF_HIP(hipGetLastError());
-    icp->order_lut_gen = icp->map->generation;
-    return SF_OK;
-}
-
-// the segmented stable bucket sort of sf_order.hpp: nseg segments (uniform: nseg scans of n queries; sharded: the
-// owned-query candidates of each scan, seg_off / src_idx on the device), `longest` = the longest segment
-int run_order_sort(sf_icp *icp, int nseg, int64_t longest, int64_t total, const uint32_t *seg_off, const uint32_t *src_idx)
-{
-    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
-    const SfGrid &g = icp->map->grid;
-    if (seg_off) icp->tile_on = false; // (the sharded path's owned-query arrays keep the cell order)
-    sf::OrderSrc src;
-    src.src_idx = src_idx;
-    src.seg_off = seg_off;
-    src.n = (int)ss.n;
-    src.tiles = (int)std::max<int64_t>(1, sf::div_up(longest, sf::ORD_TILE));
-    CellKeyFn kf;
-    kf.g = g;
-    kf.x = soa(ss.X0, ss.plane, 0); kf.y = soa(ss.X0, ss.plane, 1); kf.z = soa(ss.X0, ss.plane, 2);
-    kf.st = ln.state.as<IcpState>();
-    kf.shift = order_key_shift(g);
-    kf.lut = nullptr;
-    kf.lut_shift = 0;
-    if (icp->order_lut_on && icp->order_lut.p && icp->order_lut_gen == icp->map->generation) { // (prepared by order_lut_prepare; otherwise the plain key)
-        kf.lut = reinterpret_cast<const uint16_t *>(icp->order_lut.as<uint32_t>() + ORDER_LUT_BINS);
-        kf.lut_shift = icp->order_lut_shift;
-    }
-    const size_t cap = (size_t)std::max<int64_t>(total, 1);
-    SF_TRY(ln.Xq.reserve(sizeof(float) * 3 * std::max(cap, (size_t)(seg_off ? 0 : ss.plane))));
-    SF_TRY(ln.qkeys.reserve(sizeof(uint16_t) * cap));                                                      // bucket key of every element
-    SF_TRY(ln.qkeys2.reserve(sizeof(uint32_t) * (size_t)nseg * (size_t)(src.tiles + 1) * sf::ORD_BINS));  // per-tile bucket counts / starts
-    SF_TRY(ln.qidx.reserve(sizeof(uint32_t) * cap));                                                       // ordered query ids
-    uint16_t *keys = ln.qkeys.as<uint16_t>();
-    uint32_t *counts = ln.qkeys2.as<uint32_t>(), *ordered = ln.qidx.as<uint32_t>();
-    hipStream_t s = icp->ctx->stream;
-    src.nseg = nseg;
-    const dim3 grid(sf::order_grid(src.tiles, nseg)), blk(sf::ORD_BLK);
-    if (icp->tile_on) { // by map tile: a 20-bit key, least significant 10-bit digit first (stable passes)
-        TileKeyFn tk;
-        tk.g = g; tk.tl = icp->tiles;
-        tk.x = kf.x; tk.y = kf.y; tk.z = kf.z;
-        tk.st = kf.st; tk.n = (int)ss.n;
-        const bool two = icp->tiles.ntiles > sf::ORD_BINS;
-        uint32_t *first = ordered;
-        if (two) {
-            SF_TRY(ln.qidx2.reserve(sizeof(uint32_t) * cap));
-            first = ln.qidx2.as<uint32_t>();
-        }
-        tk.digit = 0;
-        hipLaunchKernelGGL(k_order_hist_tile, grid, blk, 0, s, src, tk, keys, counts);
-        hipLaunchKernelGGL(sf::k_order_scan, dim3((unsigned)nseg), dim3(sf::ORD_BINS), 0, s, counts, src.tiles);
-        hipLaunchKernelGGL(k_order_scatter, grid, blk, 0, s, src, keys, counts, first);
-        if (two) {
-            sf::OrderSrc src2 = src;
-            src2.src_idx = first;
-            tk.digit = 1;
-            hipLaunchKernelGGL(k_order_hist_tile, grid, blk, 0, s, src2, tk, keys, counts);
-            hipLaunchKernelGGL(sf::k_order_scan, dim3((unsigned)nseg), dim3(sf::ORD_BINS), 0, s, counts, src2.tiles);
-            hipLaunchKernelGGL(k_order_scatter, grid, blk, 0, s, src2, keys, counts, ordered);
-        }
-    } else {
-        hipLaunchKernelGGL(k_order_hist, grid, blk, 0, s, src, kf, keys, counts);
-        hipLaunchKernelGGL(sf::k_order_scan, dim3((unsigned)nseg), dim3(sf::ORD_BINS), 0, s, counts, src.tiles);
-        hipLaunchKernelGGL(k_order_scatter, grid, blk, 0, s, src, keys, counts, ordered);
-    }
-    const int64_t qplane = seg_off ? total : ss.plane; // sharded: the compact arrays have their own length
-    if (seg_off) {
-        hipLaunchKernelGGL(k_order_gather, dim3(nblk(total, GATHER_TILE)), dim3(256), 0, s, ss.X0r.as<float4>(), ordered, total, 0, 0, 0, soa(ln.Xq, qplane, 0),
-                           soa(ln.Xq, qplane, 1), soa(ln.Xq, qplane, 2));
-    } else {
-        const int gt = (int)std::max<int64_t>(1, sf::div_up(ss.n, GATHER_TILE));
-        hipLaunchKernelGGL(k_order_gather, dim3(sf::order_grid(gt, nseg)), dim3(256), 0, s, ss.X0r.as<float4>(), ordered, total, (int)ss.n, gt, nseg,
-                           soa(ln.Xq, qplane, 0), soa(ln.Xq, qplane, 1), soa(ln.Xq, qplane, 2));
-    }
-    if (icp->tile_on) { // where each tile's queries start in every scan's ordered array
-        TileKeyFn tk;
-        tk.g = g; tk.tl = icp->tiles;
-        tk.x = soa(ln.Xq, qplane, 0); tk.y = soa(ln.Xq, qplane, 1); tk.z = soa(ln.Xq, qplane, 2);
-        tk.st = kf.st; tk.n = (int)ss.n; tk.digit = 0;
-        const int64_t rows = (int64_t)icp->tiles.ntiles + 1;
-        SF_TRY(ln.qtkey.reserve(sizeof(uint32_t) * cap));
-        SF_TRY(ln.tseg.reserve(sizeof(uint32_t) * (size_t)rows * (size_t)nseg));
-        SF_TRY(ln.tile_stats.reserve(sizeof(unsigned long long) * TILE_STATS));
-        SF_HIP(hipMemsetAsync(ln.tile_stats.p, 0, sizeof(unsigned long long) * TILE_STATS, s));
-        hipLaunchKernelGGL(k_tile_keys, dim3(nblk(total)), dim3(256), 0, s, tk, total, ln.qtkey.as<uint32_t>());
-        hipLaunchKernelGGL(k_tile_starts, dim3(nblk(rows * nseg)), dim3(256), 0, s, ln.qtkey.as<uint32_t>(), (int)ss.n, nseg, icp->tiles.ntiles, ln.tseg.as<uint32_t>());
-    }
-    SF_HIP(hipGetLastError());
-    return SF_OK;
-}
-
-int order_queries(sf_icp *icp, int mode)
-{
-    SrcSet &ss = icp->src();
-    const int64_t total = ss.n * ss.batch;
-    const bool want = icp->order == SF_ORDER_CELL || (icp->order == SF_ORDER_AUTO && total >= ORDER_AUTO_MIN_QUERIES);
-    icp->ordered = false;
-    icp->tile_on = false;
-    if (!want || total == 0 || icp->map->grid.n == 0 || ss.n_on_device) return SF_OK; // (a count left on the device: the tail of the arrays is not data)
-    icp->tile_on = tile_wanted(icp, mode) && tile_plan(icp->map->grid, &icp->tiles);
-    SF_TRY(run_order_sort(icp, ss.batch, ss.n, total, nullptr, nullptr));
-    icp->ordered = true;
-    return SF_OK;
-}
-
-// the lanes' streams and every event of the pipeline, once
-int ensure_lanes(sf_icp *icp)
-{
-    for (int l = 0; l < 2; ++l) {
-        Lane &ln = icp->lanes[l];
-        if (!ln.stream) SF_HIP(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-        if (!ln.done) SF_HIP(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
-        if (!icp->srcs[l].used) SF_HIP(hipEventCreateWithFlags(&icp->srcs[l].used, hipEventDisableTiming));
-        if (!ln.started) SF_HIP(hipEventCreateWithFlags(&ln.started, hipEventDisableTiming));
-    }
-    if (!icp->main_mark) SF_HIP(hipEventCreateWithFlags(&icp->main_mark, hipEventDisableTiming));
-    if (!icp->src_ready) SF_HIP(hipEventCreateWithFlags(&icp->src_ready, hipEventDisableTiming));
-    if (!icp->unmarked_ev) SF_HIP(hipEventCreateWithFlags(&icp->unmarked_ev, hipEventDisableTiming));
-    return SF_OK;
-}
-
-// src() was written on a lane's stream and nothing has been ordered behind that upload yet: stream `s` waits for it
-int wait_src_ahead(sf_icp *icp, hipStream_t s)
-{
-    if (!icp->src_ahead) return SF_OK;
-    SF_HIP(hipStreamWaitEvent(s, icp->src_ready, 0));
-    icp->src_ahead = false;
-    return SF_OK;
-}
-
-// RAII around a call that writes the source.  While an alignment of this object is unfetched (and the lanes are on) the new
-// source goes into the OTHER source set -- the constructor flips src_set, so src() is the set being written from then on -- on
-// the stream of prev(), the lane the next alignment will take: it waits for the last alignment that read that set, not for the
-// alignment in flight.  Otherwise: the set at hand on the context's stream, as before.
-struct SrcScope {
-    sf_icp *icp;
-    hipStream_t main = nullptr;
-    bool ahead = false;
-    uint64_t version0 = 0;
-    int rc = SF_OK;
-    SrcScope(sf_icp *i, bool allowed) : icp(i), main(i->ctx->stream), version0(i->src_version)
-    {
-        static const bool ahead_on = []() { const char *e = std::getenv("SF_SRC_AHEAD"); return !e || std::atoi(e) != 0; }(); // (A/B switch)
-        const bool go = ahead_on && allowed && icp->pipeline != 0 && icp->unfetched && !icp->shard && !icp->profiling;
-        if (!go) { // the set at hand on the context's stream: behind an upload that went to a lane's stream, if there was one
-            rc = wait_src_ahead(icp, main);
-            return;
-        }
-        rc = ensure_lanes(icp);
-        if (rc != SF_OK) return;
-        if (!icp->src_ahead) icp->src_set ^= 1; // (a second source before any alignment: the same set, the same stream, again)
-        const SrcSet &ss = icp->src();
-        hipStream_t ls = icp->prev().stream;
-        if (icp->src_unmarked_use) { // readers that left no event: everything the context's stream holds
-            if (hipEventRecord(icp->unmarked_ev, main) != hipSuccess || hipStreamWaitEvent(ls, icp->unmarked_ev, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-            icp->src_unmarked_use = false;
-        }
-        if (ss.used_rec && hipStreamWaitEvent(ls, ss.used, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-        static const bool stagger_on = []() { const char *e = std::getenv("SF_UPLOAD_STAGGER"); return !e || std::atoi(e) != 0; }(); // (A/B switch)
-        if (stagger_on && icp->cur().started_rec && hipStreamWaitEvent(ls, icp->cur().started, 0) != hipSuccess) { rc = SF_ERR_HIP; return; } // see Lane::started
-        icp->ctx->stream = ls;
-        ahead = true;
-    }
-    ~SrcScope()
-    {
-        hipStream_t ran = icp->ctx->stream;
-        icp->ctx->stream = main;
-        if (!ahead) return;
-        if (hipEventRecord(icp->src_ready, ran) == hipSuccess) icp->src_ahead = true;
-        // (this source did not pass the context's stream: the mark of the inputs that did stands as it stood)
-        if (icp->mark_valid && icp->mark_src_version == version0) icp->mark_src_version = icp->src_version;
-    }
-};
-
-// what an alignment of the source at hand writes per scan, in the lane at hand
-int lane_reserve(sf_icp *icp)
-{
-    Lane &ln = icp->cur(); const SrcSet &ss = icp->src();
-    const int batch = std::max(ss.batch, 1);
-    SF_TRY(ln.state.reserve(sizeof(IcpState) * (size_t)batch));
-    SF_TRY(ln.d_inits.reserve(sizeof(double) * 16 * (size_t)batch));
-    SF_TRY(ln.partials.reserve(sizeof(double) * (size_t)REC_STRIDE * (size_t)std::max(ss.nblocks, 1) * (size_t)batch));
-    return SF_OK;
-}
-
-// outputs = false (a source written ahead of an alignment in flight): the lane's output buffers are left to lane_reserve at the next enqueue
-int icp_alloc(sf_icp *icp, int64_t n, int batch, bool outputs = true)
-{
-    Lane &ln = icp->cur(); SrcSet &ss = icp->src();
-    const int64_t total = n * batch;
-    // plane = distance between the x, y and z components of the SoA arrays: rounded up and never shrinking, so that the
-    // component pointers a captured launch list holds survive scans of slightly different sizes
-    ss.plane = std::max<int64_t>(ss.plane, sf::div_up(std::max<int64_t>(total, 1), 4096) * 4096);
-    SF_TRY(ss.X0.reserve(sizeof(float) * 3 * (size_t)ss.plane));
-    SF_TRY(ss.X0r.reserve(sizeof(float4) * (size_t)ss.plane));
-    // single scan: workgroups for the point count rounded up to 4096 (the kernels bound themselves by the count in
-    // device memory), so the launch geometry -- and with it a captured graph -- is shared by scans of similar size
-    ss.n_cap = batch == 1 ? sf::div_up(std::max<int64_t>(n, 1), 4096) * 4096 : n;
-    ss.nblocks = (int)std::max<int64_t>(1, sf::div_up(ss.n_cap, BLK));
-    // Two queries per lane are part of the summation order, so the choice must not depend on which path runs an alignment: above
-    // wide_from always; between WIDE_AUTO_POINTS and wide_from when no single-launch kernel could take the batch anyway (more
-    // rows than any of them keeps resident) -- a 64-ring sensor's 130 k points in a batch then run wide and may freeze.
-    bool wide = n > icp->wide_from;
-    if (!wide && icp->wide_auto && n > WIDE_AUTO_POINTS) {
-        const int64_t cap = std::max(fused_capacity(icp, SF_ICP_O3D_P2P), fused_capacity(icp, SF_ICP_P2PLANE));
-        wide = sf::div_up(n, BLK) * (int64_t)batch > cap;
-    }
-    ss.qpl = wide ? SF_WIDE_QPL : 1;
-    ss.nblocks_nn = (int)std::max<int64_t>(1, sf::div_up(n, BLK * ss.qpl));
-    // (set before the outputs: lane_reserve sizes them from the set, so after a failed reservation the set says n and batch as it says n_cap / nblocks / qpl; batch >= 1 from every caller, so its max(.., 1) is idle)
-    ss.n = n;
-    ss.batch = batch;
-    if (outputs) {
-        const auto e0 = ln.state.epoch;
-        SF_TRY(lane_reserve(icp));
-        if (ln.state.epoch != e0) ln.meta.valid = false; // (the states of this lane's last alignment went with the old allocation: sf_icp_fetch_previous has nothing to read)
-        SF_TRY(icp->xchg_own.reserve(sizeof(double) * REC_STRIDE * (size_t)batch));
-    }
-    if (icp->inits.size() != (size_t)batch * 16) { // (by the priors' own size, not by the batch of whichever source set was at hand)
-        icp->inits.assign((size_t)batch * 16, 0.0);
-        for (int b = 0; b < batch; ++b)
-            for (int d = 0; d < 4; ++d) icp->inits[(size_t)b * 16 + 5 * d] = 1.0;
-    }
-    icp->h_state.resize((size_t)batch);
-    return SF_OK;
-}
-
-int icp_set_source_device_aos(sf_icp *icp, const float *d_aos, int64_t n, int batch, bool ahead = false)
-{
-    SrcSet &ss = icp->src();
-    SF_TRY(icp_alloc(icp, n, batch, !ahead));
-    ss.n_on_device = false;
-    const int64_t total = n * batch;
-    if (total > 0)
-        hipLaunchKernelGGL(k_soa_from_aos, dim3(nblk(total)), dim3(256), 0, icp->ctx->stream, d_aos, total, soa(ss.X0, ss.plane, 0), soa(ss.X0, ss.plane, 1),
-                           soa(ss.X0, ss.plane, 2), ss.X0r.as<float4>());
-    SF_TRY(ss.n_dev.reserve(sizeof(int)));
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, icp->ctx->stream, ss.n_dev.as<int>(), (int)n);
-    SF_HIP(hipGetLastError());
-    // bounding box of every scan on its own, reduced on the device and left there (no host synchronisation per scan): what moves
-    // a scan's points is bounded by ITS box (a batch of 10 m scans spread over a 100 m map has a 100 m box and every rotation a
-    // 50 m lever arm).  (The box of the whole batch, which rounds 1-3 also formed here, had no reader left.)
-    SF_TRY(ss.d_boxes.reserve(sizeof(ScanBox) * (size_t)std::max(batch, 1)));
-    SF_TRY(ss.d_box_parts.reserve(sizeof(ScanBox) * BOX_PARTS * (size_t)std::max(batch, 1)));
-    hipLaunchKernelGGL(k_scan_boxes_partial, dim3(BOX_PARTS, (unsigned)std::max(batch, 1)), dim3(256), 0, icp->ctx->stream, soa(ss.X0, ss.plane, 0), soa(ss.X0, ss.plane, 1),
-                       soa(ss.X0, ss.plane, 2), (int)n, ss.d_box_parts.as<ScanBox>());
-    hipLaunchKernelGGL(k_scan_boxes_final, dim3(nblk(std::max(batch, 1), 64)), dim3(64), 0, icp->ctx->stream, ss.d_box_parts.as<ScanBox>(), std::max(batch, 1), ss.d_boxes.as<ScanBox>());
-    ss.have_source = true;
-    icp->src_version += 1;
-    return SF_OK;
-}
 
 // HIP events around a phase of the alignment on the context's stream (profiling only).  kind 0 = the NN kernel (the
 // per-launch list of sf_icp_profile_read_launches); the sharded path also times its other phases (sf_icp_profile_read_phases)
@@ -3751,6 +3187,13 @@ int nbr_prepare(sf_icp *icp, int mode)
     return SF_OK;
 }
 
+// runtime bools as template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a launch
+// site names its kernel once, k<..., A(), ...>, in a generic lambda, and every combination is instantiated
+template <bool... DONE, class F>
+void with_bools(F &&f) { f(std::bool_constant<DONE>{}...); }
+template <bool... DONE, class F, class... REST>
+void with_bools(F &&f, bool b, REST... rest) { if (b) with_bools<DONE..., true>(f, rest...); else with_bools<DONE..., false>(f, rest...); }
+
 float o3d_thr(const sf_icp *icp) { return (float)((double)icp->prm.max_corr * (double)icp->prm.max_corr); }
 
 // one_per_lane: a wide scan's launch with ONE query per lane (rows of 256 queries: icp->nblocks of them) -- the launches in
@@ -3770,33 +3213,19 @@ void launch_nn_red(sf_icp *icp, bool sharded = false, bool one_per_lane = false)
     ProfScope ps(icp);
     uint32_t *stats = nn_stats_slot(icp);
     const bool win = m->window.kind != 0;
+    const bool q1 = ss.qpl == 1 || one_per_lane;
     if (MODE == 2 && robust_on(icp, MODE)) {
         const RobustArg rk = robust_arg(icp);
-#define SF_LAUNCH_NNRED_ROB(W, S, QQ)                                                                                                                         \
-    hipLaunchKernelGGL((k_nn_red_rob<W, S, QQ>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb, \
-                       icp->own_off.as<uint32_t>(), icp->reuse ? ln.qcache.as<float4>() : nullptr, icp->cache_n, stats, rk)
-        const bool q1 = ss.qpl == 1 || one_per_lane;
-        if (win && sharded) { if (q1) SF_LAUNCH_NNRED_ROB(true, true, 1); else SF_LAUNCH_NNRED_ROB(true, true, SF_WIDE_QPL); }
-        else if (win) { if (q1) SF_LAUNCH_NNRED_ROB(true, false, 1); else SF_LAUNCH_NNRED_ROB(true, false, SF_WIDE_QPL); }
-        else if (sharded) { if (q1) SF_LAUNCH_NNRED_ROB(false, true, 1); else SF_LAUNCH_NNRED_ROB(false, true, SF_WIDE_QPL); }
-        else { if (q1) SF_LAUNCH_NNRED_ROB(false, false, 1); else SF_LAUNCH_NNRED_ROB(false, false, SF_WIDE_QPL); }
-#undef SF_LAUNCH_NNRED_ROB
+        with_bools([&](auto W, auto S, auto Q1) {
+            hipLaunchKernelGGL((k_nn_red_rob<W(), S(), Q1() ? 1 : SF_WIDE_QPL>), grid, blk, 0, s, m->grid, m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb,
+                               icp->own_off.as<uint32_t>(), icp->reuse ? ln.qcache.as<float4>() : nullptr, icp->cache_n, stats, rk);
+        }, win, sharded, q1);
         return;
     }
-#define SF_LAUNCH_NNRED_Q(W, S, QQ)                                                                                                                              \
-    hipLaunchKernelGGL((k_nn_red<MODE, W, S, QQ>), grid, blk, 0, s, grid_for(icp), m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb, \
-                       icp->own_off.as<uint32_t>(), icp->reuse ? ln.qcache.as<float4>() : nullptr, icp->cache_n, stats)
-#define SF_LAUNCH_NNRED(W, S)                                  \
-    do {                                                       \
-        if (ss.qpl == 1 || one_per_lane) SF_LAUNCH_NNRED_Q(W, S, 1); \
-        else SF_LAUNCH_NNRED_Q(W, S, SF_WIDE_QPL);             \
-    } while (0)
-    if (win && sharded) SF_LAUNCH_NNRED(true, true);
-    else if (win) SF_LAUNCH_NNRED(true, false);
-    else if (sharded) SF_LAUNCH_NNRED(false, true);
-    else SF_LAUNCH_NNRED(false, false);
-#undef SF_LAUNCH_NNRED_Q
-#undef SF_LAUNCH_NNRED
+    with_bools([&](auto W, auto S, auto Q1) {
+        hipLaunchKernelGGL((k_nn_red<MODE, W(), S(), Q1() ? 1 : SF_WIDE_QPL>), grid, blk, 0, s, grid_for(icp), m->window, x, y, z, (int)ss.n, st, thr, icp->xlo, icp->xhi, part, nb,
+                           icp->own_off.as<uint32_t>(), icp->reuse ? ln.qcache.as<float4>() : nullptr, icp->cache_n, stats);
+    }, win, sharded, q1);
 }
 
 // a searching launch tile by tile: k_tile_search leaves every query's pair in the neighbour cache, k_red_cached sums them in
@@ -3818,10 +3247,9 @@ void launch_tile_search(sf_icp *icp, bool one_per_lane)
     hipLaunchKernelGGL((k_tile_search<MODE>), dim3(tgrid), dim3(sf::TILE_BLK), 0, s, m->grid, icp->tiles, x, y, z, (int)ss.n, ss.batch, st, thr, ln.tseg.as<uint32_t>(),
                        ln.qcache.as<float4>(), icp->cache_n, (int)icp->reuse, stats);
     const dim3 grid((unsigned)((nb + 7) & ~7), (unsigned)ss.batch), blk(BLK);
-    if (ss.qpl == 1 || one_per_lane)
-        hipLaunchKernelGGL((k_red_cached<MODE, 1>), grid, blk, 0, s, x, y, z, (int)ss.n, st, thr, ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n);
-    else
-        hipLaunchKernelGGL((k_red_cached<MODE, SF_WIDE_QPL>), grid, blk, 0, s, x, y, z, (int)ss.n, st, thr, ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n);
+    with_bools([&](auto Q1) {
+        hipLaunchKernelGGL((k_red_cached<MODE, Q1() ? 1 : SF_WIDE_QPL>), grid, blk, 0, s, x, y, z, (int)ss.n, st, thr, ln.partials.as<double>(), nb, ln.qcache.as<float4>(), icp->cache_n);
+    }, ss.qpl == 1 || one_per_lane);
 }
 
 // the buffers of the frozen-pairs schedule (Schedule::fz; sharded: what a rank contributes to the all-reduced record is the same sum either way)
@@ -3925,13 +3353,9 @@ void launch_nn_red_fz(sf_icp *icp, bool sharded, bool few)
     A.act_ids = ln.fz_ids.as<uint16_t>();
     A.act_all = ln.fz_all.as<uint32_t>();
     hipStream_t s = icp->ctx->stream;
-    if (few) {
-        if (sharded) hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, true>), grid_few, blk, 0, s, grid_for(icp), m->window, A);
-        else hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, false>), grid_few, blk, 0, s, grid_for(icp), m->window, A);
-    } else {
-        if (sharded) hipLaunchKernelGGL((k_nn_red_fz<SF_WIDE_QPL, true>), grid_full, blk, 0, s, grid_for(icp), m->window, A);
-        else hipLaunchKernelGGL((k_nn_red_fz<SF_WIDE_QPL, false>), grid_full, blk, 0, s, grid_for(icp), m->window, A);
-    }
+    // (one with_bools per kernel, not `few` inside one lambda: that would interleave the two kernels' instantiations and with them their order in the device assembly)
+    if (few) with_bools([&](auto S) { hipLaunchKernelGGL((k_nn_red_fz_few<SF_WIDE_QPL, S()>), grid_few, blk, 0, s, grid_for(icp), m->window, A); }, sharded);
+    else with_bools([&](auto S) { hipLaunchKernelGGL((k_nn_red_fz<SF_WIDE_QPL, S()>), grid_full, blk, 0, s, grid_for(icp), m->window, A); }, sharded);
 }
 
 // the NN launch of a step in the form its schedule gives it: every driver's launches go through here
@@ -4018,10 +3442,9 @@ void launch_cov(sf_icp *icp, bool in_list)
     const int *nl = (MODE == 0 && B == 1) ? ss.n_dev.as<int>() : nullptr;
     const RobustArg rk = robust_on(icp, MODE) ? robust_arg(icp) : RobustArg{SF_ROBUST_NONE, 0.0};
     double *part = ln.cov_part.as<double>();
-    if (win)
-        hipLaunchKernelGGL((k_nn_cov<MODE, true>), grid, blk, 0, s, m->grid, m->window, wdev, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), thr, part, nb, rk);
-    else
-        hipLaunchKernelGGL((k_nn_cov<MODE, false>), grid, blk, 0, s, m->grid, m->window, wdev, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), thr, part, nb, rk);
+    with_bools([&](auto W) {
+        hipLaunchKernelGGL((k_nn_cov<MODE, W()>), grid, blk, 0, s, m->grid, m->window, wdev, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), thr, part, nb, rk);
+    }, win);
     hipLaunchKernelGGL(k_cov_solve<MODE>, dim3((unsigned)B), dim3(COV_SBLK), 0, s, part, nb, icp->cov_arg, ln.cov_out.as<sf_icp_covariance>());
 }
 
@@ -4068,12 +3491,12 @@ int enqueue_align(sf_icp *icp, int mode)
         const dim3 gpts((unsigned)ss.nblocks, (unsigned)B), gred((unsigned)ss.nblocks, (unsigned)B);
         const int *nl = B == 1 ? ss.n_dev.as<int>() : nullptr; // single scan: the count comes from the device (see k_ref_init)
         const bool win = m->window.kind != 0;
+        const SfWindow *wdev = win ? m->d_window.as<SfWindow>() : nullptr;
         const float thr = icp->prm.max_corr; // squared-vs-unsquared quirk, icp_point_to_point.cpp:70
         const dim3 gnn((unsigned)((ss.nblocks + 7) & ~7), (unsigned)B); // see the XCD mapping in k_ref_nn
         auto nn = [&](int force) {
             ProfScope ps(icp);
-            if (win) hipLaunchKernelGGL(k_ref_nn<true>, gnn, dim3(BLK), 0, s, m->grid, m->d_window.as<SfWindow>(), Xx, Xy, Xz, n, nl, st, thr, force, corr, ss.nblocks);
-            else hipLaunchKernelGGL(k_ref_nn<false>, gnn, dim3(BLK), 0, s, m->grid, (const SfWindow *)nullptr, Xx, Xy, Xz, n, nl, st, thr, force, corr, ss.nblocks);
+            with_bools([&](auto W) { hipLaunchKernelGGL(k_ref_nn<W()>, gnn, dim3(BLK), 0, s, m->grid, wdev, Xx, Xy, Xz, n, nl, st, thr, force, corr, ss.nblocks); }, win);
         };
         auto red = [&](int apply, int only_research) {
             hipLaunchKernelGGL(k_ref_red, gred, dim3(BLK), 0, s, Xx, Xy, Xz, n, nl, st, corr, apply, only_research, part, ss.nblocks);
@@ -4176,24 +3599,16 @@ void launch_icp_fused(sf_icp *icp, dim3 grid)
     const bool win = m->window.kind != 0;
     if (MODE == 2 && robust_on(icp, MODE)) {
         const RobustArg rk = robust_arg(icp);
-#define SF_LAUNCH_ICPF_ROB(W, R)                                                                                                                                        \
-    hipLaunchKernelGGL((k_icp_fused_rob<W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(), thr, \
-                       icp->prm.num_iters, ln.partials.as<double>(), ss.nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin, rk)
-        if (win && icp->reuse) SF_LAUNCH_ICPF_ROB(true, true);
-        else if (win) SF_LAUNCH_ICPF_ROB(true, false);
-        else if (icp->reuse) SF_LAUNCH_ICPF_ROB(false, true);
-        else SF_LAUNCH_ICPF_ROB(false, false);
-#undef SF_LAUNCH_ICPF_ROB
+        with_bools([&](auto W, auto R) {
+            hipLaunchKernelGGL((k_icp_fused_rob<W(), R()>), grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(), thr,
+                               icp->prm.num_iters, ln.partials.as<double>(), ss.nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin, rk);
+        }, win, icp->reuse);
         return;
     }
-#define SF_LAUNCH_ICPF(W, R)                                                                                                                                               \
-    hipLaunchKernelGGL((k_icp_fused<MODE, W, R>), grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(), thr, \
-                       icp->prm.num_iters, ln.partials.as<double>(), ss.nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin)
-    if (win && icp->reuse) SF_LAUNCH_ICPF(true, true);
-    else if (win) SF_LAUNCH_ICPF(true, false);
-    else if (icp->reuse) SF_LAUNCH_ICPF(false, true);
-    else SF_LAUNCH_ICPF(false, false);
-#undef SF_LAUNCH_ICPF
+    with_bools([&](auto W, auto R) {
+        hipLaunchKernelGGL((k_icp_fused<MODE, W(), R()>), grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, ln.state.as<IcpState>(), thr,
+                           icp->prm.num_iters, ln.partials.as<double>(), ss.nblocks_nn, icp->bar.as<uint32_t>(), icp->h_pin);
+    }, win, icp->reuse);
 }
 
 int launch_fused(sf_icp *icp, int mode)
@@ -4226,12 +3641,10 @@ int launch_fused(sf_icp *icp, int mode)
     const float thr = icp->prm.max_corr; // squared-vs-unsquared quirk, icp_point_to_point.cpp:70
     IcpParams prm = icp->prm;
     const int *nl = ss.n_on_device ? ss.n_dev.as<int>() : nullptr;
-    if (m->window.kind != 0)
-        hipLaunchKernelGGL(k_ref_fused<true>, grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), prm, thr,
+    with_bools([&](auto W) {
+        hipLaunchKernelGGL(k_ref_fused<W()>, grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), prm, thr,
                            ln.partials.as<double>(), ss.nblocks, icp->bar.as<uint32_t>(), icp->h_pin);
-    else
-        hipLaunchKernelGGL(k_ref_fused<false>, grid, dim3(BLK), 0, s, m->grid, m->window, queries(icp, 0), queries(icp, 1), queries(icp, 2), (int)ss.n, nl, ln.state.as<IcpState>(), prm, thr,
-                           ln.partials.as<double>(), ss.nblocks, icp->bar.as<uint32_t>(), icp->h_pin);
+    }, m->window.kind != 0);
     SF_HIP(hipGetLastError());
     icp->fused_launches += 1;
     return SF_OK;
@@ -4793,101 +4206,6 @@ extern "C" int sf_icp_use_graph(sf_icp *icp, int on)
     icp->use_graph = on != 0;
     return SF_OK;
 }
-
-namespace {
-// RAII around the enqueue of one alignment.  An alignment enqueued while an earlier one of this object has not been fetched yet
-// (back-to-back sf_icp_align_batch_async: the throughput pattern) takes the OTHER lane -- the constructor flips `lane`, so cur()
-// is the lane of this alignment from then on -- and that lane's stream; the first one after a fetch -- and every alignment of a
-// caller that fetches each result before asking for the next -- runs on the context's stream in the lane it finds, as before.
-// Per lane an event marks its last alignment, whatever stream it ran on.
-struct LaneScope {
-    sf_icp *icp;
-    hipStream_t main = nullptr;
-    bool piped = false;
-    int rc = SF_OK;
-    LaneScope(sf_icp *i, bool allowed) : icp(i), main(i->ctx->stream)
-    {
-        if (!allowed && !icp->lanes[0].done) { // the per-scan path (single launch) of an object that has never piped: no streams, no events, nothing to record
-            icp->src_unmarked_use = true;
-            return;
-        }
-        rc = ensure_lanes(icp); // (every alignment marks the end of its reading of the source set: the events must exist)
-        if (rc != SF_OK) return;
-        if (!allowed) { // the context's stream, the lane at hand -- behind a source that was written on a lane's stream, if one was
-            rc = wait_src_ahead(icp, main);
-            return;
-        }
-        // the mark: where the context's stream stood when the inputs last changed (taken before anything of this alignment is enqueued)
-        const sf_map *m = icp->map;
-        // (the initial poses are not part of it: they travel in the kernel arguments or through the lane's own copy, on the lane's stream)
-        const bool same = icp->mark_valid && icp->mark_src_version == icp->src_version && icp->mark_map == (const void *)m && icp->mark_map_generation == m->generation && icp->mark_nbr_stamp == m->nbr_stamp &&
-                          std::memcmp(&icp->mark_window, &m->window, sizeof(SfWindow)) == 0;
-        if (!same) {
-            if (hipEventRecord(icp->main_mark, main) != hipSuccess) { rc = SF_ERR_HIP; return; }
-            icp->mark_valid = true;
-            icp->mark_src_version = icp->src_version;
-            icp->mark_map = (const void *)m;
-            icp->mark_map_generation = m->generation;
-            icp->mark_nbr_stamp = m->nbr_stamp;
-            icp->mark_window = m->window;
-        }
-        if (!icp->unfetched && !icp->src_ahead) { // nothing of this object in flight: the context's stream, the lane at hand
-            if (hipEventRecord(icp->cur().started, main) == hipSuccess) icp->cur().started_rec = true;
-            return;
-        }
-        icp->lane ^= 1; // take turns (a source written ahead went to this lane's stream)
-        Lane &ln = icp->cur();
-        rc = lane_reserve(icp);
-        if (rc != SF_OK) return;
-        // after the inputs, and after this lane's previous alignment (which may have run on the context's stream)
-        if (hipStreamWaitEvent(ln.stream, icp->main_mark, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-        if (ln.used && hipStreamWaitEvent(ln.stream, ln.done, 0) != hipSuccess) { rc = SF_ERR_HIP; return; }
-        rc = wait_src_ahead(icp, ln.stream);
-        if (rc != SF_OK) return;
-        icp->ctx->stream = ln.stream;
-        piped = true;
-        if (hipEventRecord(ln.started, ln.stream) == hipSuccess) ln.started_rec = true;
-    }
-    ~LaneScope()
-    {
-        hipStream_t ran = icp->ctx->stream;
-        icp->ctx->stream = main;
-        Lane &ln = icp->cur(); SrcSet &ss = icp->src();
-        if (!ln.done) return; // (the lanes have never been set up: nothing to mark)
-        if (ss.used && hipEventRecord(ss.used, ran) == hipSuccess) ss.used_rec = true; // the last reader of this source set
-        if (hipEventRecord(ln.done, ran) != hipSuccess) return;
-        ln.used = true;
-        // whatever the caller enqueues next on the context's stream is ordered behind this alignment
-        if (piped) { hipError_t e = hipStreamWaitEvent(main, ln.done, 0); (void)e; }
-    }
-};
-
-// cur().meta <- the alignment being enqueued: sf_icp_fetch_results and a redo describe the latest alignment as it was enqueued
-void lane_describe(sf_icp *icp, int mode, bool cov)
-{
-    sf_icp::LaneMeta &M = icp->cur().meta;
-    M.valid = true; M.cov = cov; M.batch = icp->src().batch; M.mode = mode;
-    M.inits = icp->inits; M.src_set = icp->src_set; M.src_version = icp->src_version;
-    M.sched = sf::Schedule{}; M.lk_waves = 0; // (schedule_describe, once the queries are ordered; the single launch has none)
-}
-
-// The stepping and the sharded entry points run on the context's stream in the lane at hand, without a LaneScope.  A source that
-// SrcScope wrote ahead of an unfetched alignment (on a lane's stream, icp_alloc(outputs = false)) is theirs to adopt at the start of
-// an alignment: the context's stream waits for the upload, and everything an alignment writes per scan -- states, initial poses,
-// partial rows, the exchange records -- is sized for the source now at hand.  They leave no event on the source set they read: the
-// next source written ahead waits for the context's stream instead (src_unmarked_use).
-int step_adopt_source(sf_icp *icp)
-{
-    SF_TRY(wait_src_ahead(icp, icp->ctx->stream));
-    Lane &ln = icp->cur();
-    const auto e0 = ln.state.epoch;
-    SF_TRY(lane_reserve(icp));
-    if (ln.state.epoch != e0) ln.meta.valid = false; // (as icp_alloc: the states of the last alignment went with the old allocation)
-    SF_TRY(icp->xchg_own.reserve(sizeof(double) * REC_STRIDE * (size_t)std::max(icp->src().batch, 1)));
-    icp->src_unmarked_use = true;
-    return SF_OK;
-}
-} // namespace
 
 extern "C" int sf_icp_align_batch_async(sf_icp *icp, int mode)
 {

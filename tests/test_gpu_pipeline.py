@@ -188,7 +188,7 @@ def test_a_stepped_alignment_behind_a_source_set_ahead(api, ctx, synth, world):
     runs on the context's stream in the buffers at hand.  Its five results must be bitwise those of an object without the lanes
     given the same calls, and those of a fresh object that only ran the stepped alignment.
 
-    What makes it pass: step_adopt_source, called by sf_icp_step_begin when first != 0 (csrc/sf_icp.hip) -- the context's stream
+    What makes it pass: step_adopt_source, called by sf_icp_step_begin when first != 0 (csrc/sf_icp_pipeline.hpp) -- the context's stream
     waits for src_ready, and lane_reserve + the xchg_own reserve size the states, partial rows and exchange records for five
     scans.  Without it the step reads a source still uploading and writes five scans' states and records into buffers sized for
     three.  That fetch_results returns the stepped alignment's five scans (and not three, described by the asynchronous one) is the
@@ -331,7 +331,7 @@ def test_fetch_previous_across_modes_and_batch_sizes(api, ctx, synth, world):
 
 def test_a_stream_of_new_batches_equals_each_alone(api, ctx, synth, world):
     """The whole streaming loop: a NEW source batch and new priors every step, set while the previous step's alignment is in
-    flight (the upload takes the other source set on the next lane's stream, sf_icp.hip SrcScope), the previous step's results
+    flight (the upload takes the other source set on the next lane's stream, sf_icp_pipeline.hpp SrcScope), the previous step's results
     fetched while this step runs.  Every step's results are those of the same batch registered alone, bit for bit -- also when a
     step sets its source twice, changes the number of scans, or fetches in between."""
     rng = np.random.default_rng(11)

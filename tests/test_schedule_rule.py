@@ -158,6 +158,20 @@ def test_the_header_of_the_schedule_is_plain_host_code():
     assert re.findall(r'#include\s+[<"]([^>"]+)', code) == ["slamfusion.h"]
 
 
+def test_the_source_hash_reads_what_the_compiler_read(api):
+    """kernel_source_hash follows the #include "..." lines from sf_icp.hip; the dependency file the compiler wrote for that
+    translation unit (csrc/Makefile, -MMD) names what it opened.  The two sets of csrc files must be the same."""
+    csrc = os.path.join(ROOT, "slam_sensor_fusion_amd", "csrc")
+    dep = os.path.join(ROOT, "slam_sensor_fusion_amd", "lib", "obj", "sf_icp.hip.d")
+    if not os.path.isfile(dep):
+        pytest.skip("no dependency file: the library was not built by csrc/Makefile here")
+    with open(dep) as f:
+        words = f.read().replace("\\\n", " ").split()
+    named = {os.path.basename(w) for w in words if not w.endswith(":") and os.path.realpath(os.path.join(csrc, os.path.dirname(w))) == os.path.realpath(csrc)}
+    assert named == set(api.kernel_sources()), sorted(named ^ set(api.kernel_sources()))
+    assert "sf_icp.hip" in named and len(api.kernel_source_hash()) == 16
+
+
 def test_the_wrappers_keep_their_shape(api):
     import inspect
     assert list(inspect.signature(api.Icp.defer_stats).parameters) == ["self"]
