@@ -1047,6 +1047,18 @@ int sf_test_label_boxes(sf_cloud *c, const int32_t *labels, int64_t n_labels, co
 #define SF_TEST_SCHEDULE_OUT 10
 int sf_test_launch_schedule(const int32_t *in, int64_t rows, int k, int32_t *out);
 
+/* The stream compaction every crop and filter ends in, and the bounds reduction every voxel grid and grid index starts from
+ * (csrc/sf_cloud.hip), run directly on a cloud.  Both CALL the production functions -- no copy.
+ * sf_test_compact: uploads flags[n] (n = the cloud's size, host memory) into the cloud's own flag buffer, takes a new stamp as
+ *   the crops do and runs sf::compact_cloud: the points whose flag is not 0 stay, in order; read them with sf_cloud_download and
+ *   their indices with sf_cloud_last_indices.  n = 0 succeeds (flags may be NULL then).
+ * sf_test_cloud_minmax: bounds of the points whose three coordinates are finite and their number (zeros when there is none).
+ *   enqueue_form = 0: sf::cloud_minmax (the voxel grids, sf_map_build); otherwise sf::cloud_minmax_enqueue into a device buffer
+ *   of the hook's own, copied back after a stream synchronise (sf_cloud_voxel_merge, sf_map_patch).  n = 0 succeeds in both.
+ * SF_ERR_INVALID: a NULL argument that is needed. */
+int sf_test_compact(sf_cloud *c, const uint8_t *flags); /* flags: host, [n] */
+int sf_test_cloud_minmax(sf_cloud *c, int enqueue_form, float mn[3], float mx[3], int64_t *n_finite);
+
 #ifdef __cplusplus
 }
 #endif

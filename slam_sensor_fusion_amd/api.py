@@ -230,6 +230,8 @@ def load_library():
     lib.sf_cloud_cluster_boxes.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sf_cloud_remove_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p]
     lib.sf_test_launch_schedule.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -375,6 +377,24 @@ def hook_reduce_partials(ctx, nrec, nt, part):
     out = np.full(32, np.nan)
     _check(ctx.lib.sf_test_reduce_partials(ctx.h, int(nrec), int(nt), _p(part), len(part), _p(out)))
     return out
+
+
+def hook_compact(cloud, flags):
+    """Test hook (sf_test_compact): the stream compaction behind every crop and filter with flags of the caller's choosing (uint8, one
+    per point, non-zero keeps), in place.  Returns (points, kept indices)."""
+    flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    if len(flags) != len(cloud):
+        raise SlamFusionError("hook_compact: %d flags for %d points" % (len(flags), len(cloud)))
+    _check(cloud.lib.sf_test_compact(cloud.h, _p(flags) if len(flags) else None))
+    return cloud.download(), cloud.last_indices()
+
+
+def hook_cloud_minmax(cloud, enqueue=False):
+    """Test hook (sf_test_cloud_minmax): bounds of the finite points as the voxel grids take them (sf::cloud_minmax) or, enqueue=True,
+    as the merge and the patch do (sf::cloud_minmax_enqueue).  Returns (mn float32[3], mx float32[3], finite points)."""
+    mn, mx, cnt = np.full(3, np.nan, np.float32), np.full(3, np.nan, np.float32), C.c_int64(-1)
+    _check(cloud.lib.sf_test_cloud_minmax(cloud.h, int(bool(enqueue)), _p(mn), _p(mx), C.addressof(cnt)))
+    return mn, mx, cnt.value
 
 
 def _pc2_layout(msg):

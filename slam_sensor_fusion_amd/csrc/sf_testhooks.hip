@@ -4,6 +4,8 @@
 // sf::scan_u32<OP> on the context's stream -- no copy of the kernels, no second implementation -- so that a test can
 // compare them with numpy at the sizes, key distributions and pointer alignments the entry points never produce.
 // And the launch schedule of an alignment (sf_schedule.hpp), evaluated on the host alone: sf_test_launch_schedule.
+// And the stream compaction and the bounds reduction of sf_cloud.hip, run on a cloud with flags / points of the test's own
+// choosing: sf_test_compact (sf::compact_cloud), sf_test_cloud_minmax (sf::cloud_minmax, sf::cloud_minmax_enqueue).
 //
 // Every device array of a run is carved from ONE allocation as [guard | lead | n elements | guard]: a guard is
 // GUARD elements, the front one ends on a 16-byte boundary, `lead` elements displace the first element from it (the
@@ -154,5 +156,44 @@ extern "C" int sf_test_scan_u32(sf_ctx *ctx, int op, const uint32_t *in, int64_t
     for (int k = 0; k < narr; ++k) SF_TRY(count_guard_damage(ctx, base, a[k], host, &damage));
     SF_HIP(hipGetLastError());
     *guard_damage = damage;
+    return SF_OK;
+}
+
+// the compaction behind every crop and filter, with the caller's flags: what the crops do after their predicate kernel
+extern "C" int sf_test_compact(sf_cloud *c, const uint8_t *flags)
+{
+    SF_CHECK(c, SF_ERR_INVALID, "sf_test_compact: c is NULL");
+    SF_CHECK(flags || c->n == 0, SF_ERR_INVALID, "sf_test_compact: flags is NULL");
+    SF_HIP(hipSetDevice(c->ctx->device));
+    if (c->n > 0) {
+        SF_TRY(c->flags.reserve((size_t)c->n));
+        SF_TRY(sf::upload_staged(c->ctx, c->flags.p, flags, (size_t)c->n));
+    }
+    sf::cloud_touch(c);
+    return sf::compact_cloud(c, c->flags.as<uint8_t>());
+}
+
+// the bounds of the finite points in either form; the enqueue form writes into a buffer that starts as the guard pattern
+extern "C" int sf_test_cloud_minmax(sf_cloud *c, int enqueue_form, float mn[3], float mx[3], int64_t *n_finite)
+{
+    SF_CHECK(c && mn && mx && n_finite, SF_ERR_INVALID, "sf_test_cloud_minmax: a NULL argument");
+    sf_ctx *ctx = c->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    if (!enqueue_form) {
+        sf::MinMaxHost h;
+        SF_TRY(sf::cloud_minmax(ctx, c->xyz.as<float>(), c->n, &h));
+        for (int d = 0; d < 3; ++d) { mn[d] = h.mn[d]; mx[d] = h.mx[d]; }
+        *n_finite = h.n_finite;
+        return SF_OK;
+    }
+    sf::DevBuf buf; // freed on every path
+    SF_TRY(buf.reserve(sizeof(sf::MinMaxDev)));
+    SF_HIP(hipMemsetAsync(buf.p, GUARD_BYTE, sizeof(sf::MinMaxDev), ctx->stream));
+    SF_TRY(sf::cloud_minmax_enqueue(ctx, c->xyz.as<float>(), c->n, buf.as<sf::MinMaxDev>()));
+    sf::MinMaxDev h;
+    SF_HIP(hipMemcpyAsync(&h, buf.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    SF_HIP(hipStreamSynchronize(ctx->stream));
+    for (int d = 0; d < 3; ++d) { mn[d] = h.mn[d]; mx[d] = h.mx[d]; }
+    *n_finite = (int64_t)h.cnt;
     return SF_OK;
 }
