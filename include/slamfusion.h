@@ -1059,6 +1059,17 @@ int sf_test_launch_schedule(const int32_t *in, int64_t rows, int k, int32_t *out
 int sf_test_compact(sf_cloud *c, const uint8_t *flags); /* flags: host, [n] */
 int sf_test_cloud_minmax(sf_cloud *c, int enqueue_form, float mn[3], float mx[3], int64_t *n_finite);
 
+/* The query ordering that runs in front of an alignment (csrc/sf_order.hpp), run directly on host points with
+ * buffers of the hook's own: k_order_hist -> k_order_scan -> form 0: k_order_scatter + k_order_gather (ids, then the records
+ * gathered), form 1: k_order_move (ranked and moved in one pass; what an alignment's plain path runs).  The library's own path is
+ * not altered.
+ *   points [batch][n][3]: the scans; poses [batch][16]: one row-major 4x4 pose per scan (the key is the map cell of the posed
+ *   point); table != 0: the density-equalised buckets of the map's index (what an alignment uses), 0: the plain cell key.
+ *   keys [batch][n]: the 10-bit bucket of every point, in element order (1023: a non-finite posed point);
+ *   ordered [batch][n][3]: every scan stably ordered by key, the coordinates bit for bit those of `points`.
+ * SF_ERR_INVALID: a NULL argument, a map without an index, batch outside [1, 64], n outside [1, 2^20], form not 0 or 1. */
+int sf_test_query_order(sf_map *map, const float *points, int batch, int64_t n, const double *poses, int form, int table, uint16_t *keys, float *ordered);
+
 #ifdef __cplusplus
 }
 #endif

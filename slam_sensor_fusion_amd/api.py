@@ -232,6 +232,7 @@ def load_library():
     lib.sf_test_launch_schedule.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_test_query_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -395,6 +396,22 @@ def hook_cloud_minmax(cloud, enqueue=False):
     mn, mx, cnt = np.full(3, np.nan, np.float32), np.full(3, np.nan, np.float32), C.c_int64(-1)
     _check(cloud.lib.sf_test_cloud_minmax(cloud.h, int(bool(enqueue)), _p(mn), _p(mx), C.addressof(cnt)))
     return mn, mx, cnt.value
+
+
+def hook_query_order(map_, points, poses=None, form=1, table=False):
+    """Test hook (sf_test_query_order): the query ordering of an alignment on host scans points[B][n][3] under one 4x4 pose per scan
+    (default: identity), form 0 = k_order_scatter + k_order_gather, 1 = k_order_move; table: the density-equalised buckets of the
+    map's index instead of the plain cell key.  Returns (keys uint16 [B][n] in element order, ordered float32 [B][n][3])."""
+    points = _f32(points)
+    if points.ndim != 3 or points.shape[2] != 3:
+        raise SlamFusionError("hook_query_order: points must be [B][n][3], not %r" % (points.shape,))
+    batch, n = points.shape[:2]
+    poses = np.tile(np.eye(4), (batch, 1, 1)) if poses is None else _f64(poses).reshape(batch, 4, 4)
+    poses = _f64(poses)
+    keys = np.empty((batch, n), np.uint16)
+    ordered = np.empty((batch, n, 3), np.float32)
+    _check(map_.lib.sf_test_query_order(map_.h, _p(points), batch, n, _p(poses), int(form), int(bool(table)), _p(keys), _p(ordered)))
+    return keys, ordered
 
 
 def _pc2_layout(msg):

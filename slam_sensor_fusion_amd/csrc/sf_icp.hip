@@ -8,7 +8,7 @@
 //
 // Once per alignment (O3D_P2P / P2PLANE, enough work to pay for it): every scan's points are
 // ordered by the map cell they fall in under the initial pose (k_order_hist / k_order_scan /
-// k_order_scatter / k_order_gather, sf_order.hpp), so that the scans in flight walk the map together.
+// k_order_move, sf_order.hpp), so that the scans in flight walk the map together.
 // Per iteration:
 //   k_nn_red        one lane per source point: s = T*x0 (float64); the neighbour found by the
 //                   point's last search is kept when a bound proved by that search shows it
@@ -973,6 +973,15 @@ __global__ __launch_bounds__(1024) void k_order_lut_make(const uint32_t *__restr
 __global__ __launch_bounds__(sf::ORD_BLK) void k_order_scatter(sf::OrderSrc s, const uint16_t *__restrict__ keys, const uint32_t *__restrict__ starts, uint32_t *__restrict__ out)
 {
     sf::order_scatter_body(s, keys, starts, out);
+}
+
+// k_order_scatter + k_order_gather in one pass for uniform segments in element order (no src_idx, no seg_off): the SoA scans
+// X0 -> the cell-ordered SoA Xq through LDS, no ids in between (sf_order.hpp)
+__global__ __launch_bounds__(sf::ORD_BLK) void k_order_move(sf::OrderSrc s, const uint16_t *__restrict__ keys, const uint32_t *__restrict__ starts, const float *__restrict__ sx,
+                                                            const float *__restrict__ sy, const float *__restrict__ sz, float *__restrict__ dx, float *__restrict__ dy,
+                                                            float *__restrict__ dz)
+{
+    sf::order_move_body(s, keys, starts, sx, sy, sz, dx, dy, dz);
 }
 
 // the ordered ids read coalesced, the queries' float4 records gathered (four in flight per lane), the cell-ordered
@@ -4872,4 +4881,69 @@ extern "C" int sf_test_reduce_partials(sf_ctx *ctx, int nrec, int nt, const doub
     SF_CHECK(nblocks >= 0 && nblocks <= TEST_MAX_ROWS, SF_ERR_INVALID, "sf_test_reduce_partials: nblocks %d outside [0, 65536]", nblocks);
     SF_CHECK(part || nblocks == 0, SF_ERR_INVALID, "sf_test_reduce_partials: part is NULL");
     return test_reduce_partials_run(ctx, nrec, nt, part, nblocks, out);
+}
+
+// ------------------------------------------------------------------ test hook of the query order (sf_order.hpp, launch_order_plain)
+// The ordering kernels on host points: k_order_hist -> k_order_scan -> form 0: k_order_scatter + k_order_gather, form 1:
+// k_order_move, with buffers of the hook's own.  The ordered planes start as 0xff bytes: a slot no kernel wrote shows.
+extern "C" int sf_test_query_order(sf_map *map, const float *points, int batch, int64_t n, const double *poses, int form, int table, uint16_t *keys, float *ordered)
+{
+    SF_CHECK(map && points && poses && keys && ordered, SF_ERR_INVALID, "sf_test_query_order: a NULL argument");
+    SF_CHECK(map->built && map->grid.n > 0, SF_ERR_INVALID, "sf_test_query_order: the map has no index");
+    SF_CHECK(batch >= 1 && batch <= 64 && n >= 1 && n <= ((int64_t)1 << 20), SF_ERR_INVALID, "sf_test_query_order: batch %d outside [1, 64] or n %lld outside [1, 2^20]", batch,
+             (long long)n);
+    SF_CHECK(form == 0 || form == 1, SF_ERR_INVALID, "sf_test_query_order: form %d (0: ids + gather, 1: the move kernel)", form);
+    sf_ctx *ctx = map->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t total = (size_t)batch * (size_t)n;
+    // the scans as sf_icp_set_source* leaves them: SoA planes and float4 records
+    std::vector<float> h_soa(3 * total);
+    std::vector<float4> h_rec(total);
+    for (size_t i = 0; i < total; ++i) {
+        for (int a = 0; a < 3; ++a) h_soa[(size_t)a * total + i] = points[3 * i + a];
+        h_rec[i] = make_float4(points[3 * i], points[3 * i + 1], points[3 * i + 2], 0.0f);
+    }
+    std::vector<IcpState> h_state((size_t)batch);
+    std::memset(static_cast<void *>(h_state.data()), 0, sizeof(IcpState) * h_state.size());
+    for (int b = 0; b < batch; ++b) std::memcpy(h_state[(size_t)b].T, poses + 16 * (size_t)b, sizeof(double) * 16);
+    sf::OrderSrc src;
+    src.src_idx = nullptr;
+    src.seg_off = nullptr;
+    src.n = (int)n;
+    src.tiles = (int)std::max<int64_t>(1, sf::div_up(n, sf::ORD_TILE));
+    src.nseg = batch;
+    sf::DevBuf x0, rec, state, xq, dkeys, counts, ids, lut; // freed on every path
+    SF_TRY(x0.reserve(sizeof(float) * 3 * total));
+    SF_TRY(rec.reserve(sizeof(float4) * total));
+    SF_TRY(state.reserve(sizeof(IcpState) * (size_t)batch));
+    SF_TRY(xq.reserve(sizeof(float) * 3 * total));
+    SF_TRY(dkeys.reserve(sizeof(uint16_t) * total));
+    SF_TRY(counts.reserve(sizeof(uint32_t) * (size_t)batch * (size_t)(src.tiles + 1) * sf::ORD_BINS));
+    SF_TRY(ids.reserve(sizeof(uint32_t) * total));
+    SF_TRY(sf::upload_staged(ctx, x0.p, h_soa.data(), sizeof(float) * 3 * total));
+    SF_TRY(sf::upload_staged(ctx, rec.p, h_rec.data(), sizeof(float4) * total));
+    SF_TRY(sf::upload_staged(ctx, state.p, h_state.data(), sizeof(IcpState) * (size_t)batch));
+    SF_HIP(hipMemsetAsync(xq.p, 0xff, sizeof(float) * 3 * total, st));
+    CellKeyFn kf;
+    kf.g = map->grid;
+    kf.x = soa(x0, (int64_t)total, 0); kf.y = soa(x0, (int64_t)total, 1); kf.z = soa(x0, (int64_t)total, 2);
+    kf.st = state.as<IcpState>();
+    kf.n = (int)n;
+    kf.shift = order_key_shift(map->grid);
+    kf.lut = nullptr;
+    kf.lut_shift = 0;
+    if (table) { // the density table of the attached index, as order_lut_prepare builds it
+        SF_TRY(order_lut_build(st, map->grid, lut, &kf.lut_shift));
+        kf.lut = reinterpret_cast<const uint16_t *>(lut.as<uint32_t>() + ORDER_LUT_BINS);
+    }
+    float *const planes[3] = {soa(xq, (int64_t)total, 0), soa(xq, (int64_t)total, 1), soa(xq, (int64_t)total, 2)};
+    launch_order_plain(st, src, kf, dkeys.as<uint16_t>(), counts.as<uint32_t>(), form, ids.as<uint32_t>(), rec.as<float4>(), planes);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(keys, dkeys.p, sizeof(uint16_t) * total, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(h_soa.data(), xq.p, sizeof(float) * 3 * total, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i < total; ++i)
+        for (int a = 0; a < 3; ++a) ordered[3 * i + a] = h_soa[(size_t)a * total + i];
+    return SF_OK;
 }

@@ -1,5 +1,6 @@
 // sf_icp_order_host.hpp -- the host side of the query order: which alignments go tile by tile and with which tiles (tile_plan,
-// tile_wanted), the key table of the attached index (order_lut_prepare), the segmented sort (run_order_sort) and order_queries.
+// tile_wanted), the key table of the attached index (order_lut_build, order_lut_prepare), the launches of the plain path
+// (launch_order_plain), the segmented sort (run_order_sort) and order_queries.
 // A fragment, not a stand-alone header: sf_icp.hip includes it at file scope, after sf_icp_object.hpp.  It launches the k_order_*,
 // k_order_lut_* and k_tile_* kernels of sf_icp.hip's device code with that code's CellKeyFn, TileKeyFn, IcpState, nblk, GATHER_TILE,
 // ORDER_LUT_LOG2, TILE_KEY_NONE and TILE_STATS, and uses Lane, SrcSet, soa(), robust_on(), order_span() and order_key_shift()
@@ -62,24 +63,48 @@ bool tile_wanted(const sf_icp *icp, int mode)
 // BEFORE an alignment takes a lane: the lanes order themselves behind the context's stream whenever the target changes
 // (LaneScope), so both see the finished table.
 constexpr int ORDER_LUT_BINS = (1 << ORDER_LUT_LOG2) + 1;
+// the table of index g into buf (histogram, then the keys), enqueued on st; *shift: what CellKeyFn::lut_shift takes
+int order_lut_build(hipStream_t st, const SfGrid &g, sf::DevBuf &buf, int *shift)
+{
+    const OrderSpan sp = order_span(g);
+    *shift = std::max(0, sp.bits - ORDER_LUT_LOG2);
+    const int nbins = (int)(sp.cells >> *shift) + 1;
+    SF_TRY(buf.reserve(sizeof(uint32_t) * (size_t)ORDER_LUT_BINS + sizeof(uint16_t) * (size_t)ORDER_LUT_BINS));
+    uint32_t *hist = buf.as<uint32_t>();
+    uint16_t *lut = reinterpret_cast<uint16_t *>(hist + ORDER_LUT_BINS);
+    SF_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)ORDER_LUT_BINS, st));
+    hipLaunchKernelGGL(k_order_lut_hist, dim3(nblk(g.n)), dim3(256), 0, st, g, *shift, hist);
+    hipLaunchKernelGGL(k_order_lut_make, dim3(1), dim3(1024), 0, st, hist, nbins, (uint32_t)g.n, lut);
+    SF_HIP(hipGetLastError());
+    return SF_OK;
+}
 int order_lut_prepare(sf_icp *icp)
 {
     if (!icp->order_lut_on || !icp->map || !icp->map->built) return SF_OK;
     const SfGrid &g = icp->map->grid;
     if (g.n <= 0 || (icp->order_lut.p && icp->order_lut_gen == icp->map->generation)) return SF_OK;
-    const OrderSpan sp = order_span(g);
-    icp->order_lut_shift = std::max(0, sp.bits - ORDER_LUT_LOG2);
-    const int nbins = (int)(sp.cells >> icp->order_lut_shift) + 1;
-    SF_TRY(icp->order_lut.reserve(sizeof(uint32_t) * (size_t)ORDER_LUT_BINS + sizeof(uint16_t) * (size_t)ORDER_LUT_BINS));
-    uint32_t *hist = icp->order_lut.as<uint32_t>();
-    uint16_t *lut = reinterpret_cast<uint16_t *>(hist + ORDER_LUT_BINS);
-    hipStream_t st = icp->ctx->stream;
-    SF_HIP(hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)ORDER_LUT_BINS, st));
-    hipLaunchKernelGGL(k_order_lut_hist, dim3(nblk(g.n)), dim3(256), 0, st, g, icp->order_lut_shift, hist);
-    hipLaunchKernelGGL(k_order_lut_make, dim3(1), dim3(1024), 0, st, hist, nbins, (uint32_t)g.n, lut);
-    SF_HIP(hipGetLastError());
+    SF_TRY(order_lut_build(icp->ctx->stream, g, icp->order_lut, &icp->order_lut_shift));
     icp->order_lut_gen = icp->map->generation;
     return SF_OK;
+}
+
+// The plain path of the sort: uniform segments (src.nseg scans of src.n queries in element order), one 10-bit digit.
+// k_order_hist -> k_order_scan -> form 1: k_order_move (x0 -> xq in one pass, no ids); form 0: k_order_scatter + k_order_gather
+// through `ids` and the float4 records `rec` (what the sharded start and the tile sort still run, and what sf_test_query_order
+// compares the move kernel with).  x0 / xq: the three planes of the scans as given / in cell order.
+void launch_order_plain(hipStream_t s, const sf::OrderSrc &src, const CellKeyFn &kf, uint16_t *keys, uint32_t *counts, int form, uint32_t *ids, const float4 *rec,
+                        float *const xq[3])
+{
+    const dim3 grid(sf::order_grid(src.tiles, src.nseg)), blk(sf::ORD_BLK);
+    hipLaunchKernelGGL(k_order_hist, grid, blk, 0, s, src, kf, keys, counts);
+    hipLaunchKernelGGL(sf::k_order_scan, dim3((unsigned)src.nseg), dim3(sf::ORD_BINS), 0, s, counts, src.tiles);
+    if (form == 1) {
+        hipLaunchKernelGGL(k_order_move, grid, blk, 0, s, src, keys, counts, kf.x, kf.y, kf.z, xq[0], xq[1], xq[2]);
+        return;
+    }
+    hipLaunchKernelGGL(k_order_scatter, grid, blk, 0, s, src, keys, counts, ids);
+    const int gt = (int)std::max<int64_t>(1, sf::div_up(src.n, GATHER_TILE));
+    hipLaunchKernelGGL(k_order_gather, dim3(sf::order_grid(gt, src.nseg)), dim3(256), 0, s, rec, ids, (int64_t)src.n * src.nseg, src.n, gt, src.nseg, xq[0], xq[1], xq[2]);
 }
 
 // the segmented stable bucket sort of sf_order.hpp: nseg segments (uniform: nseg scans of n queries; sharded: the
@@ -109,11 +134,19 @@ int run_order_sort(sf_icp *icp, int nseg, int64_t longest, int64_t total, const 
     SF_TRY(ln.Xq.reserve(sizeof(float) * 3 * std::max(cap, (size_t)(seg_off ? 0 : ss.plane))));
     SF_TRY(ln.qkeys.reserve(sizeof(uint16_t) * cap));                                                      // bucket key of every element
     SF_TRY(ln.qkeys2.reserve(sizeof(uint32_t) * (size_t)nseg * (size_t)(src.tiles + 1) * sf::ORD_BINS));  // per-tile bucket counts / starts
-    SF_TRY(ln.qidx.reserve(sizeof(uint32_t) * cap));                                                       // ordered query ids
     uint16_t *keys = ln.qkeys.as<uint16_t>();
-    uint32_t *counts = ln.qkeys2.as<uint32_t>(), *ordered = ln.qidx.as<uint32_t>();
+    uint32_t *counts = ln.qkeys2.as<uint32_t>();
     hipStream_t s = icp->ctx->stream;
     src.nseg = nseg;
+    if (!icp->tile_on && !seg_off && !src_idx) { // the plain path: ranked and moved in one pass, no ids (and no qidx: 4 bytes per query and lane)
+        float *const xq[3] = {soa(ln.Xq, ss.plane, 0), soa(ln.Xq, ss.plane, 1), soa(ln.Xq, ss.plane, 2)};
+        launch_order_plain(s, src, kf, keys, counts, 1, nullptr, nullptr, xq);
+        SF_HIP(hipGetLastError());
+        return SF_OK;
+    }
+    // the sharded start (seg_off / src_idx) and the two-digit tile sort need the ids between their passes
+    SF_TRY(ln.qidx.reserve(sizeof(uint32_t) * cap));                                                       // ordered query ids
+    uint32_t *ordered = ln.qidx.as<uint32_t>();
     const dim3 grid(sf::order_grid(src.tiles, nseg)), blk(sf::ORD_BLK);
     if (icp->tile_on) { // by map tile: a 20-bit key, least significant 10-bit digit first (stable passes)
         TileKeyFn tk;

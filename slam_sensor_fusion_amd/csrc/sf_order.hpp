@@ -13,8 +13,18 @@
 //   k_order_hist     per-tile bucket counts (LDS histogram, keys computed from the coordinates, the key of every
 //                    query kept as a u16 so the scatter does not recompute it)
 //   k_order_scan     per segment: exclusive prefix over tiles and over buckets, in place
-//   k_order_scatter  rank inside the tile + prefix -> the query's id at its ordered position
+//   k_order_move     the plain path (uniform segments in element order, one digit): rank inside the tile + prefix, the tile
+//                    put into bucket order in LDS and the three coordinate planes written to their ordered positions, slot
+//                    i by thread i % 256 -- a bucket's queries of one tile are consecutive in the segment, so consecutive
+//                    lanes store consecutive addresses while the bucket lasts (about 15 lines per wave and plane on
+//                    randomly drawn scans, fewer on a sensor's sweep order).  No ids and no float4 records: 107 us per
+//                    64 x 200 k-point step against 82 + 121 for the two kernels below, the same Xq bit for bit.  (Round 3's
+//                    attempt stored x, y, z straight from the scatter in ELEMENT order: three scattered 4-byte streams,
+//                    420 us.  The store pattern was the failure, not the fusion.)
+//   k_order_scatter  rank inside the tile + prefix -> the query's id at its ordered position: the forms that need ids
+//                    between their passes (segment offsets / src_idx of the sharded start, the two-digit tile sort)
 //   k_order_gather   (sf_icp.hip) ids read coalesced, float4 records gathered, cell-ordered SoA written coalesced
+// sf_test_query_order (include/slamfusion.h; tests/test_gpu_query_order.py) runs hist -> scan -> either form on host points.
 //
 // Stability inside a tile without a per-element sequential loop: a tile is split into contiguous quarters, one per
 // wave; each wave keeps its own running counter per bucket in LDS (started at the tile's start for that bucket +
@@ -209,6 +219,144 @@ __device__ __forceinline__ void order_scatter_body(const OrderSrc &s, const uint
 #pragma unroll
     for (int c = 0; c < ORD_PER_LANE; ++c)
         if (valid[c]) out[seg_start + rank[c]] = id[c];
+}
+
+// ---- k_order_move: rank and move in one pass (uniform segments, identity ids)
+// LDS of a workgroup: 16 KB that hold the per-wave counters while the tile is ranked and one coordinate plane of the tile
+// afterwards, the key of every slot (8 KB) and per bucket what turns a slot into a position of the segment (4 KB): 28 KB.
+struct OrderMoveLds {
+    union {
+        uint32_t ctr[ORD_WAVES][ORD_BINS]; // ranking: where the wave's next query of a bucket goes INSIDE the tile
+        float plane[ORD_TILE];             // write-out: one coordinate of the tile in bucket order
+    };
+    uint32_t delta[ORD_BINS];              // (bucket start + tile prefix) - the bucket's offset inside the tile
+    uint16_t skey[ORD_TILE];               // key of the query in slot i
+    uint32_t wsum[ORD_WAVES];
+};
+static_assert(sizeof(uint32_t) * ORD_WAVES * ORD_BINS == sizeof(float) * ORD_TILE, "the plane takes the counters' place");
+
+// one coordinate plane of the tile: v[c] (element order, in registers) -> LDS in bucket order -> dst, slot i by thread i % ORD_BLK
+__device__ __forceinline__ void order_move_plane(OrderMoveLds &L, const float (&v)[ORD_PER_LANE], const bool (&valid)[ORD_PER_LANE], const uint32_t (&slot)[ORD_PER_LANE],
+                                                 const uint32_t (&pos)[ORD_PER_LANE], uint32_t tile_cnt, float *__restrict__ dst)
+{
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c)
+        if (valid[c]) L.plane[slot[c]] = v[c];
+    __syncthreads();
+    float o[ORD_PER_LANE];
+#pragma unroll
+    for (int j = 0; j < ORD_PER_LANE; ++j) {
+        const uint32_t i = threadIdx.x + (uint32_t)ORD_BLK * j;
+        o[j] = i < tile_cnt ? L.plane[i] : 0.0f;
+    }
+    __syncthreads(); // the plane is in registers: the next one may be written while the stores below drain
+#pragma unroll
+    for (int j = 0; j < ORD_PER_LANE; ++j)
+        if (threadIdx.x + (uint32_t)ORD_BLK * j < tile_cnt) dst[pos[j]] = o[j];
+}
+
+// dx / dy / dz[seg_start + rank] <- sx / sy / sz[seg_start + e]: the ranks of order_scatter_body (bucket start + tile prefix + the
+// waves before + the ballot rank, chunks of a wave in order), so every query lands where k_order_scatter + k_order_gather put it.
+// A rank is formed as (slot inside the tile) + delta[key]: the tile's queries go to their slots in LDS first -- bucket order --
+// and slot i is written out by thread i % ORD_BLK, so that consecutive lanes store consecutive addresses as long as the bucket
+// lasts (a bucket's queries of one tile are consecutive in the segment) instead of one line per lane.  The three planes go
+// through the same 16 KB one after the other with the positions computed once.  No atomic returns a value and every LDS word
+// written between two barriers has exactly one writer: the result does not depend on the order lanes are served in.
+__device__ __forceinline__ void order_move_body(const OrderSrc &s, const uint16_t *__restrict__ keys, const uint32_t *__restrict__ starts, const float *__restrict__ sx,
+                                                const float *__restrict__ sy, const float *__restrict__ sz, float *__restrict__ dx, float *__restrict__ dy, float *__restrict__ dz)
+{
+    __shared__ OrderMoveLds L;
+    int b, tile;
+    if (!order_block(s.tiles, s.nseg, &b, &tile)) return;
+    const uint32_t seg_len = (uint32_t)s.n, tile_first = (uint32_t)tile * ORD_TILE;
+    if (tile_first >= seg_len) return;
+    const size_t seg_start = (size_t)b * (size_t)s.n;
+    const uint32_t tile_cnt = seg_len - tile_first < (uint32_t)ORD_TILE ? seg_len - tile_first : (uint32_t)ORD_TILE;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int d = threadIdx.x; d < ORD_BINS * ORD_WAVES; d += ORD_BLK) (&L.ctr[0][0])[d] = 0;
+    __syncthreads();
+    uint32_t key[ORD_PER_LANE];
+    bool valid[ORD_PER_LANE];
+    float vx[ORD_PER_LANE], vy[ORD_PER_LANE], vz[ORD_PER_LANE];
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c) {
+        const uint32_t e = order_element(tile, c);
+        valid[c] = e < seg_len;
+        key[c] = valid[c] ? (uint32_t)keys[seg_start + e] : 0u;
+    }
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c) vx[c] = valid[c] ? sx[seg_start + order_element(tile, c)] : 0.0f; // in flight while the tile is ranked
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c)
+        if (valid[c]) atomicAdd(&L.ctr[wv][key[c]], 1u);
+    __syncthreads();
+    // per-wave counts -> per-wave running slot: the bucket's offset inside the tile (exclusive scan of the tile's ORD_BINS bucket
+    // totals: four consecutive buckets per thread, then the workgroup's threads) + what the waves before hold
+    {
+        static_assert(ORD_BINS == 4 * ORD_BLK, "four buckets per thread");
+        const int d0 = 4 * threadIdx.x;
+        const uint32_t *seg_tab = starts + (size_t)b * (s.tiles + 1) * ORD_BINS;
+        const uint4 tp = *reinterpret_cast<const uint4 *>(seg_tab + (size_t)tile * ORD_BINS + d0);
+        const uint4 bs = *reinterpret_cast<const uint4 *>(seg_tab + (size_t)s.tiles * ORD_BINS + d0);
+        const uint32_t first[4] = {tp.x + bs.x, tp.y + bs.y, tp.z + bs.z, tp.w + bs.w}; // where the tile's queries of the bucket start in the segment
+        uint32_t cnt[ORD_WAVES][4], mine = 0;
+#pragma unroll
+        for (int w = 0; w < ORD_WAVES; ++w)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                cnt[w][j] = L.ctr[w][d0 + j];
+                mine += cnt[w][j];
+            }
+        uint32_t incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t t = __shfl_up(incl, off);
+            if (lane >= off) incl += t;
+        }
+        if (lane == 63) L.wsum[wv] = incl;
+        __syncthreads();
+        uint32_t run = incl - mine;
+#pragma unroll
+        for (int w = 0; w < ORD_WAVES; ++w)
+            if (w < wv) run += L.wsum[w];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            L.delta[d0 + j] = first[j] - run; // (uint32 arithmetic: slot + delta is the position in the segment)
+#pragma unroll
+            for (int w = 0; w < ORD_WAVES; ++w) {
+                L.ctr[w][d0 + j] = run;
+                run += cnt[w][j];
+            }
+        }
+    }
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t slot[ORD_PER_LANE];
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c) { // the wave's chunks in order: stability (the loop of order_scatter_body)
+        const unsigned long long peers = order_peers(key[c], valid[c]);
+        slot[c] = valid[c] ? L.ctr[wv][key[c]] + (uint32_t)__popcll(peers & below) : 0u;
+        __builtin_amdgcn_wave_barrier(); // every lane has read the counter before the group's last lane advances it
+        if (valid[c] && (peers >> lane) <= 1ull) L.ctr[wv][key[c]] += (uint32_t)__popcll(peers);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c) {
+        if (valid[c]) L.skey[slot[c]] = (uint16_t)key[c];
+        vy[c] = valid[c] ? sy[seg_start + order_element(tile, c)] : 0.0f;
+        vz[c] = valid[c] ? sz[seg_start + order_element(tile, c)] : 0.0f;
+    }
+    __syncthreads(); // the counters are done with (the plane takes their place) and every slot has its key
+    uint32_t pos[ORD_PER_LANE];
+#pragma unroll
+    for (int j = 0; j < ORD_PER_LANE; ++j) {
+        const uint32_t i = threadIdx.x + (uint32_t)ORD_BLK * j;
+        pos[j] = i < tile_cnt ? L.delta[L.skey[i]] + i : 0u;
+    }
+    order_move_plane(L, vx, valid, slot, pos, tile_cnt, dx + seg_start);
+    order_move_plane(L, vy, valid, slot, pos, tile_cnt, dy + seg_start);
+    order_move_plane(L, vz, valid, slot, pos, tile_cnt, dz + seg_start);
 }
 
 } // namespace sf
