@@ -380,6 +380,70 @@ int sf_cloud_cluster_boxes(sf_cloud *c, double tolerance, int64_t min_size, int6
                            sf_label_box *boxes, int64_t cap_boxes, sf_cluster_stats *cstats, sf_box_stats *bstats);
 int sf_cloud_remove_boxes(sf_cloud *c, const double *center /* [B][3] */, const double *R /* [B][9] */, const double *extent /* [B][3] */,
                           int64_t n_boxes /* 0 .. 1024 */, double margin, int keep_inside, int64_t *n_inside);
+/* FPFH descriptors and descriptor matching (extension, no reference code; pcl::FPFHEstimation, Open3D compute_fpfh_feature and
+ * the nearest-descriptor correspondences both libraries feed to a global registration; DESIGN §21, restated in
+ * tests/fpfh_ref_np.py).  The first step from "refine a pose" to "find a pose": estimating the pose from the matches is not here.
+ * sf_features: n rows of SF_FPFH_DIM float32 and one validity byte per row on the device, in the ORIGINAL point order of whatever
+ *   produced them.  A row that holds a non-finite value is invalid whatever flag came with it (valid NULL: every row is offered as
+ *   valid); the byte always comes out as 0 or 1.  download: cap >= n rows, *n = n (SF_ERR_INVALID when cap is too small, *n set).
+ * Neighbours.  r2 = (float)(radius * radius); j is a neighbour of i iff both are indexed, j != i and d2(x_i, x_j) < r2 under the
+ *   float32, unfused, strict rule of sf_map_radius_outliers (symmetric bit for bit; the same walk, so the same proof that nothing
+ *   is lost).  The window is ignored; the map's index, normals, covariances and neighbour table are not modified.
+ * Normals.  The stored normal of a point, converted to float64; SF_ORIENT_NONE: as stored; SF_ORIENT_DIRECTION: negated when
+ *   n . toward < 0 (Open3D's default with toward = +z); SF_ORIENT_VIEWPOINT: negated when n . (toward - x) < 0 (PCL's viewpoint
+ *   rule) -- as the normal is loaded, the stored normals stay as they are.  A point whose normal is all zeros or not finite has no
+ *   normal: it contributes to nothing and gets no descriptor.  A map without normals: SF_ERR_STATE.
+ * Pair (i, j), float64, unfused, in the order written (dot products and squares left to right over x, y, z): d = x_j - x_i,
+ *   L = sqrt(d.d), L == 0 skips the pair; a_i = (n_i.d) / L, a_j = (n_j.d) / L; if |a_i| < |a_j|: source j, target i, d = -d,
+ *   phi = -a_j, else source i, target j, phi = a_i; v = d x n_src, |v| == 0 skips the pair, v = v / |v|, w = n_src x v;
+ *   alpha = v . n_tgt; theta = atan2(w . n_tgt, n_src . n_tgt).
+ * Bins.  floor(11 (theta + pi) / (2 pi)), floor(11 (alpha + 1) / 2), floor(11 (phi + 1) / 2), each clamped to 0 .. 10; a row is
+ *   [0, 11) theta, [11, 22) alpha, [22, 33) phi.
+ * SPFH.  cnt_i[b] = the pairs of i that were not skipped, per bin; P_i their number; SPFH_i[b] = cnt_i[b] * (100.0 / P_i);
+ *   P_i == 0: no SPFH.  sf_map_compute_spfh returns cnt ([n][33]) and P ([n]) in original order, zeros for points without one:
+ *   integers, so they depend on the cloud and the parameters alone, not on the cell.
+ * FPFH.  Over the neighbours j of i that have an SPFH and d2_ij > 0, in the order the index walks them:
+ *   W[b] = sum SPFH_j[b] / (double)d2_ij (d2_ij the float32 value of the neighbour rule: the weight is the squared distance, as in
+ *   both libraries); per group of 11 bins S_g = sum W[b] in ascending b; F_i[b] = (S_g > 0 ? W[b] * (100.0 / S_g) : 0) +
+ *   SPFH_i[b], rounded to float32 once.  Point i gets a descriptor (valid = 1) iff it has an SPFH, otherwise 33 zeros and 0.
+ *   The same call on the same index returns the same bits every time (integer atomics only); another cell moves the float64 sums
+ *   W by their rounding, nothing else.
+ * SF_ERR_INVALID, nothing touched: a radius that is not finite and > 0, an unknown orient, a toward that is not finite.  An empty
+ *   map is SF_OK with zero stats and an empty set.  n_valid: the indexed points; n_featured: the valid rows; n_pairs = sum P_i,
+ *   max_pairs = max P_i.  profile != 0: spfh_ms and fpfh_ms are the device-event times of the two passes, otherwise both are -1.
+ * sf_cloud_compute_fpfh: a temporary map of the cloud (`cell` as in sf_map_build, 0 = automatic),
+ *   sf_map_estimate_normals((float)normal_radius) on it, then the device code of sf_map_compute_fpfh: bit for bit what those
+ *   three calls give.  The cloud is not modified.
+ * sf_features_match.  D(a, b): float32, unfused, ascending k: acc = 0; for k = 0 .. 32: t = a[k] - b[k]; t = t * t; acc = acc + t.
+ *   Invalid rows are never candidates and never queries.  idx[i] = the valid dst row with the smallest (D, index), dist2[i] its D,
+ *   second2[i] the smallest D over the OTHER valid rows (+inf when there is none); idx = -1, dist2 = second2 = +inf for an invalid
+ *   query or an empty candidate set.  i is accepted iff idx[i] >= 0, and with 0 < ratio < 1 also
+ *   dist2[i] < (float)(ratio * ratio) * second2[i], and with mutual != 0 also: the best src row for dst row idx[i] under the same
+ *   (D, index) rule is i.  pairs: the accepted (i, idx[i]) in ascending i, truncated at cap_pairs; n_matched counts them all.
+ *   idx, dist2, second2 and pairs may be NULL.  SF_ERR_INVALID: different contexts, either side >= 2^31 rows.  profile != 0:
+ *   match_ms = the device time from the first to the last kernel, otherwise -1. */
+#define SF_FPFH_DIM 33
+#define SF_ORIENT_NONE 0
+#define SF_ORIENT_DIRECTION 1
+#define SF_ORIENT_VIEWPOINT 2
+typedef struct sf_features sf_features;
+typedef struct { double radius; int32_t orient, profile; double toward[3]; } sf_fpfh_params;
+typedef struct { int64_t n_points, n_valid, n_featured, n_pairs, max_pairs; float spfh_ms, fpfh_ms; } sf_fpfh_stats;
+typedef struct { double ratio; int32_t mutual, profile; } sf_match_params;   /* ratio <= 0 or >= 1: no ratio test */
+typedef struct { int64_t n_src, n_dst, n_src_valid, n_dst_valid, n_matched; float match_ms; int32_t pad; } sf_match_stats;
+int sf_features_create(sf_ctx *ctx, sf_features **out);
+void sf_features_destroy(sf_features *f);
+int sf_features_size(const sf_features *f, int64_t *n);
+int sf_features_upload(sf_features *f, const float *rows /* [n][33] */, const uint8_t *valid /* [n] or NULL */, int64_t n);
+int sf_features_download(sf_features *f, float *rows /* [cap][33] */, uint8_t *valid /* [cap] or NULL */, int64_t cap, int64_t *n);
+void sf_fpfh_default_params(sf_fpfh_params *p);     /* radius 0 (to be set), SF_ORIENT_NONE, no profile, toward +z */
+void sf_match_default_params(sf_match_params *p);   /* no ratio test, not mutual, no profile */
+int sf_map_compute_fpfh(sf_map *m, const sf_fpfh_params *p, sf_features *out, sf_fpfh_stats *stats);
+int sf_map_compute_spfh(sf_map *m, const sf_fpfh_params *p, uint32_t *counts /* [n][33] */, int32_t *n_pairs /* [n] */);
+int sf_cloud_compute_fpfh(sf_cloud *c, double normal_radius, const sf_fpfh_params *p, float cell, sf_features *out, sf_fpfh_stats *stats);
+int sf_features_match(sf_features *src, sf_features *dst, const sf_match_params *p,
+                      int32_t *idx /* [n_src] */, float *dist2 /* [n_src] */, float *second2 /* [n_src] or NULL */,
+                      int32_t *pairs /* [cap][2] or NULL */, int64_t cap_pairs, sf_match_stats *stats);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */

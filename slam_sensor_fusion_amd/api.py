@@ -162,12 +162,55 @@ def _box_params(mode, up, profile):
     return p
 
 
+ORIENT_MODES = {"none": 0, "direction": 1, "viewpoint": 2}  # SF_ORIENT_*
+FPFH_DIM = 33                                               # SF_FPFH_DIM
+
+
+class FpfhParams(C.Structure):
+    """sf_fpfh_params: the feature radius, how the stored normals are oriented as they are loaded (SF_ORIENT_*; toward: a direction or
+    a viewpoint) and the profile switch."""
+    _fields_ = [("radius", C.c_double), ("orient", C.c_int32), ("profile", C.c_int32), ("toward", C.c_double * 3)]
+
+    def as_dict(self):
+        return dict(radius=float(self.radius), orient=int(self.orient), profile=int(self.profile), toward=[float(v) for v in self.toward])
+
+
+class FpfhStats(C.Structure):
+    """sf_fpfh_stats: n_valid = the indexed points, n_featured = the rows with a descriptor, n_pairs / max_pairs = the sum and the
+    largest of the pair counts P_i; spfh_ms / fpfh_ms: -1 unless profiled."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_valid", "n_featured", "n_pairs", "max_pairs")] + [("spfh_ms", C.c_float), ("fpfh_ms", C.c_float)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+class MatchParams(C.Structure):
+    """sf_match_params: ratio (<= 0 or >= 1: no ratio test), mutual, profile."""
+    _fields_ = [("ratio", C.c_double), ("mutual", C.c_int32), ("profile", C.c_int32)]
+
+
+class MatchStats(C.Structure):
+    """sf_match_stats: the rows and the valid rows of both sides, the accepted pairs; match_ms: -1 unless profiled."""
+    _fields_ = [(name, C.c_int64) for name in ("n_src", "n_dst", "n_src_valid", "n_dst_valid", "n_matched")] + [("match_ms", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_ if name != "pad"}
+
+
+def _fpfh_params(radius, orient, toward, profile):
+    """The keyword form of the FPFH calls -> FpfhParams (orient: "none" | "direction" | "viewpoint" or the SF_ORIENT_* number)."""
+    p = FpfhParams()
+    p.radius, p.orient, p.profile = float(radius), (ORIENT_MODES[orient] if orient in ORIENT_MODES else int(orient)), int(bool(profile))
+    p.toward[0], p.toward[1], p.toward[2] = [float(v) for v in np.asarray(toward, dtype=np.float64).reshape(3)]
+    return p
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
 
 def _close_all():
-    for kind in ("Node", "Comm", "Icp", "BruteForceAlignment", "Map", "Cloud", "Context"):
+    for kind in ("Node", "Comm", "Icp", "BruteForceAlignment", "Features", "Map", "Cloud", "Context"):
         for obj in [o for o in list(_live) if type(o).__name__ == kind]:
             try:
                 obj.close()
@@ -229,6 +272,18 @@ def load_library():
     lib.sf_test_label_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_cloud_cluster_boxes.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sf_cloud_remove_boxes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p]
+    lib.sf_fpfh_default_params.restype = None
+    lib.sf_match_default_params.restype = None
+    lib.sf_features_create.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_features_destroy.argtypes = [C.c_void_p]
+    lib.sf_features_destroy.restype = None
+    lib.sf_features_size.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_features_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sf_features_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_map_compute_fpfh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_map_compute_spfh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_compute_fpfh.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    lib.sf_features_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.sf_test_launch_schedule.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -675,6 +730,14 @@ class Cloud:
                                               C.byref(n_inside)))
         return n_inside.value
 
+    def compute_fpfh(self, normal_radius, radius, orient="none", toward=(0, 0, 1), cell=0.0, profile=False):
+        """sf_cloud_compute_fpfh: a temporary map of the cloud, Map.estimate_normals(normal_radius) on it, then Map.compute_fpfh(radius,
+        orient, toward) -> (Features in the cloud's point order, stats dict); bit for bit what those three calls give.  The cloud stays
+        as it is."""
+        p, st, out = _fpfh_params(radius, orient, toward, profile), FpfhStats(), Features(self.ctx)
+        _check(self.lib.sf_cloud_compute_fpfh(self.h, C.c_double(normal_radius), C.byref(p), C.c_float(cell), out.h, C.byref(st)))
+        return out, st.as_dict()
+
     def last_indices(self):
         n = C.c_int64()
         cap = 1 << 20
@@ -891,6 +954,24 @@ class Map:
         _check(self.lib.sf_map_radius_outliers(self.h, C.c_double(radius), C.c_int(int(min_neighbors)), _p(keep), _p(cnt), C.byref(st)))
         return keep.astype(bool), cnt, st.as_dict()
 
+    def compute_fpfh(self, radius, orient="none", toward=(0, 0, 1), profile=False):
+        """sf_map_compute_fpfh (pcl::FPFHEstimation, Open3D compute_fpfh_feature): the 33-bin FPFH of every map point from the points with
+        float32 d2 < float32(radius^2) and the map's normals -> (Features in original point order, stats dict).  orient "none": the
+        normals as stored; "direction": negated when n . toward < 0; "viewpoint": negated when n . (toward - x) < 0.  A point without a
+        normal or without a usable pair gets 33 zeros and valid = 0."""
+        p, st, out = _fpfh_params(radius, orient, toward, profile), FpfhStats(), Features(self.ctx)
+        _check(self.lib.sf_map_compute_fpfh(self.h, C.byref(p), out.h, C.byref(st)))
+        return out, st.as_dict()
+
+    def compute_spfh(self, radius, orient="none", toward=(0, 0, 1)):
+        """sf_map_compute_spfh: the integer half of compute_fpfh -> (counts uint32 [n, 33], n_pairs int32 [n]), original point order;
+        SPFH_i = counts_i * (100 / n_pairs_i)."""
+        n = len(self)
+        p = _fpfh_params(radius, orient, toward, False)
+        counts, pairs = np.zeros((n, FPFH_DIM), np.uint32), np.zeros(n, np.int32)
+        _check(self.lib.sf_map_compute_spfh(self.h, C.byref(p), _p(counts), _p(pairs)))
+        return counts, pairs
+
     def _clusters(self, call, *args):
         n = len(self)
         labels = np.empty(n, np.int32)
@@ -981,6 +1062,68 @@ class Map:
     def close(self):
         if self.h:
             self.lib.sf_map_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Features:
+    """sf_features: n descriptor rows of 33 float32 and a validity byte per row on the device, in the point order of what produced
+    them (Map.compute_fpfh, Cloud.compute_fpfh, or `upload`)."""
+
+    def __init__(self, ctx, rows=None, valid=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        _check(self.lib.sf_features_create(ctx.h, C.byref(self.h)))
+        _live.add(self)
+        if rows is not None:
+            self.upload(rows, valid)
+
+    def upload(self, rows, valid=None):
+        """rows [n, 33] float32; valid [n] (None: all offered as valid).  A row holding a non-finite value is invalid either way."""
+        rows = _f32(rows).reshape(-1, FPFH_DIM)
+        v = None
+        if valid is not None:
+            v = np.ascontiguousarray(np.asarray(valid).reshape(-1) != 0, dtype=np.uint8)
+            if len(v) != len(rows):
+                raise SlamFusionError("valid must have one entry per row (%d, got %d)" % (len(rows), len(v)))
+        _check(self.lib.sf_features_upload(self.h, _p(rows), _p(v) if v is not None else None, C.c_int64(len(rows))))
+        return self
+
+    def __len__(self):
+        n = C.c_int64()
+        _check(self.lib.sf_features_size(self.h, C.byref(n)))
+        return n.value
+
+    def download(self):
+        """-> (rows float32 [n, 33], valid bool [n])"""
+        n = len(self)
+        rows, valid = np.zeros((n, FPFH_DIM), np.float32), np.zeros(n, np.uint8)
+        _check(self.lib.sf_features_download(self.h, _p(rows), _p(valid), C.c_int64(n), None))
+        return rows, valid.astype(bool)
+
+    def match(self, other, ratio=0, mutual=False, max_pairs=None, profile=False):
+        """sf_features_match: for every valid row the valid row of `other` with the smallest float32 squared distance (ties: the
+        smallest index) -> dict(idx int32 [n] (-1: none), dist2, second2 float32 [n], pairs int32 [m, 2], stats).  pairs are the
+        accepted (i, idx[i]) in ascending i: idx >= 0, with 0 < ratio < 1 also dist2 < float32(ratio^2) * second2 (Lowe's test), with
+        `mutual` also i being the best row of this set for other[idx[i]]; at most max_pairs of them (None: all), stats counts all."""
+        if not isinstance(other, Features):
+            raise SlamFusionError("match: the other side must be a Features object")
+        n = len(self)
+        cap = n if max_pairs is None else max(int(max_pairs), 0)
+        p, st = MatchParams(float(ratio), int(bool(mutual)), int(bool(profile))), MatchStats()
+        idx, d2, s2 = np.full(n, -1, np.int32), np.full(n, np.inf, np.float32), np.full(n, np.inf, np.float32)
+        pairs = np.zeros((max(cap, 1), 2), np.int32)
+        _check(self.lib.sf_features_match(self.h, other.h, C.byref(p), _p(idx), _p(d2), _p(s2), _p(pairs), C.c_int64(cap), C.byref(st)))
+        return dict(idx=idx, dist2=d2, second2=s2, pairs=pairs[:min(int(st.n_matched), cap)].copy(), stats=st.as_dict())
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.sf_features_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
