@@ -913,17 +913,42 @@ struct CellKeyFn {
         return P;
     }
     __device__ __forceinline__ Point load(uint32_t o) const { return Point{x[o], y[o], z[o]}; }
-    __device__ __forceinline__ uint32_t key(const Pose &P, const Point &p) const
+    // The key in two stages (sf::order_hist_body runs each over all elements of a lane before the next).  position: arithmetic
+    // only -> the index into the table, or without a table the key itself; POS_NONE for a non-finite query.
+    static constexpr uint32_t POS_NONE = 0xffffffffu;
+    __device__ __forceinline__ uint32_t position(const Pose &P, const Point &p) const
     {
         const float qx = fmaf(P.T[0], p.x, fmaf(P.T[1], p.y, fmaf(P.T[2], p.z, P.T[3])));
         const float qy = fmaf(P.T[4], p.x, fmaf(P.T[5], p.y, fmaf(P.T[6], p.z, P.T[7])));
         const float qz = fmaf(P.T[8], p.x, fmaf(P.T[9], p.y, fmaf(P.T[10], p.z, P.T[11])));
-        if (!(isfinite(qx) && isfinite(qy) && isfinite(qz))) return sf::ORD_KEY_NONE; // non-finite queries go to the end of their scan
+        const bool finite = isfinite(qx) && isfinite(qy) && isfinite(qz); // (grid_cell clamps whatever it is given: no branch needed)
         const int cx = sf::grid_cell((qx - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((qy - g.org[1]) * g.inv_h, g.dim[1]),
                   cz = sf::grid_cell((qz - g.org[2]) * g.inv_h, g.dim[2]);
-        if (lut) return (uint32_t)lut[order_cell(g, cx, cy, cz) >> lut_shift];
-        const uint64_t key = order_cell(g, cx, cy, cz) >> shift;
-        return (uint32_t)(key < (uint64_t)(sf::ORD_KEY_NONE - 1u) ? key : (uint64_t)(sf::ORD_KEY_NONE - 1u));
+        const uint64_t cell = order_cell(g, cx, cy, cz);
+        uint32_t w;
+        if (lut) {
+            w = (uint32_t)(cell >> lut_shift); // (at most ORDER_LUT_BINS - 1)
+        } else {
+            const uint64_t key = cell >> shift;
+            w = (uint32_t)(key < (uint64_t)(sf::ORD_KEY_NONE - 1u) ? key : (uint64_t)(sf::ORD_KEY_NONE - 1u));
+        }
+        return finite ? w : POS_NONE;
+    }
+    // table: the gathers of all N positions issued together (entry 0 for a non-finite query, whose key is chosen afterwards:
+    // no branch around a gather); non-finite queries go to the end of their scan
+    template <int N>
+    __device__ __forceinline__ void table(const uint32_t (&w)[N], uint32_t (&key)[N]) const
+    {
+        if (lut) {
+            uint16_t t[N];
+#pragma unroll
+            for (int c = 0; c < N; ++c) t[c] = lut[w[c] == POS_NONE ? 0u : w[c]];
+#pragma unroll
+            for (int c = 0; c < N; ++c) key[c] = w[c] == POS_NONE ? sf::ORD_KEY_NONE : (uint32_t)t[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < N; ++c) key[c] = w[c] == POS_NONE ? sf::ORD_KEY_NONE : w[c];
+        }
     }
 };
 
@@ -1049,7 +1074,14 @@ struct TileKeyFn {
                   cz = sf::grid_cell((qz - g.org[2]) * g.inv_h, g.dim[2]);
         return sf::tile_of_cell(tl, cx, cy, cz);
     }
-    __device__ __forceinline__ uint32_t key(const Pose &P, const Point &p) const { return (full_key(P, p) >> (sf::ORD_KEY_BITS * digit)) & (uint32_t)(sf::ORD_BINS - 1); }
+    // the two stages of sf::order_hist_body: the digit needs no table
+    __device__ __forceinline__ uint32_t position(const Pose &P, const Point &p) const { return (full_key(P, p) >> (sf::ORD_KEY_BITS * digit)) & (uint32_t)(sf::ORD_BINS - 1); }
+    template <int N>
+    __device__ __forceinline__ void table(const uint32_t (&w)[N], uint32_t (&key)[N]) const
+    {
+#pragma unroll
+        for (int c = 0; c < N; ++c) key[c] = w[c];
+    }
 };
 
 __global__ __launch_bounds__(sf::ORD_BLK) void k_order_hist_tile(sf::OrderSrc s, TileKeyFn kf, uint16_t *__restrict__ keys, uint32_t *__restrict__ counts)

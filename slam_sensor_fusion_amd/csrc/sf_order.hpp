@@ -11,13 +11,18 @@
 // Scans are independent segments: the order of a scan does not depend on what else is in the batch.
 //
 //   k_order_hist     per-tile bucket counts (LDS histogram, keys computed from the coordinates, the key of every
-//                    query kept as a u16 so the scatter does not recompute it)
+//                    query kept as a u16 so the scatter does not recompute it).  Stage by stage over a lane's 16 queries,
+//                    every load of a stage in flight before the first is waited for: ids, 48 coordinate loads, positions
+//                    (KEYFN::position, arithmetic), the 16 gathers from the density table (KEYFN::table), key stores, LDS
+//                    adds.  93 -> 65 us per 64 x 200 k-point step, every key bit for bit the same
+//                    (tests/test_gpu_order_keys.py).  What was tried beside it, and why the table is still gathered from
+//                    L2: profiles/LADDER.md, round 11
 //   k_order_scan     per segment: exclusive prefix over tiles and over buckets, in place
 //   k_order_move     the plain path (uniform segments in element order, one digit): rank inside the tile + prefix, the tile
 //                    put into bucket order in LDS and the three coordinate planes written to their ordered positions, slot
 //                    i by thread i % 256 -- a bucket's queries of one tile are consecutive in the segment, so consecutive
 //                    lanes store consecutive addresses while the bucket lasts (about 15 lines per wave and plane on
-//                    randomly drawn scans, fewer on a sensor's sweep order).  No ids and no float4 records: 107 us per
+//                    randomly drawn scans, fewer on a sensor's sweep order).  No ids and no float4 records: 103 us per
 //                    64 x 200 k-point step against 82 + 121 for the two kernels below, the same Xq bit for bit.  (Round 3's
 //                    attempt stored x, y, z straight from the scatter in ELEMENT order: three scattered 4-byte streams,
 //                    420 us.  The store pattern was the failure, not the fusion.)
@@ -95,6 +100,11 @@ __device__ __forceinline__ uint32_t order_element(int tile, int c)
 }
 
 // counts[(seg * (tiles + 1) + tile) * ORD_BINS + key]; keys[segment space] <- KEYFN(global query id)
+// Stage by stage over the lane's ORD_PER_LANE elements, nothing conditional between the loads of a stage: the ids (the test for
+// src_idx around the whole loop -- a per-element "id or load" select makes the compiler branch around every id load and wait for
+// everything in flight in front of the next element's coordinates), the 3 coordinate loads of every element behind one counted
+// wait, KEYFN::position (arithmetic only), KEYFN::table (the table gathers of all elements in flight together), then the key stores
+// and the LDS adds with no wait between them.  Elements past the segment's end read its last element and store nothing.
 template <class KEYFN>
 __device__ __forceinline__ void order_hist_body(const OrderSrc &s, KEYFN keyfn, uint16_t *__restrict__ keys, uint32_t *__restrict__ counts)
 {
@@ -110,24 +120,31 @@ __device__ __forceinline__ void order_hist_body(const OrderSrc &s, KEYFN keyfn, 
     }
     for (int d = threadIdx.x; d < ORD_BINS; d += ORD_BLK) h[d] = 0;
     __syncthreads();
-    // every load of the lane first (KEYFN::load: 16 x 3 coordinate loads in flight), then the arithmetic and the stores
     const typename KEYFN::Pose pose = keyfn.prepare(b); // segment b is scan b
+    const uint32_t last = seg_len - 1u;                 // (seg_len > 0: the tile holds an element)
+    uint32_t o[ORD_PER_LANE];
+    if (s.src_idx) {
+#pragma unroll
+        for (int c = 0; c < ORD_PER_LANE; ++c) o[c] = s.src_idx[seg_start + min(order_element(tile, c), last)];
+    } else {
+#pragma unroll
+        for (int c = 0; c < ORD_PER_LANE; ++c) o[c] = seg_start + min(order_element(tile, c), last);
+    }
     typename KEYFN::Point pt[ORD_PER_LANE];
 #pragma unroll
-    for (int c = 0; c < ORD_PER_LANE; ++c) {
-        const uint32_t e = order_element(tile, c);
-        const uint32_t o = e < seg_len ? (s.src_idx ? s.src_idx[seg_start + e] : seg_start + e) : seg_start;
-        pt[c] = keyfn.load(o);
-    }
+    for (int c = 0; c < ORD_PER_LANE; ++c) pt[c] = keyfn.load(o[c]);
+    uint32_t w[ORD_PER_LANE], key[ORD_PER_LANE];
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c) w[c] = keyfn.position(pose, pt[c]);
+    keyfn.table(w, key);
 #pragma unroll
     for (int c = 0; c < ORD_PER_LANE; ++c) {
         const uint32_t e = order_element(tile, c);
-        if (e < seg_len) {
-            const uint32_t key = keyfn.key(pose, pt[c]);
-            keys[seg_start + e] = (uint16_t)key;
-            atomicAdd(&h[key], 1u); // integer: order independent
-        }
+        if (e < seg_len) keys[seg_start + e] = (uint16_t)key[c];
     }
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c)
+        if (order_element(tile, c) < seg_len) atomicAdd(&h[key[c]], 1u); // integer: order independent
     __syncthreads();
     for (int d = threadIdx.x; d < ORD_BINS; d += ORD_BLK) dst[d] = h[d];
 }
@@ -210,11 +227,13 @@ __device__ __forceinline__ void order_scatter_body(const OrderSrc &s, const uint
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    uint32_t id[ORD_PER_LANE];
+    uint32_t id[ORD_PER_LANE]; // (the test for src_idx around the whole loop, as in order_hist_body; elements past the end read the last id and store nothing)
+    if (s.src_idx) {
 #pragma unroll
-    for (int c = 0; c < ORD_PER_LANE; ++c) {
-        const uint32_t e = order_element(tile, c);
-        id[c] = valid[c] ? (s.src_idx ? s.src_idx[seg_start + e] : seg_start + e) : 0u;
+        for (int c = 0; c < ORD_PER_LANE; ++c) id[c] = s.src_idx[seg_start + min(order_element(tile, c), seg_len - 1u)];
+    } else {
+#pragma unroll
+        for (int c = 0; c < ORD_PER_LANE; ++c) id[c] = seg_start + order_element(tile, c);
     }
 #pragma unroll
     for (int c = 0; c < ORD_PER_LANE; ++c)
@@ -285,8 +304,6 @@ __device__ __forceinline__ void order_move_body(const OrderSrc &s, const uint16_
         key[c] = valid[c] ? (uint32_t)keys[seg_start + e] : 0u;
     }
 #pragma unroll
-    for (int c = 0; c < ORD_PER_LANE; ++c) vx[c] = valid[c] ? sx[seg_start + order_element(tile, c)] : 0.0f; // in flight while the tile is ranked
-#pragma unroll
     for (int c = 0; c < ORD_PER_LANE; ++c)
         if (valid[c]) atomicAdd(&L.ctr[wv][key[c]], 1u);
     __syncthreads();
@@ -330,6 +347,11 @@ __device__ __forceinline__ void order_move_body(const OrderSrc &s, const uint16_
         }
     }
     __syncthreads();
+    // the x plane: in flight while the tile is ranked.  Requested here, behind the counting, so that the wait in front of the counting
+    // covers the key loads alone (requested beside them it held the counting back for 16 more loads).  The y and z planes follow behind
+    // the ranking; the compiler drains all three, vmcnt(0), in front of the first plane's LDS writes (profiles/LADDER.md, round 11)
+#pragma unroll
+    for (int c = 0; c < ORD_PER_LANE; ++c) vx[c] = valid[c] ? sx[seg_start + order_element(tile, c)] : 0.0f;
     const unsigned long long below = (1ull << lane) - 1ull;
     uint32_t slot[ORD_PER_LANE];
 #pragma unroll
