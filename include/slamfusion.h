@@ -382,7 +382,8 @@ int sf_cloud_remove_boxes(sf_cloud *c, const double *center /* [B][3] */, const 
                           int64_t n_boxes /* 0 .. 1024 */, double margin, int keep_inside, int64_t *n_inside);
 /* FPFH descriptors and descriptor matching (extension, no reference code; pcl::FPFHEstimation, Open3D compute_fpfh_feature and
  * the nearest-descriptor correspondences both libraries feed to a global registration; DESIGN §21, restated in
- * tests/fpfh_ref_np.py).  The first step from "refine a pose" to "find a pose": estimating the pose from the matches is not here.
+ * tests/fpfh_ref_np.py).  The first step from "refine a pose" to "find a pose": estimating the pose from the matches is
+ * sf_cloud_register_pairs, below.
  * sf_features: n rows of SF_FPFH_DIM float32 and one validity byte per row on the device, in the ORIGINAL point order of whatever
  *   produced them.  A row that holds a non-finite value is invalid whatever flag came with it (valid NULL: every row is offered as
  *   valid); the byte always comes out as 0 or 1.  download: cap >= n rows, *n = n (SF_ERR_INVALID when cap is too small, *n set).
@@ -444,6 +445,57 @@ int sf_cloud_compute_fpfh(sf_cloud *c, double normal_radius, const sf_fpfh_param
 int sf_features_match(sf_features *src, sf_features *dst, const sf_match_params *p,
                       int32_t *idx /* [n_src] */, float *dist2 /* [n_src] */, float *second2 /* [n_src] or NULL */,
                       int32_t *pairs /* [cap][2] or NULL */, int64_t cap_pairs, sf_match_stats *stats);
+/* RANSAC pose estimation from descriptor matches (extension, no reference code; pcl::SampleConsensusPrerejective, Open3D
+ * registration_ransac_based_on_correspondence; DESIGN §22, restated in tests/reg_ref_np.py).  The consumer of sf_features_match:
+ * src and dst are two clouds of one context, pairs [m][2] int32 the (i, j) that sf_features_match returns, i into src, j into dst.
+ *   pairs       an index outside its cloud: SF_ERR_INVALID, nothing touched.  A pair with a non-finite point is never an inlier and
+ *               makes every hypothesis that samples it degenerate (NaN arithmetic).  Scoring runs over the m pairs, not over a
+ *               nearest-neighbour search of the whole source.
+ *   samples     mix = the splitmix64 step of sf_cloud_segment_plane; hypothesis h of num_hypotheses samples the pairs
+ *               k_j = mix(seed + 0x9E3779B97F4A7C15 (3h + j + 1)) mod m, j = 0, 1, 2; (s_j, t_j) are their points widened to float64.
+ *   hypothesis  on the device, float64, unfused, in the order written (sums and dot products left to right over x, y, z).
+ *               status 1 (degenerate): two equal k_j; c = (s1 - s0) x (s2 - s0), cc = cx cx; cc = cc + cy cy; cc = cc + cz cz not > 0 or
+ *               not finite, likewise for t; or the resulting transform is not finite.  status 2 (rejected): edge_similarity > 0 and
+ *               for an edge (a, b) of (0,1), (0,2), (1,2) not (ls2 >= e2 * lt2 && lt2 >= e2 * ls2), ls2 = |s_a - s_b|^2,
+ *               lt2 = |t_a - t_b|^2 (dx dx, + dy dy, + dz dz), e2 = edge_similarity * edge_similarity -- squared lengths, no square
+ *               root.  status 0 otherwise: cs = ((s0 + s1) + s2) / 3, ct likewise, H_ab = sum_j (s_j - cs)_a (t_j - ct)_b in ascending j,
+ *               Horn's symmetric 4x4 matrix of H solved by the Jacobi eigen-solve of the library, q = the eigenvector of the largest
+ *               eigenvalue (the first index on a tie) divided by its norm and signed q_w >= 0, R the rotation of q (always proper),
+ *               t = ct - R cs.  T is row-major 4x4, src -> dst.  Statuses 1 and 2 carry sixteen NaNs.
+ *   score       float32, unfused: Tf = the twelve entries of [R | t] rounded to float32, t2 = (float)(distance_threshold *
+ *               distance_threshold); qx = Tf00 x; qx = qx + Tf01 y; qx = qx + Tf02 z; qx = qx + Tf03, likewise qy, qz; dx = qx - tx,
+ *               dy, dz; d2 = dx dx; d2 = d2 + dy dy; d2 = d2 + dz dz; the pair is an inlier iff d2 < t2.  count_h = the inliers, 0 for
+ *               status 1 and 2.
+ *   choice      the largest count, on a tie the smallest h (all counts 0: h = 0).  Below min_inliers: found = 0, T = the identity, no
+ *               inlier, SF_OK.  top [top_k] (may be NULL when top_k = 0): the best in (count descending, h ascending) order, only
+ *               status 0 with count > 0; stats->n_top of them are written.
+ *   refit       refine_rounds times: over the inliers of the current Tf the float64 record (n, sum s', sum t', sum s' t'^T) with
+ *               s' = s - s_ref, t' = t - t_ref, the references being sample 0 of the chosen hypothesis; H = sum s' t'^T -
+ *               (sum s')(sum t')^T / n, cs = s_ref + sum s' / n, ct likewise, then the same solve.  Fewer than 3 inliers or a
+ *               transform that is not finite: the previous transform stands and the rounds end (rounds_done counts the others).
+ *   outputs     T [16]; inlier [m] (may be NULL) and n_inliers under the final Tf; fitness = n_inliers / m; rmse =
+ *               sqrt(sum (double)d2 / n_inliers) (0 without inliers), the sum taken over tiles of 256 consecutive pairs (a non-inlier
+ *               adds 0): within each 64 a balanced binary tree over adjacent pairs, the four 64s left to right, the tiles in
+ *               ascending order.  Integer atomics only, every order fixed by m and the parameters: the same call returns the same bits.
+ * SF_ERR_INVALID, nothing touched: num_hypotheses outside 1 .. 2^20; refine_rounds outside 0 .. 8; min_inliers < 3; top_k outside
+ * 0 .. 64; a threshold that is not finite and > 0; an edge_similarity that is NaN or > 1; clouds of different contexts; m < 0 or
+ * m >= 2^31.  m < 3 or an empty cloud: SF_OK, found = 0, zero stats (pair_hypotheses: every status 1, samples -1; score_poses: zero
+ * counts).  No call modifies a cloud or its last indices.  profile != 0: hyp_ms (gather and hypotheses), score_ms (compaction,
+ * scoring, choice) and refit_ms (refit rounds and final flags) are device-event times, otherwise -1.
+ * sf_cloud_pair_hypotheses: the first two stages alone.  sf_cloud_score_poses: the scoring stage alone on n_poses (1 .. 2^20)
+ * uploaded float32 transforms T12 [n_poses][12] (the rows of [R | t]). */
+typedef struct { double distance_threshold, edge_similarity; int32_t num_hypotheses, refine_rounds; int64_t min_inliers;
+                 int32_t top_k, profile; uint64_t seed; } sf_reg_params;
+typedef struct { int32_t h, status; int64_t count; double T[16]; } sf_reg_candidate;
+typedef struct { int64_t n_pairs, n_degenerate, n_rejected, n_scored, best, best_count, n_inliers; int32_t found, rounds_done;
+                 double fitness, rmse; float hyp_ms, score_ms, refit_ms; int32_t n_top; } sf_reg_stats;
+void sf_reg_default_params(sf_reg_params *p);       /* threshold 0 (to be set), similarity 0.9, 4096, 2 rounds, min_inliers 3, top_k 0, seed 0 */
+int sf_cloud_register_pairs(sf_cloud *src, sf_cloud *dst, const int32_t *pairs /* [m][2] */, int64_t m, const sf_reg_params *p,
+                            double *T /* [16] */, uint8_t *inlier /* [m] or NULL */, sf_reg_candidate *top /* [top_k] or NULL */, sf_reg_stats *stats);
+int sf_cloud_pair_hypotheses(sf_cloud *src, sf_cloud *dst, const int32_t *pairs /* [m][2] */, int64_t m, const sf_reg_params *p,
+                             int32_t *samples /* [H][3] or NULL */, int32_t *status /* [H] */, double *T /* [H][16] or NULL */);
+int sf_cloud_score_poses(sf_cloud *src, sf_cloud *dst, const int32_t *pairs /* [m][2] */, int64_t m, const float *T12 /* [n_poses][12] */,
+                         int64_t n_poses, double distance_threshold, int64_t *counts /* [n_poses] */);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */
@@ -1087,6 +1139,13 @@ int sf_test_reduce_partials(sf_ctx *ctx, int nrec /* 11 | 17 | 24 | 30 */, int n
 /* sf_cloud_score_planes with the grid of its scoring kernel capped at max_blocks workgroups (0: the production choice, at most
  * 65536), so that a small cloud exercises the path where one workgroup takes several tiles. */
 int sf_test_plane_score(sf_cloud *c, const float *planes, int64_t n_planes, double t, int max_blocks, int64_t *counts);
+
+/* sf_cloud_score_poses with the first grid dimension of its scoring kernel capped at max_blocks workgroups (0: the production
+ * choice; a lane then takes several transforms) and the pairs split into slices of pair_chunk (0: the production choice; the
+ * slices of a transform meet in one integer atomic each), so that a small case runs on 1 and 3 workgroups and through the path
+ * that splits the pairs.  SF_ERR_INVALID: max_blocks outside 0 .. 65536, pair_chunk < 0. */
+int sf_test_score_poses(sf_cloud *src, sf_cloud *dst, const int32_t *pairs, int64_t m, const float *T12, int64_t n_poses,
+                        double distance_threshold, int max_blocks, int64_t pair_chunk, int64_t *counts);
 
 /* sf_cloud_label_boxes with the grid of its three segmented passes capped at max_blocks workgroups (0: the production choice, at
  * most 1024), so that a small cloud exercises the path where one workgroup walks several tiles and carries the open segment

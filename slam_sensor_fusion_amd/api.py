@@ -205,6 +205,50 @@ def _fpfh_params(radius, orient, toward, profile):
     return p
 
 
+class RegParams(C.Structure):
+    """sf_reg_params: what a pose estimation from matches is asked for (sf_reg_default_params: threshold to be set, edge similarity 0.9,
+    4096 hypotheses, 2 refit rounds, min_inliers 3, top_k 0, seed 0)."""
+    _fields_ = [("distance_threshold", C.c_double), ("edge_similarity", C.c_double), ("num_hypotheses", C.c_int32), ("refine_rounds", C.c_int32),
+                ("min_inliers", C.c_int64), ("top_k", C.c_int32), ("profile", C.c_int32), ("seed", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(distance_threshold=float(self.distance_threshold), edge_similarity=float(self.edge_similarity), num_hypotheses=int(self.num_hypotheses),
+                    refine_rounds=int(self.refine_rounds), min_inliers=int(self.min_inliers), top_k=int(self.top_k), profile=int(self.profile), seed=int(self.seed))
+
+
+class RegCandidate(C.Structure):
+    """sf_reg_candidate (144 bytes): one of the best hypotheses -- its index, status (always 0), inlier count and transform."""
+    _fields_ = [("h", C.c_int32), ("status", C.c_int32), ("count", C.c_int64), ("T", C.c_double * 16)]
+
+    def as_dict(self):
+        return dict(h=int(self.h), status=int(self.status), count=int(self.count), T=np.array(self.T, dtype=np.float64).reshape(4, 4))
+
+
+class RegStats(C.Structure):
+    """sf_reg_stats: n_scored = the hypotheses that were neither degenerate nor rejected; best / best_count: the winning hypothesis and
+    its inliers; n_inliers, fitness, rmse: those of the final transform; n_top: the candidates returned; the times: -1 unless profiled."""
+    _fields_ = [(name, C.c_int64) for name in ("n_pairs", "n_degenerate", "n_rejected", "n_scored", "best", "best_count", "n_inliers")] + \
+               [("found", C.c_int32), ("rounds_done", C.c_int32), ("fitness", C.c_double), ("rmse", C.c_double), ("hyp_ms", C.c_float), ("score_ms", C.c_float),
+                ("refit_ms", C.c_float), ("n_top", C.c_int32)]
+
+    def as_dict(self):
+        return {name: (int if kind in (C.c_int64, C.c_int32) else float)(getattr(self, name)) for name, kind in self._fields_}
+
+
+def _reg_params(distance_threshold, edge_similarity, num_hypotheses, refine_rounds, min_inliers, top_k, seed, profile):
+    """The keyword form of the registration calls -> RegParams."""
+    p = RegParams()
+    load_library().sf_reg_default_params(C.byref(p))
+    p.distance_threshold, p.edge_similarity, p.num_hypotheses = float(distance_threshold), float(edge_similarity), int(num_hypotheses)
+    p.refine_rounds, p.min_inliers, p.top_k = int(refine_rounds), int(min_inliers), int(top_k)
+    p.seed, p.profile = int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(profile))
+    return p
+
+
+def _pairs(pairs):
+    return np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
@@ -284,6 +328,11 @@ def load_library():
     lib.sf_map_compute_spfh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_cloud_compute_fpfh.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     lib.sf_features_match.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_reg_default_params.restype = None
+    lib.sf_cloud_register_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_pair_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]
+    lib.sf_test_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int64, C.c_void_p]
     lib.sf_test_launch_schedule.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -362,6 +411,16 @@ def hook_plane_score(cloud, planes, distance_threshold, max_blocks=0):
     planes = _f32(planes).reshape(-1, 4)
     counts = np.empty(len(planes), np.int64)
     _check(cloud.lib.sf_test_plane_score(cloud.h, _p(planes), len(planes), float(distance_threshold), int(max_blocks), _p(counts)))
+    return counts
+
+
+def hook_score_poses(src, dst, pairs, T12, distance_threshold, max_blocks=0, pair_chunk=0):
+    """Test hook (sf_test_score_poses): Cloud.score_poses with the first grid dimension of the scoring kernel capped at max_blocks
+    workgroups and the pairs split into slices of pair_chunk (0: as in production)."""
+    pairs, T12 = _pairs(pairs), _f32(T12).reshape(-1, 12)
+    counts = np.empty(len(T12), np.int64)
+    _check(src.lib.sf_test_score_poses(src.h, dst.h, _p(pairs), C.c_int64(len(pairs)), _p(T12), C.c_int64(len(T12)), C.c_double(distance_threshold), C.c_int(int(max_blocks)),
+                                       C.c_int64(int(pair_chunk)), _p(counts)))
     return counts
 
 
@@ -737,6 +796,36 @@ class Cloud:
         p, st, out = _fpfh_params(radius, orient, toward, profile), FpfhStats(), Features(self.ctx)
         _check(self.lib.sf_cloud_compute_fpfh(self.h, C.c_double(normal_radius), C.byref(p), C.c_float(cell), out.h, C.byref(st)))
         return out, st.as_dict()
+
+    def pair_hypotheses(self, other, pairs, edge_similarity=0.9, num_hypotheses=4096, seed=0):
+        """sf_cloud_pair_hypotheses: the hypotheses a register_pairs with these parameters builds -> (samples int32 [H, 3], the sampled
+        pairs; status int32 [H]: 0, 1 degenerate, 2 rejected by the edge check; T float64 [H, 4, 4], NaN unless status 0)."""
+        pairs, p = _pairs(pairs), _reg_params(1.0, edge_similarity, num_hypotheses, 0, 3, 0, seed, False)
+        h = max(int(num_hypotheses), 0)
+        samples, status, T = np.empty((h, 3), np.int32), np.empty(h, np.int32), np.empty((h, 4, 4), np.float64)
+        _check(self.lib.sf_cloud_pair_hypotheses(self.h, other.h, _p(pairs), C.c_int64(len(pairs)), C.byref(p), _p(samples), _p(status), _p(T)))
+        return samples, status, T
+
+    def score_poses(self, other, pairs, T12, distance_threshold):
+        """sf_cloud_score_poses: the pairs each float32 transform (the rows of [R | t], [H, 12] or [H, 3, 4]) brings within
+        distance_threshold under the score rule -> int64 [H]."""
+        pairs, T12 = _pairs(pairs), _f32(T12).reshape(-1, 12)
+        counts = np.empty(len(T12), np.int64)
+        _check(self.lib.sf_cloud_score_poses(self.h, other.h, _p(pairs), C.c_int64(len(pairs)), _p(T12), C.c_int64(len(T12)), C.c_double(distance_threshold), _p(counts)))
+        return counts
+
+    def register_pairs(self, other, pairs, distance_threshold, edge_similarity=0.9, num_hypotheses=4096, refine_rounds=2, min_inliers=3, top_k=0, seed=0,
+                       profile=False):
+        """sf_cloud_register_pairs (pcl::SampleConsensusPrerejective, Open3D registration_ransac_based_on_correspondence): the pose
+        that maps this cloud into `other`, estimated from the matched pairs (i into this cloud, j into other, as Features.match returns
+        them): three-pair hypotheses, the edge-length pre-rejection, inlier counts over all pairs, a least-squares refit over the
+        inliers -> dict(T float64 [4, 4], found, inlier bool [m], top: list of dict(h, status, count, T), stats).  Neither cloud is
+        modified.  No hypothesis with min_inliers: found = 0, T the identity, no inlier."""
+        pairs, p = _pairs(pairs), _reg_params(distance_threshold, edge_similarity, num_hypotheses, refine_rounds, min_inliers, top_k, seed, profile)
+        T, inlier, st = np.zeros((4, 4), np.float64), np.zeros(len(pairs), np.uint8), RegStats()
+        top = (RegCandidate * max(int(top_k), 1))()
+        _check(self.lib.sf_cloud_register_pairs(self.h, other.h, _p(pairs), C.c_int64(len(pairs)), C.byref(p), _p(T), _p(inlier), top, C.byref(st)))
+        return dict(T=T, found=int(st.found), inlier=inlier.astype(bool), top=[top[k].as_dict() for k in range(int(st.n_top))], stats=st.as_dict())
 
     def last_indices(self):
         n = C.c_int64()
@@ -1458,6 +1547,30 @@ class Icp:
             self.close()
         except Exception:
             pass
+
+
+def global_register(src_cloud, src_features, dst_cloud, dst_features, distance_threshold, ratio=0, edge_similarity=0.9, num_hypotheses=4096, refine_rounds=2,
+                    min_inliers=3, top_k=0, seed=0, icp=None, icp_mode="o3d_p2p", profile=False):
+    """Pose of src_cloud in dst_cloud without a prior: the mutual matches of the two descriptor sets, then Cloud.register_pairs on them.
+    icp: None, or a factory icp(batch) -> an Icp with its target set; the top_k candidates and the refit pose are then refined as ONE
+    batch of the batched ICP and the result with the best (fitness, -rmse) is returned.
+    -> dict(T float64 [4, 4], found, fitness, rmse, pairs, match_stats, ransac: the register_pairs dict, icp: the batch results or None,
+    chosen: the index into the batch, the refit pose last, or None)."""
+    match = src_features.match(dst_features, ratio=ratio, mutual=True, profile=profile)
+    reg = src_cloud.register_pairs(dst_cloud, match["pairs"], distance_threshold, edge_similarity, num_hypotheses, refine_rounds, min_inliers, top_k, seed, profile)
+    out = dict(T=reg["T"], found=reg["found"], fitness=reg["stats"]["fitness"], rmse=reg["stats"]["rmse"], pairs=match["pairs"], match_stats=match["stats"], ransac=reg,
+               icp=None, chosen=None)
+    if icp is None or not reg["found"]:
+        return out
+    inits = [c["T"] for c in reg["top"]] + [reg["T"]]
+    scan = src_cloud.download()
+    solver = icp(len(inits))
+    solver.set_source_batch(np.broadcast_to(scan, (len(inits),) + scan.shape))
+    solver.set_initial_batch(np.stack(inits))
+    res = solver.align_batch(icp_mode)
+    chosen = max(range(len(res)), key=lambda k: (res[k]["fitness"], -res[k]["rmse"], k))
+    out.update(T=res[chosen]["T64"], fitness=res[chosen]["fitness"], rmse=res[chosen]["rmse"], icp=res, chosen=chosen)
+    return out
 
 
 def align_group(members, mode):

@@ -233,3 +233,48 @@ def make_tunnel(length_m=200.0, half_width_m=4.0, wall_m=2.0, height_m=30.0, m_p
     pts = sample_city(boxes, length_m, m_points, sigma=sigma, seed=seed)
     keep = (np.abs(pts[:, 1]) < half_width_m + 0.5) & (np.abs(pts[:, 0]) < keep_x)
     return boxes, pts[keep]
+
+
+def make_terrain(extent_m, spacing, seed):
+    """A scene with shape in it, for descriptors (the city of make_city is all planes): a height field over the square of side
+    extent_m about the origin, sampled every `spacing` metres with a jitter of a fifth of it -- the sum of five sinusoids of
+    incommensurate wavelengths between 2 and 9 m, and on it a few dozen spheres and upright cylinders of differing radii (the upper
+    surface counts: a sphere's cap, a cylinder's flat top).  float32 [n, 3], a function of the arguments alone; normals come from
+    Map.estimate_normals as for any other cloud."""
+    rng = np.random.default_rng(seed)
+    half = 0.5 * float(extent_m)
+    g = np.arange(-half, half + 0.5 * spacing, spacing)
+    x, y = (v.ravel() for v in np.meshgrid(g, g, indexing="ij"))
+    x = np.clip(x + rng.uniform(-0.2, 0.2, x.shape) * spacing, -half, half)
+    y = np.clip(y + rng.uniform(-0.2, 0.2, y.shape) * spacing, -half, half)
+    wavelengths = np.array([2.0, 2.0 * np.sqrt(2.0), 3.0 * np.sqrt(3.0), 2.0 * np.e, 9.0])
+    heading, phase = rng.uniform(0, 2 * np.pi, 5), rng.uniform(0, 2 * np.pi, 5)
+    amplitude = 0.06 * wavelengths * rng.uniform(0.7, 1.3, 5)
+    z = np.zeros_like(x)
+    for lam, th, ph, a in zip(wavelengths, heading, phase, amplitude):
+        z += a * np.sin(2 * np.pi * (x * np.cos(th) + y * np.sin(th)) / lam + ph)
+    ground = z.copy()
+    n_obj = int(np.clip(round(float(extent_m) ** 2 / 25.0), 12, 48))
+    for k in range(n_obj):
+        cx, cy, r = rng.uniform(-half, half), rng.uniform(-half, half), rng.uniform(0.5, 1.6)
+        d2 = (x - cx) ** 2 + (y - cy) ** 2
+        inside = d2 < r * r
+        if not inside.any():
+            continue
+        base = ground[inside].mean()
+        if k % 2 == 0:                                   # a sphere resting half sunk: its cap above the base
+            top = base + np.sqrt(np.maximum(r * r - d2[inside], 0.0))
+        else:                                            # an upright cylinder with a flat top
+            top = np.full(int(inside.sum()), base + rng.uniform(0.8, 2.5))
+        z[inside] = np.maximum(z[inside], top)
+    return np.stack([x, y, z], axis=1).astype(np.float32)
+
+
+def make_local_scan(points, spot, radius, T, sigma=NOISE_SIGMA, seed=0):
+    """The points within `radius` of `spot` (x, y) as a sensor under the unknown pose T sees them: T maps the scan into the frame of
+    `points`, so the scan is T^-1 applied to them, plus sigma noise.  -> (scan float32 [k, 3], the indices of its points)"""
+    pts = np.asarray(points, np.float32)
+    idx = np.flatnonzero((pts[:, 0].astype(np.float64) - spot[0]) ** 2 + (pts[:, 1].astype(np.float64) - spot[1]) ** 2 < float(radius) ** 2)
+    rng = np.random.default_rng(seed)
+    local = (pts[idx].astype(np.float64) - T[:3, 3]) @ T[:3, :3] + rng.normal(0.0, sigma, (len(idx), 3))
+    return local.astype(np.float32), idx
