@@ -496,6 +496,48 @@ int sf_cloud_pair_hypotheses(sf_cloud *src, sf_cloud *dst, const int32_t *pairs 
                              int32_t *samples /* [H][3] or NULL */, int32_t *status /* [H] */, double *T /* [H][16] or NULL */);
 int sf_cloud_score_poses(sf_cloud *src, sf_cloud *dst, const int32_t *pairs /* [m][2] */, int64_t m, const float *T12 /* [n_poses][12] */,
                          int64_t n_poses, double distance_threshold, int64_t *counts /* [n_poses] */);
+/* ISS keypoints and keypoint-restricted descriptor sets (extension, no reference code; Intrinsic Shape Signatures, Zhong 2009:
+ * Open3D compute_iss_keypoints, the unweighted form of pcl::ISSKeypoint3D; DESIGN §23, restated in tests/iss_ref_np.py).  The step in
+ * front of the FPFH / match / RANSAC chain: which few hundred points are worth describing and matching.  Every per-point output
+ * is in ORIGINAL point order.
+ * Neighbours.  rs2 = (float)(salient_radius * salient_radius); N_i = the indexed points j with d2(x_i, x_j) < rs2 under the float32,
+ *   unfused, strict rule of sf_map_radius_outliers, the point itself included; count_i = |N_i| is that call's count (the same walk,
+ *   the same proof that nothing is lost; symmetric bit for bit).  The window is ignored; the map's index, normals, covariances
+ *   and neighbour table are not modified; normals are not needed.
+ * Scatter, float64, unfused, in the order written, centred on the point itself: per neighbour d_a = (double)x_j[a] - (double)x_i[a]
+ *   (exact); in the order the index walks them s_a = s_a + d_a and q_ab = q_ab + d_a * d_b for ab = xx, xy, xz, yy, yz, zz; then
+ *   n = count_i, m_a = s_a / n, C_ab = q_ab / n - m_a * m_b: the unweighted covariance about the neighbourhood mean (Open3D's form;
+ *   PCL's scatter about the query point is not offered).
+ * Eigenvalues.  The Jacobi eigen-solve of the library on C; the three diagonal values sorted descending, each clamped to
+ *   max(lambda, 0): lambda1 >= lambda2 >= lambda3 >= 0.  A point that is not indexed: count 0, three zeros, salient = 0.
+ * Salient, compared in float64: count_i >= min_neighbors && lambda2 < gamma_21 * lambda1 && lambda3 < gamma_32 * lambda2 &&
+ *   lambda3 > min_lambda3.  The products stand in for the libraries' quotients, so a degenerate neighbourhood (collinear, a single
+ *   point) is simply not salient and no NaN arises.  min_lambda3 is an absolute floor in m^2 (not in Open3D): it keeps an exactly or
+ *   nearly planar edge, whose lambda3 is rounding noise, out of the competition below.
+ * Non-maximum suppression.  rn2 = (float)(non_max_radius * non_max_radius), c_i = the count under the same rule at rn2 (the point
+ *   itself included).  i is a keypoint iff it is salient, c_i >= min_neighbors, and no salient j != i with d2(x_i, x_j) < rn2 has
+ *   lambda3_j > lambda3_i, or lambda3_j == lambda3_i and j < i in original order.  Points that are not salient never suppress.
+ *   (Open3D keeps both members of a tie; here the smallest original index of equal maxima wins: coincident points, one keypoint.)
+ * Outputs.  indices: the keypoints in ascending original index, truncated at cap; *n_keypoints counts them all; flags [n]: 1 / 0 per
+ *   point; stats: n_valid = the indexed points, n_salient, n_keypoints, max_neighbors = the largest count_i; profile != 0:
+ *   saliency_ms / nms_ms are the device-event times of the two passes, otherwise both are -1.  Integer atomics serve the counts
+ *   only: the same call on the same index returns the same bits, sf_map_iss_keypoints computes the very lambda that
+ *   sf_map_iss_saliency returns (one kernel), and another cell moves s and q by their float64 rounding, nothing else.
+ * SF_ERR_INVALID, nothing touched: a radius that is not finite and > 0, a gamma that is NaN or not in (0, 1], a min_lambda3 that is
+ *   NaN or negative, min_neighbors < 1, cap < 0, indices == NULL with cap > 0.  SF_ERR_STATE: a map that is not built.  An empty map
+ *   is SF_OK with zero stats.
+ * sf_cloud_iss_keypoints: a temporary map of the cloud (`cell` as in sf_map_build, 0 = automatic), then the device code of
+ *   sf_map_iss_keypoints: bit for bit what those two calls give.  The cloud and its last indices are not modified.
+ * sf_features_gather: row r of out = row rows[r] of src with its validity byte, in the order given (repeats allowed); k = 0
+ *   empties out.  SF_ERR_INVALID, nothing touched: an index outside src, out == src, different contexts, k < 0. */
+typedef struct { double salient_radius, non_max_radius, gamma_21, gamma_32, min_lambda3; int32_t min_neighbors, profile; } sf_iss_params;
+typedef struct { int64_t n_points, n_valid, n_salient, n_keypoints, max_neighbors; float saliency_ms, nms_ms; } sf_iss_stats;
+void sf_iss_default_params(sf_iss_params *p);   /* radii 0 (to be set), gammas 0.975, min_lambda3 0, min_neighbors 5, no profile */
+int sf_map_iss_saliency(sf_map *m, const sf_iss_params *p, double *lambda /* [n][3] */, int32_t *n_neighbors /* [n] */, uint8_t *salient /* [n] */);  /* any may be NULL */
+int sf_map_iss_keypoints(sf_map *m, const sf_iss_params *p, int32_t *indices /* [cap] or NULL */, int64_t cap, int64_t *n_keypoints,
+                         uint8_t *flags /* [n] or NULL */, sf_iss_stats *stats);
+int sf_cloud_iss_keypoints(sf_cloud *c, const sf_iss_params *p, float cell, int32_t *indices, int64_t cap, int64_t *n_keypoints, sf_iss_stats *stats);
+int sf_features_gather(sf_features *src, const int32_t *rows /* [k] */, int64_t k, sf_features *out);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */

@@ -249,6 +249,39 @@ def _pairs(pairs):
     return np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
 
 
+class IssParams(C.Structure):
+    """sf_iss_params: the two radii, the two eigenvalue ratios, the absolute floor of lambda3 (m^2), the least neighbour count and the
+    profile switch (sf_iss_default_params: radii to be set, gammas 0.975, no floor, 5 neighbours)."""
+    _fields_ = [(name, C.c_double) for name in ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_lambda3")] + \
+               [("min_neighbors", C.c_int32), ("profile", C.c_int32)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_double else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+class IssStats(C.Structure):
+    """sf_iss_stats: n_valid = the indexed points, n_salient, n_keypoints, max_neighbors = the largest count at the salient radius;
+    saliency_ms / nms_ms: -1 unless profiled."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_valid", "n_salient", "n_keypoints", "max_neighbors")] + \
+               [("saliency_ms", C.c_float), ("nms_ms", C.c_float)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+def _iss_params(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, min_lambda3, profile):
+    """The keyword form of the ISS calls -> IssParams."""
+    p = IssParams()
+    load_library().sf_iss_default_params(C.byref(p))
+    p.salient_radius, p.non_max_radius, p.gamma_21, p.gamma_32 = float(salient_radius), float(non_max_radius), float(gamma_21), float(gamma_32)
+    p.min_lambda3, p.min_neighbors, p.profile = float(min_lambda3), int(min_neighbors), int(bool(profile))
+    return p
+
+
+def _rows(indices):
+    return np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int32)
+
+
 _lib = None
 _live = weakref.WeakSet()   # every wrapper object, closed in dependency order at exit
 
@@ -333,7 +366,12 @@ def load_library():
     lib.sf_cloud_pair_hypotheses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_cloud_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]
     lib.sf_test_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int64, C.c_void_p]
-    lib.sf_test_launch_schedule.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    lib.sf_iss_default_params.restype = None
+    lib.sf_map_iss_saliency.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_map_iss_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_iss_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.sf_features_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_test_launch_schedule.argtypes =[C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_test_query_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -797,6 +835,14 @@ class Cloud:
         _check(self.lib.sf_cloud_compute_fpfh(self.h, C.c_double(normal_radius), C.byref(p), C.c_float(cell), out.h, C.byref(st)))
         return out, st.as_dict()
 
+    def iss_keypoints(self, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, min_lambda3=0.0, profile=False, cell=0.0):
+        """sf_cloud_iss_keypoints: a temporary map of the cloud, then Map.iss_keypoints -> dict(indices int32 [k] ascending, stats);
+        bit for bit what those two calls give.  The cloud and its last indices stay as they are."""
+        p, st, n, nk = _iss_params(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, min_lambda3, profile), IssStats(), len(self), C.c_int64()
+        idx = np.zeros(max(n, 1), np.int32)
+        _check(self.lib.sf_cloud_iss_keypoints(self.h, C.byref(p), C.c_float(cell), _p(idx), C.c_int64(n), C.byref(nk), C.byref(st)))
+        return dict(indices=idx[:nk.value].copy(), stats=st.as_dict())
+
     def pair_hypotheses(self, other, pairs, edge_similarity=0.9, num_hypotheses=4096, seed=0):
         """sf_cloud_pair_hypotheses: the hypotheses a register_pairs with these parameters builds -> (samples int32 [H, 3], the sampled
         pairs; status int32 [H]: 0, 1 degenerate, 2 rejected by the edge check; T float64 [H, 4, 4], NaN unless status 0)."""
@@ -1061,6 +1107,27 @@ class Map:
         _check(self.lib.sf_map_compute_spfh(self.h, C.byref(p), _p(counts), _p(pairs)))
         return counts, pairs
 
+    def iss_saliency(self, salient_radius, non_max_radius=None, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, min_lambda3=0.0):
+        """sf_map_iss_saliency: the first pass of iss_keypoints -> dict(lambda float64 [n, 3] descending, n_neighbors int32 [n] (the
+        count of radius_outliers at salient_radius), salient bool [n]), original point order; zeros for points that are not indexed.
+        non_max_radius plays no part in it (None: the salient radius stands in, the parameters are checked together)."""
+        n = len(self)
+        p = _iss_params(salient_radius, salient_radius if non_max_radius is None else non_max_radius, gamma_21, gamma_32, min_neighbors, min_lambda3, False)
+        lam, cnt, sal = np.zeros((n, 3), np.float64), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        _check(self.lib.sf_map_iss_saliency(self.h, C.byref(p), _p(lam), _p(cnt), _p(sal)))
+        return {"lambda": lam, "n_neighbors": cnt, "salient": sal.astype(bool)}
+
+    def iss_keypoints(self, salient_radius, non_max_radius, gamma_21=0.975, gamma_32=0.975, min_neighbors=5, min_lambda3=0.0, profile=False):
+        """sf_map_iss_keypoints (Open3D compute_iss_keypoints, the unweighted pcl::ISSKeypoint3D): a point is salient when the
+        eigenvalues of the covariance of its neighbours within salient_radius have lambda2 < gamma_21 lambda1, lambda3 < gamma_32
+        lambda2 and lambda3 > min_lambda3 (an absolute floor in m^2), and a keypoint when no salient point within non_max_radius has a
+        larger lambda3 (ties: the smallest index) -> dict(indices int32 [k] ascending, flags bool [n], stats), original point order."""
+        n = len(self)
+        p, st, nk = _iss_params(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors, min_lambda3, profile), IssStats(), C.c_int64()
+        idx, flags = np.zeros(max(n, 1), np.int32), np.zeros(n, np.uint8)
+        _check(self.lib.sf_map_iss_keypoints(self.h, C.byref(p), _p(idx), C.c_int64(n), C.byref(nk), _p(flags), C.byref(st)))
+        return dict(indices=idx[:nk.value].copy(), flags=flags.astype(bool), stats=st.as_dict())
+
     def _clusters(self, call, *args):
         n = len(self)
         labels = np.empty(n, np.int32)
@@ -1194,6 +1261,13 @@ class Features:
         rows, valid = np.zeros((n, FPFH_DIM), np.float32), np.zeros(n, np.uint8)
         _check(self.lib.sf_features_download(self.h, _p(rows), _p(valid), C.c_int64(n), None))
         return rows, valid.astype(bool)
+
+    def gather(self, indices):
+        """sf_features_gather: -> a new Features whose row r is row indices[r] of this set with its validity, in the order given
+        (repeats allowed): the descriptors of chosen points, e.g. of Map.iss_keypoints."""
+        rows, out = _rows(indices), Features(self.ctx)
+        _check(self.lib.sf_features_gather(self.h, _p(rows) if len(rows) else None, C.c_int64(len(rows)), out.h))
+        return out
 
     def match(self, other, ratio=0, mutual=False, max_pairs=None, profile=False):
         """sf_features_match: for every valid row the valid row of `other` with the smallest float32 squared distance (ties: the
@@ -1550,15 +1624,28 @@ class Icp:
 
 
 def global_register(src_cloud, src_features, dst_cloud, dst_features, distance_threshold, ratio=0, edge_similarity=0.9, num_hypotheses=4096, refine_rounds=2,
-                    min_inliers=3, top_k=0, seed=0, icp=None, icp_mode="o3d_p2p", profile=False):
+                    min_inliers=3, top_k=0, seed=0, icp=None, icp_mode="o3d_p2p", profile=False, src_keypoints=None, dst_keypoints=None):
     """Pose of src_cloud in dst_cloud without a prior: the mutual matches of the two descriptor sets, then Cloud.register_pairs on them.
     icp: None, or a factory icp(batch) -> an Icp with its target set; the top_k candidates and the refit pose are then refined as ONE
     batch of the batched ICP and the result with the best (fitness, -rmse) is returned.
-    -> dict(T float64 [4, 4], found, fitness, rmse, pairs, match_stats, ransac: the register_pairs dict, icp: the batch results or None,
-    chosen: the index into the batch, the refit pose last, or None)."""
-    match = src_features.match(dst_features, ratio=ratio, mutual=True, profile=profile)
-    reg = src_cloud.register_pairs(dst_cloud, match["pairs"], distance_threshold, edge_similarity, num_hypotheses, refine_rounds, min_inliers, top_k, seed, profile)
-    out = dict(T=reg["T"], found=reg["found"], fitness=reg["stats"]["fitness"], rmse=reg["stats"]["rmse"], pairs=match["pairs"], match_stats=match["stats"], ransac=reg,
+    src_keypoints / dst_keypoints: None, or an int array of indices into that side's cloud (Cloud.iss_keypoints, Map.iss_keypoints);
+    only those rows of its descriptor set are matched (Features.gather) and the matcher's pairs are mapped back to cloud indices.
+    -> dict(T float64 [4, 4], found, fitness, rmse, pairs (cloud indices), match_stats, ransac: the register_pairs dict, icp: the batch
+    results or None, chosen: the index into the batch, the refit pose last, or None)."""
+    src_rows = None if src_keypoints is None else _rows(src_keypoints)
+    dst_rows = None if dst_keypoints is None else _rows(dst_keypoints)
+    src_set = src_features if src_rows is None else src_features.gather(src_rows)
+    dst_set = dst_features if dst_rows is None else dst_features.gather(dst_rows)
+    match = src_set.match(dst_set, ratio=ratio, mutual=True, profile=profile)
+    pairs = match["pairs"]
+    if src_rows is not None or dst_rows is not None:
+        pairs = pairs.copy()
+        if src_rows is not None:
+            pairs[:, 0] = src_rows[pairs[:, 0]]
+        if dst_rows is not None:
+            pairs[:, 1] = dst_rows[pairs[:, 1]]
+    reg = src_cloud.register_pairs(dst_cloud, pairs, distance_threshold, edge_similarity, num_hypotheses, refine_rounds, min_inliers, top_k, seed, profile)
+    out = dict(T=reg["T"], found=reg["found"], fitness=reg["stats"]["fitness"], rmse=reg["stats"]["rmse"], pairs=pairs, match_stats=match["stats"], ransac=reg,
                icp=None, chosen=None)
     if icp is None or not reg["found"]:
         return out
