@@ -538,6 +538,58 @@ int sf_map_iss_keypoints(sf_map *m, const sf_iss_params *p, int32_t *indices /* 
                          uint8_t *flags /* [n] or NULL */, sf_iss_stats *stats);
 int sf_cloud_iss_keypoints(sf_cloud *c, const sf_iss_params *p, float cell, int32_t *indices, int64_t cap, int64_t *n_keypoints, sf_iss_stats *stats);
 int sf_features_gather(sf_features *src, const int32_t *rows /* [k] */, int64_t k, sf_features *out);
+/* Normal Distributions Transform scan-to-map registration (extension: Magnusson 2009, PCL's NormalDistributionsTransform; DESIGN §24,
+ * restated in tests/ndt_ref_np.py).  No correspondence search and no normals; the basin is about the voxel size.
+ * Target voxels.  The grid index of the target at cell = resolution is the one sf_map_build(m, cloud, resolution) makes (origin,
+ *   float32 binning, table limits; SF_ERR_OVERFLOW when the table does not fit, or holds 2^31 cells or more).  Per occupied cell,
+ *   float64, two passes: count m, mean mu, Sigma = sum (x - mu)(x - mu)^T / (m - 1); the library's Jacobi eigen-solve.  A cell is a
+ *   voxel iff m >= min_points and lambda_max is finite and > 0; then lambda~_i = max(lambda_i, min_eig_ratio * lambda_max),
+ *   cov = V L~ V^T, B = V L~^-1 V^T.  sf_ndt_download_voxels: the voxels in ascending cell id (cell = (z * dims[1] + y) * dims[0] + x);
+ *   mean [n][3], cov and icov [n][6] as xx xy xz yy yz zz; any array may be NULL; cap below the count with an array given is
+ *   SF_ERR_INVALID (*n set).  The same target gives the same bits every build.  sf_ndt_set_target_map takes the map's points in
+ *   their original order: bit for bit what sf_ndt_set_target_cloud of the cloud gives.  A grown map rebuilds its voxels in full.
+ * Objective.  p = outlier_ratio, r = resolution: c1 = 10 (1 - p), c2 = p / r^3, d3 = -ln c2, d1 = -ln(c1 + c2) - d3,
+ *   d2 = -2 ln((-ln(c1 e^-1/2 + c2) - d3) / d1).  y = T x in float64 (rows summed left to right, unfused); grid coordinate
+ *   (y - org) * inv_h in float64; a point with a coordinate < 0 or >= dims has no home cell and contributes nothing (no clamp).
+ *   SF_NDT_DIRECT1: the home cell; SF_NDT_DIRECT7: plus the face neighbours inside the grid.  Each voxel met gives the term
+ *   d1 exp(-(d2 / 2) q^T B q), q = y - mu; the score is their sum (d1 < 0: smaller is better).  gradient and hessian are taken at
+ *   delta = 0 of y(delta) = M(delta) y, delta = (rx, ry, rz, tx, ty, tz), M = [Rz Ry Rx | t] as everywhere in the library; the
+ *   hessian is the full 6 x 6, row-major, symmetric bit for bit.  n_inside: the points that met a voxel; n_terms: the terms.
+ * Step.  H = V L V^T (Jacobi), l~_i = max(|l_i|, hessian_floor * max_j |l_j|), delta = -V L~^-1 V^T g, scaled to step_size when
+ *   longer (radians and metres together), T <- M(delta) T.  An alignment stops after max_iterations steps, or (converged = 1)
+ *   when the applied |delta| < transformation_epsilon.  When an evaluation finds no term, or a Hessian that is all zero or not
+ *   finite, SF_NDT_FLAG_NO_OVERLAP is set, the pose stays as it is and score, gradient and hessian are zeros: no NaN is returned.
+ *   iterations counts the steps taken, modified those in which an eigenvalue was negative or floored.  score, gradient and
+ *   hessian of a result are those at its final pose T (one more pass), bit for bit what sf_ndt_derivatives gives there.
+ * sf_ndt_set_source_batch: batch 1 .. 64 scans of n_per_scan points; sf_ndt_set_source_cloud: one scan (copied).  sf_ndt_align
+ *   aligns entry 0 from init and fills trace [max_iterations + 1][16] (or NULL) with T_0 .. T_iterations, the rest untouched;
+ *   sf_ndt_align_batch takes inits [batch][16] and fills out [batch]: entry b is bit for bit the single alignment of scan b.
+ *   sf_ndt_derivatives evaluates entry 0 at poses [k][16] (T, score, gradient, hessian, n_inside, n_terms are filled).  All
+ *   iterations are enqueued without a host synchronisation; the call waits once.  profile != 0: build_ms / align_ms of
+ *   sf_ndt_stats_read are device-event times of the last voxel build / of the launches of the last alignment or evaluation call
+ *   (sf_ndt_derivatives: of its last 64 poses), otherwise -1.
+ * SF_ERR_INVALID ("bad arguments"), before any device work: NULL handles; resolution <= 0 or not finite; outlier_ratio outside
+ *   (0, 1); min_points < 3; neighbours not 1 or 7; max_iterations outside [0, 1024]; step_size <= 0; batch outside [1, 64]; an
+ *   evaluation or alignment before a target and a source are set.  An empty target or source is no error: NO_OVERLAP. */
+#define SF_NDT_DIRECT1 1
+#define SF_NDT_DIRECT7 7
+#define SF_NDT_FLAG_NO_OVERLAP 1
+typedef struct sf_ndt sf_ndt;
+typedef struct { double resolution, outlier_ratio, step_size, transformation_epsilon, min_eig_ratio, hessian_floor; int32_t min_points, neighbours, max_iterations, profile; } sf_ndt_params;
+typedef struct { double T[16], score, gradient[6], hessian[36]; int64_t n_inside, n_terms; int32_t iterations, converged, modified, flags; } sf_ndt_result;
+typedef struct { int64_t n_points, n_cells, n_occupied, n_voxels; int32_t dims[3]; float build_ms, align_ms; } sf_ndt_stats;
+void sf_ndt_default_params(sf_ndt_params *p);   /* resolution 1, outlier_ratio 0.55, step_size 0.1, transformation_epsilon 1e-4, min_eig_ratio 0.01, hessian_floor 1e-6, min_points 6, DIRECT7, 30 iterations, no profile */
+int sf_ndt_create(sf_ctx *ctx, const sf_ndt_params *p, sf_ndt **out);
+void sf_ndt_destroy(sf_ndt *ndt);
+int sf_ndt_set_target_cloud(sf_ndt *ndt, sf_cloud *cloud);
+int sf_ndt_set_target_map(sf_ndt *ndt, sf_map *map);
+int sf_ndt_download_voxels(sf_ndt *ndt, int64_t *cell, int32_t *count, double *mean, double *cov, double *icov, int64_t cap, int64_t *n);
+int sf_ndt_set_source_cloud(sf_ndt *ndt, sf_cloud *cloud);
+int sf_ndt_set_source_batch(sf_ndt *ndt, const float *xyz, int64_t n_per_scan, int batch);
+int sf_ndt_derivatives(sf_ndt *ndt, const double *poses, int64_t k, sf_ndt_result *out);
+int sf_ndt_align(sf_ndt *ndt, const double init[16], sf_ndt_result *out, double *trace);
+int sf_ndt_align_batch(sf_ndt *ndt, const double *inits, sf_ndt_result *out);
+int sf_ndt_stats_read(sf_ndt *ndt, sf_ndt_stats *out);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */

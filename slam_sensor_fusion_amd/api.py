@@ -278,6 +278,45 @@ def _iss_params(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbor
     return p
 
 
+SF_NDT_DIRECT1, SF_NDT_DIRECT7 = 1, 7
+SF_NDT_FLAG_NO_OVERLAP = 1
+
+
+class NdtParams(C.Structure):
+    """sf_ndt_params (sf_ndt_default_params: resolution 1, outlier_ratio 0.55, step_size 0.1, transformation_epsilon 1e-4,
+    min_eig_ratio 0.01, hessian_floor 1e-6, min_points 6, DIRECT7, 30 iterations, no profile)."""
+    _fields_ = [(name, C.c_double) for name in ("resolution", "outlier_ratio", "step_size", "transformation_epsilon", "min_eig_ratio", "hessian_floor")] + \
+               [(name, C.c_int32) for name in ("min_points", "neighbours", "max_iterations", "profile")]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_double else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+class NdtResult(C.Structure):
+    """sf_ndt_result: the pose, the NDT score with its gradient and full Hessian at that pose (order rx ry rz tx ty tz), the points
+    that met a voxel, the terms, and how the alignment went."""
+    _fields_ = [("T", C.c_double * 16), ("score", C.c_double), ("gradient", C.c_double * 6), ("hessian", C.c_double * 36),
+                ("n_inside", C.c_int64), ("n_terms", C.c_int64), ("iterations", C.c_int32), ("converged", C.c_int32),
+                ("modified", C.c_int32), ("flags", C.c_int32)]
+
+    def as_dict(self):
+        a = lambda f, *shape: np.array(f, dtype=np.float64).reshape(shape)
+        return dict(T64=a(self.T, 4, 4), score=float(self.score), gradient=a(self.gradient, 6), hessian=a(self.hessian, 6, 6),
+                    n_inside=int(self.n_inside), n_terms=int(self.n_terms), iterations=int(self.iterations),
+                    converged=bool(self.converged), modified=int(self.modified), flags=int(self.flags))
+
+
+class NdtStats(C.Structure):
+    """sf_ndt_stats: the target's points, the cells of its index at `resolution`, the occupied ones, the voxels; build_ms /
+    align_ms: -1 unless profiled."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_cells", "n_occupied", "n_voxels")] + \
+               [("dims", C.c_int32 * 3), ("build_ms", C.c_float), ("align_ms", C.c_float)]
+
+    def as_dict(self):
+        return dict(n_points=int(self.n_points), n_cells=int(self.n_cells), n_occupied=int(self.n_occupied), n_voxels=int(self.n_voxels),
+                    dims=tuple(int(v) for v in self.dims), build_ms=float(self.build_ms), align_ms=float(self.align_ms))
+
+
 def _rows(indices):
     return np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int32)
 
@@ -287,7 +326,7 @@ _live = weakref.WeakSet()   # every wrapper object, closed in dependency order a
 
 
 def _close_all():
-    for kind in ("Node", "Comm", "Icp", "BruteForceAlignment", "Features", "Map", "Cloud", "Context"):
+    for kind in ("Node", "Comm", "Icp", "Ndt", "BruteForceAlignment", "Features", "Map", "Cloud", "Context"):
         for obj in [o for o in list(_live) if type(o).__name__ == kind]:
             try:
                 obj.close()
@@ -371,6 +410,20 @@ def load_library():
     lib.sf_map_iss_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_cloud_iss_keypoints.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sf_features_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_ndt_default_params.restype = None
+    lib.sf_ndt_default_params.argtypes = [C.c_void_p]
+    lib.sf_ndt_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_ndt_destroy.argtypes = [C.c_void_p]
+    lib.sf_ndt_destroy.restype = None
+    lib.sf_ndt_set_target_cloud.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_ndt_set_target_map.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_ndt_download_voxels.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_ndt_set_source_cloud.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_ndt_set_source_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
+    lib.sf_ndt_derivatives.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_ndt_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_ndt_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_ndt_stats_read.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_launch_schedule.argtypes =[C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1287,6 +1340,105 @@ class Features:
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             self.lib.sf_features_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Ndt:
+    """sf_ndt: Normal Distributions Transform registration of scans against the per-voxel Gaussians of `target` (a Cloud or a Map)
+    at cell = resolution (include/slamfusion.h).  neighbours: 1 (the home cell) or 7 (plus the face neighbours)."""
+
+    def __init__(self, ctx, target, resolution, neighbours=7, outlier_ratio=0.55, min_points=6, min_eig_ratio=0.01, step_size=0.1,
+                 transformation_epsilon=1e-4, max_iterations=30, hessian_floor=1e-6, profile=False):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        p = NdtParams()
+        self.lib.sf_ndt_default_params(C.byref(p))
+        p.resolution, p.outlier_ratio, p.step_size, p.transformation_epsilon = float(resolution), float(outlier_ratio), float(step_size), float(transformation_epsilon)
+        p.min_eig_ratio, p.hessian_floor = float(min_eig_ratio), float(hessian_floor)
+        p.min_points, p.neighbours, p.max_iterations, p.profile = int(min_points), int(neighbours), int(max_iterations), int(bool(profile))
+        self.params = p
+        _check(self.lib.sf_ndt_create(ctx.h, C.byref(p), C.byref(self.h)))
+        _live.add(self)
+        self.batch = 0
+        if target is not None:
+            self.set_target(target)
+
+    def set_target(self, target):
+        if isinstance(target, Map):
+            _check(self.lib.sf_ndt_set_target_map(self.h, target.h))
+        elif isinstance(target, Cloud):
+            _check(self.lib.sf_ndt_set_target_cloud(self.h, target.h))
+        else:
+            raise SlamFusionError("Ndt: the target must be a Cloud or a Map")
+        return self
+
+    def voxels(self):
+        """-> dict(cell int64 [n] ascending, count int32 [n], mean [n, 3], cov [n, 6], icov [n, 6] (xx xy xz yy yz zz), dims)"""
+        n = C.c_int64()
+        _check(self.lib.sf_ndt_download_voxels(self.h, None, None, None, None, None, C.c_int64(0), C.byref(n)))
+        n = n.value
+        cell, count = np.zeros(n, np.int64), np.zeros(n, np.int32)
+        mean, cov, icov = np.zeros((n, 3), np.float64), np.zeros((n, 6), np.float64), np.zeros((n, 6), np.float64)
+        if n:
+            _check(self.lib.sf_ndt_download_voxels(self.h, _p(cell), _p(count), _p(mean), _p(cov), _p(icov), C.c_int64(n), None))
+        return dict(cell=cell, count=count, mean=mean, cov=cov, icov=icov, dims=self.stats()["dims"])
+
+    def _set_source(self, source):
+        if isinstance(source, Cloud):
+            _check(self.lib.sf_ndt_set_source_cloud(self.h, source.h))
+            self.batch = 1
+            return
+        xyz = _f32(source)
+        if xyz.ndim != 3:
+            xyz = xyz.reshape(1, -1, 3)
+        _check(self.lib.sf_ndt_set_source_batch(self.h, _p(xyz) if xyz.size else None, C.c_int64(xyz.shape[1]), C.c_int(xyz.shape[0])))
+        self.batch = xyz.shape[0]
+
+    def derivatives(self, source, poses):
+        """Score, gradient and Hessian of `source` (a Cloud or [n, 3]) at poses [k, 4, 4] -> a list of k dicts."""
+        self._set_source(source)
+        poses = _f64(poses).reshape(-1, 16)
+        out = (NdtResult * max(len(poses), 1))()
+        _check(self.lib.sf_ndt_derivatives(self.h, _p(poses) if len(poses) else None, C.c_int64(len(poses)), out))
+        return [out[i].as_dict() for i in range(len(poses))]
+
+    def align(self, source, init=None, trace=False):
+        """One scan from `init` (None: the identity) -> dict(T64, score, gradient, hessian, n_inside, n_terms, iterations, converged,
+        modified, flags[, trace [iterations + 1, 4, 4]])."""
+        self._set_source(source)
+        init = _f64(np.eye(4) if init is None else init).reshape(16)
+        out = NdtResult()
+        tr = np.zeros((int(self.params.max_iterations) + 1, 16), np.float64) if trace else None
+        _check(self.lib.sf_ndt_align(self.h, _p(init), C.byref(out), _p(tr) if trace else None))
+        r = out.as_dict()
+        if trace:
+            r["trace"] = tr[:r["iterations"] + 1].reshape(-1, 4, 4).copy()
+        return r
+
+    def align_batch(self, sources, inits):
+        """sources [batch, n, 3] from inits [batch, 4, 4] -> a list of batch dicts; entry b is bit for bit align(sources[b], inits[b])."""
+        self._set_source(_f32(sources).reshape(len(sources), -1, 3))
+        inits = _f64(inits).reshape(-1, 16)
+        if len(inits) != self.batch:
+            raise SlamFusionError("align_batch: %d poses for %d scans" % (len(inits), self.batch))
+        out = (NdtResult * self.batch)()
+        _check(self.lib.sf_ndt_align_batch(self.h, _p(inits), out))
+        return [out[i].as_dict() for i in range(self.batch)]
+
+    def stats(self):
+        st = NdtStats()
+        _check(self.lib.sf_ndt_stats_read(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.sf_ndt_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

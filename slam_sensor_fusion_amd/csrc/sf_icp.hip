@@ -31,6 +31,7 @@
 #include "sf_order.hpp"
 #include "sf_p2p.hpp"
 #include "sf_schedule.hpp"
+#include "sf_sort.hpp"
 
 #include <cfloat>
 #include <cstdlib>
@@ -3094,6 +3095,7 @@ __global__ __launch_bounds__(BLK) void k_icp_fused_rob(SfGrid g, SfWindow w, con
 
 #include "sf_cov.hpp"
 #include "sf_icp_testhooks.hpp"
+#include "sf_ndt.hpp"
 
 } // namespace
 
@@ -4979,3 +4981,6 @@ extern "C" int sf_test_query_order(sf_map *map, const float *points, int batch, 
         for (int a = 0; a < 3; ++a) ordered[3 * i + a] = h_soa[(size_t)a * total + i];
     return SF_OK;
 }
+
+// ==================================================================== NDT (sf_ndt_*)
+#include "sf_ndt_host.hpp"

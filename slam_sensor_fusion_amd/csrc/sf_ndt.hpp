@@ -1,0 +1,343 @@
+// sf_ndt.hpp -- Normal Distributions Transform scan-to-map registration (sf_ndt_*, include/slamfusion.h; extension, no reference
+// code: the rule is in DESIGN section 24 and restated in tests/ndt_ref_np.py).  Included by sf_icp.hip inside its anonymous
+// namespace, after every other kernel, so that none of them changes: it uses that file's block_reduce_store, reduce_partials,
+// wave_reduce_1, vec6_to_mat4, mat4_mul and sf_jacobi.hpp's jacobi_sym as they are.  The host side is sf_ndt_host.hpp.
+//
+// Target (once per target, on the grid index sf_map_build makes at cell = resolution):
+//   k_ndt_cell_flags   one lane per cell: 1 when the cell holds a point; an exclusive scan ranks the occupied cells
+//   k_ndt_occupied     the occupied cells in ascending cell id
+//   k_ndt_voxels       one WAVE per occupied cell over the cell's contiguous run: the mean, then the centred second moments,
+//                      float64, lanes strided by 64 and the fixed butterfly of wave_reduce_1 -- the same bits every build;
+//                      then on every lane alike the 3 x 3 Jacobi solve, the eigenvalue floor, cov = V L V^T and B = V L^-1 V^T
+//   k_ndt_compact      the voxels in ascending cell id (an exclusive scan of the voxel flags) and the dense cell -> voxel table
+// Alignment (per iteration, no host synchronisation in between):
+//   k_ndt_derivs<NB>   one lane per source point, blockIdx.y the batch entry: y = T x, the home cell, 1 or 7 voxel records of
+//                      80 bytes, the 30-double record (score, gradient 6, upper Hessian 21, points that met a voxel, terms) in
+//                      registers; block_reduce_store<30> into partials[b][block][32]
+//   k_ndt_step         one workgroup per batch entry: reduce_partials<30, 256>, then on one lane the modified Newton step
+//                      (jacobi_sym<6>), the pose update, the done flag and the trace row; as the last launch of an alignment
+//                      (final_pass) it only records score, gradient and Hessian at the final pose
+
+constexpr int NREC_NDT = 30;
+constexpr int NDT_VOX_STRIDE = 10; // doubles per voxel record: mean[3], B xx xy xz yy yz zz, count -- five 16-byte loads
+constexpr int NDT_TMP_STRIDE = 16; // per occupied cell before the compaction: mean[3], cov[6], B[6], count
+constexpr int NDT_SBLK = 256;
+
+struct NdtGrid {
+    double org[3], inv_h;          // the index's float32 origin and 1 / cell, widened
+    int dim[3];
+    const int32_t *cell_voxel;     // [ncell]: voxel id or -1
+    const double *vox;             // [n_voxels][NDT_VOX_STRIDE]
+};
+
+struct NdtConst { double d1, half_d2, d2, neg_d1d2; };
+struct NdtStepArg { double step_size, eps, hessian_floor; };
+
+struct NdtState {
+    double T[16];
+    double score, g[6], H[36];
+    long long n_inside, n_terms;
+    int iterations, converged, modified, flags, done, pad;
+};
+
+__global__ __launch_bounds__(256) void k_ndt_cell_flags(const uint32_t *__restrict__ cell_start, int64_t ncell, uint32_t *__restrict__ flag)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c < ncell) flag[c] = cell_start[c + 1] > cell_start[c] ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_ndt_occupied(const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t ncell, uint32_t *__restrict__ occ)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c < ncell && flag[c]) occ[pos[c]] = (uint32_t)c;
+}
+
+__global__ __launch_bounds__(BLK) void k_ndt_voxels(const float4 *__restrict__ pts, const uint32_t *__restrict__ cell_start, const uint32_t *__restrict__ occ, int64_t n_occ,
+                                                    int min_points, double min_eig_ratio, double *__restrict__ tmp, uint32_t *__restrict__ is_voxel)
+{
+    const int64_t o = (int64_t)blockIdx.x * (BLK / 64) + (threadIdx.x >> 6);
+    if (o >= n_occ) return; // (the whole wave leaves together)
+    const int lane = threadIdx.x & 63;
+    const uint32_t c = occ[o];
+    const uint32_t a = cell_start[c], b = cell_start[c + 1];
+    const int m = (int)(b - a);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (uint32_t k = a + lane; k < b; k += 64) {
+        const float4 p = pts[k];
+        sx = sx + (double)p.x; sy = sy + (double)p.y; sz = sz + (double)p.z;
+    }
+    sx = wave_reduce_1(sx); sy = wave_reduce_1(sy); sz = wave_reduce_1(sz);
+    const double mx = sx / (double)m, my = sy / (double)m, mz = sz / (double)m;
+    bool voxel = m >= min_points; // (min_points >= 3: m - 1 > 0 below)
+    double cov[6] = {0, 0, 0, 0, 0, 0}, B[6] = {0, 0, 0, 0, 0, 0};
+    if (voxel) { // wave-uniform
+        double qxx = 0.0, qxy = 0.0, qxz = 0.0, qyy = 0.0, qyz = 0.0, qzz = 0.0;
+        for (uint32_t k = a + lane; k < b; k += 64) {
+            const float4 p = pts[k];
+            const double dx = (double)p.x - mx, dy = (double)p.y - my, dz = (double)p.z - mz;
+            qxx = qxx + dx * dx; qxy = qxy + dx * dy; qxz = qxz + dx * dz;
+            qyy = qyy + dy * dy; qyz = qyz + dy * dz; qzz = qzz + dz * dz;
+        }
+        qxx = wave_reduce_1(qxx); qxy = wave_reduce_1(qxy); qxz = wave_reduce_1(qxz);
+        qyy = wave_reduce_1(qyy); qyz = wave_reduce_1(qyz); qzz = wave_reduce_1(qzz);
+        const double dof = (double)(m - 1);
+        double A[9], V[9];
+        A[0] = qxx / dof;
+        A[1] = A[3] = qxy / dof;
+        A[2] = A[6] = qxz / dof;
+        A[4] = qyy / dof;
+        A[5] = A[7] = qyz / dof;
+        A[8] = qzz / dof;
+        jacobi_sym<3>(A, V);
+        const double lmax = fmax(A[0], fmax(A[4], A[8]));
+        voxel = lmax > 0.0 && lmax < INFINITY; // (NaN compares false)
+        if (voxel) {
+            const double fl = min_eig_ratio * lmax;
+            double l[3], il[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                l[k] = fmax(A[4 * k], fl);
+                il[k] = 1.0 / l[k];
+            }
+            int e = 0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+#pragma unroll
+                for (int j = i; j < 3; ++j) {
+                    cov[e] = (l[0] * V[3 * i] * V[3 * j] + l[1] * V[3 * i + 1] * V[3 * j + 1]) + l[2] * V[3 * i + 2] * V[3 * j + 2];
+                    B[e] = (il[0] * V[3 * i] * V[3 * j] + il[1] * V[3 * i + 1] * V[3 * j + 1]) + il[2] * V[3 * i + 2] * V[3 * j + 2];
+                    ++e;
+                }
+        }
+    }
+    if (lane == 0) {
+        double *t = tmp + (size_t)o * NDT_TMP_STRIDE;
+        t[0] = mx; t[1] = my; t[2] = mz;
+#pragma unroll
+        for (int e = 0; e < 6; ++e) { t[3 + e] = cov[e]; t[9 + e] = B[e]; }
+        t[15] = (double)m;
+        is_voxel[o] = voxel ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ndt_compact(const uint32_t *__restrict__ occ, const uint32_t *__restrict__ is_voxel, const uint32_t *__restrict__ vpos, int64_t n_occ,
+                                                     const double *__restrict__ tmp, double *__restrict__ vox, double *__restrict__ cov, int64_t *__restrict__ vcell,
+                                                     int32_t *__restrict__ vcount, int32_t *__restrict__ cell_voxel)
+{
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= n_occ || !is_voxel[o]) return;
+    const uint32_t v = vpos[o], c = occ[o];
+    const double *t = tmp + (size_t)o * NDT_TMP_STRIDE;
+    double *r = vox + (size_t)v * NDT_VOX_STRIDE;
+    r[0] = t[0]; r[1] = t[1]; r[2] = t[2];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) { r[3 + e] = t[9 + e]; cov[(size_t)v * 6 + e] = t[3 + e]; }
+    r[9] = t[15];
+    vcell[v] = (int64_t)c;
+    vcount[v] = (int32_t)t[15];
+    cell_voxel[c] = (int32_t)v;
+}
+
+// the map's points back in their original order (sf_ndt_set_target_map: the NDT index is built from them like from a cloud)
+__global__ __launch_bounds__(256) void k_ndt_unsort(const float4 *__restrict__ pts, int64_t n, float *__restrict__ xyz)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const float4 p = pts[j];
+    const size_t id = __float_as_uint(p.w);
+    if (id >= (size_t)n) return;
+    xyz[3 * id] = p.x; xyz[3 * id + 1] = p.y; xyz[3 * id + 2] = p.z;
+}
+
+// J_j . v for the pose parameters (rx, ry, rz, tx, ty, tz): J_i = e_i x y for i < 3, e_(i-3) beyond
+template <int J>
+__device__ __forceinline__ double ndt_jdot(const double (&y)[3], double v0, double v1, double v2)
+{
+    if constexpr (J == 0) return v2 * y[1] - v1 * y[2];
+    else if constexpr (J == 1) return v0 * y[2] - v2 * y[0];
+    else if constexpr (J == 2) return v1 * y[0] - v0 * y[1];
+    else if constexpr (J == 3) return v0;
+    else if constexpr (J == 4) return v1;
+    else return v2;
+}
+
+template <int I, int J>
+__device__ __forceinline__ void ndt_hessian_entries(double (&acc)[NREC_NDT], const double (&y)[3], const double (&c)[3], const double (&a)[6], const double (&BJ)[18], double cy,
+                                                    double w, double d2)
+{
+    constexpr int K = 7 + (I * (13 - I)) / 2 + (J - I); // the upper triangle row by row: (0,0) (0,1) .. (0,5) (1,1) .. (5,5)
+    double t = ndt_jdot<J>(y, BJ[3 * I], BJ[3 * I + 1], BJ[3 * I + 2]) - d2 * a[I] * a[J];
+    if constexpr (J < 3) { // the second derivative of y: e_I y_J - y delta_IJ
+        t = t + c[I] * y[J];
+        if constexpr (I == J) t = t - cy;
+    }
+    acc[K] = acc[K] + w * t;
+    if constexpr (J + 1 < 6) ndt_hessian_entries<I, J + 1>(acc, y, c, a, BJ, cy, w, d2);
+    else if constexpr (I + 1 < 6) ndt_hessian_entries<I + 1, I + 1>(acc, y, c, a, BJ, cy, w, d2);
+}
+
+template <int NB>
+__global__ __launch_bounds__(BLK) void k_ndt_derivs(NdtGrid g, NdtConst cn, const float *__restrict__ src, int n, size_t src_stride, const NdtState *__restrict__ st, int force,
+                                                    double *__restrict__ partials, int nblocks)
+{
+    const int b = blockIdx.y;
+    const NdtState *S = st + b;
+    if (!force && S->done) return;
+    double acc[NREC_NDT];
+#pragma unroll
+    for (int k = 0; k < NREC_NDT; ++k) acc[k] = 0.0;
+    const int i = blockIdx.x * BLK + (int)threadIdx.x;
+    if (i < n) {
+        const float *p = src + (size_t)b * src_stride + 3 * (size_t)i;
+        const double x0 = (double)p[0], x1 = (double)p[1], x2 = (double)p[2];
+        double y[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) y[d] = ((S->T[4 * d] * x0 + S->T[4 * d + 1] * x1) + S->T[4 * d + 2] * x2) + S->T[4 * d + 3];
+        const double gx = (y[0] - g.org[0]) * g.inv_h, gy = (y[1] - g.org[1]) * g.inv_h, gz = (y[2] - g.org[2]) * g.inv_h;
+        // a point outside the grid has no home cell (NaN compares false): this is not the index's clamp
+        if (gx >= 0.0 && gx < (double)g.dim[0] && gy >= 0.0 && gy < (double)g.dim[1] && gz >= 0.0 && gz < (double)g.dim[2]) {
+            const int cx = (int)floor(gx), cy_ = (int)floor(gy), cz = (int)floor(gz);
+            int terms = 0;
+            for (int nb = 0; nb < NB; ++nb) { // the home cell, then +x -x +y -y +z -z
+                const int ax = (nb + 1) >> 1, sg = (nb & 1) ? 1 : -1;
+                const int ox = cx + (ax == 1 ? sg : 0), oy = cy_ + (ax == 2 ? sg : 0), oz = cz + (ax == 3 ? sg : 0);
+                if (ox < 0 || ox >= g.dim[0] || oy < 0 || oy >= g.dim[1] || oz < 0 || oz >= g.dim[2]) continue;
+                const int32_t v = g.cell_voxel[((size_t)oz * (size_t)g.dim[1] + (size_t)oy) * (size_t)g.dim[0] + (size_t)ox];
+                if (v < 0) continue;
+                const double2 *r = reinterpret_cast<const double2 *>(g.vox + (size_t)v * NDT_VOX_STRIDE);
+                const double2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+                const double r4 = r[4].x;
+                const double q0 = y[0] - r0.x, q1 = y[1] - r0.y, q2 = y[2] - r1.x;
+                const double bxx = r1.y, bxy = r2.x, bxz = r2.y, byy = r3.x, byz = r3.y, bzz = r4;
+                double c[3];
+                c[0] = (bxx * q0 + bxy * q1) + bxz * q2;
+                c[1] = (bxy * q0 + byy * q1) + byz * q2;
+                c[2] = (bxz * q0 + byz * q1) + bzz * q2;
+                const double s = (q0 * c[0] + q1 * c[1]) + q2 * c[2];
+                const double e = exp(-(cn.half_d2 * s));
+                const double w = cn.neg_d1d2 * e;
+                acc[0] = acc[0] + cn.d1 * e;
+                double a[6];
+                a[0] = ndt_jdot<0>(y, c[0], c[1], c[2]);
+                a[1] = ndt_jdot<1>(y, c[0], c[1], c[2]);
+                a[2] = ndt_jdot<2>(y, c[0], c[1], c[2]);
+                a[3] = c[0]; a[4] = c[1]; a[5] = c[2];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) acc[1 + k] = acc[1 + k] + w * a[k];
+                // B J_i: J_0 = (0, -y2, y1), J_1 = (y2, 0, -y0), J_2 = (-y1, y0, 0), J_3.. = the unit vectors
+                double BJ[18];
+                BJ[0] = bxz * y[1] - bxy * y[2]; BJ[1] = byz * y[1] - byy * y[2]; BJ[2] = bzz * y[1] - byz * y[2];
+                BJ[3] = bxx * y[2] - bxz * y[0]; BJ[4] = bxy * y[2] - byz * y[0]; BJ[5] = bxz * y[2] - bzz * y[0];
+                BJ[6] = bxy * y[0] - bxx * y[1]; BJ[7] = byy * y[0] - bxy * y[1]; BJ[8] = byz * y[0] - bxz * y[1];
+                BJ[9] = bxx; BJ[10] = bxy; BJ[11] = bxz;
+                BJ[12] = bxy; BJ[13] = byy; BJ[14] = byz;
+                BJ[15] = bxz; BJ[16] = byz; BJ[17] = bzz;
+                const double cy = (c[0] * y[0] + c[1] * y[1]) + c[2] * y[2];
+                ndt_hessian_entries<0, 0>(acc, y, c, a, BJ, cy, w, cn.d2);
+                ++terms;
+            }
+            acc[28] = terms > 0 ? 1.0 : 0.0;
+            acc[29] = (double)terms;
+        }
+    }
+    block_reduce_store<NREC_NDT>(acc, partials + ((size_t)b * nblocks + blockIdx.x) * REC_STRIDE);
+}
+
+__global__ __launch_bounds__(NDT_SBLK) void k_ndt_step(NdtState *__restrict__ st, const double *__restrict__ partials, int nblocks, NdtStepArg sa, int it, int final_pass,
+                                                       double *__restrict__ trace)
+{
+    const int b = blockIdx.x;
+    NdtState *S = st + b;
+    if (!final_pass && S->done) return;
+    __shared__ double rec[REC_STRIDE];
+    reduce_partials<NREC_NDT, NDT_SBLK>(partials + (size_t)b * nblocks * REC_STRIDE, nblocks, rec);
+    if (threadIdx.x != 0) return;
+    double g[6], H[36];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) g[k] = rec[1 + k];
+    {
+        int k = 7;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c) { H[6 * a + c] = rec[k]; H[6 * c + a] = rec[k]; ++k; }
+    }
+    // usable: a term exists, everything is finite and H is not all zero
+    double hsum = 0.0, gsum = 0.0;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) hsum = hsum + fabs(H[k]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) gsum = gsum + fabs(g[k]);
+    const bool usable = rec[29] > 0.0 && hsum > 0.0 && hsum < INFINITY && gsum < INFINITY && fabs(rec[0]) < INFINITY;
+    if (final_pass) {
+        S->score = usable ? rec[0] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) S->g[k] = usable ? g[k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 36; ++k) S->H[k] = usable ? H[k] : 0.0;
+        S->n_inside = (long long)rec[28];
+        S->n_terms = (long long)rec[29];
+        if (!usable) S->flags |= SF_NDT_FLAG_NO_OVERLAP;
+        if (!S->done) { S->iterations = it; S->done = 1; }
+        return;
+    }
+    if (!usable) { // the pose stays as it is
+        S->flags |= SF_NDT_FLAG_NO_OVERLAP;
+        S->iterations = it;
+        S->done = 1;
+        return;
+    }
+    double V[36];
+    jacobi_sym<6>(H, V);
+    double amax = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) amax = fmax(amax, fabs(H[7 * k]));
+    const double fl = sa.hessian_floor * amax;
+    bool modified = false;
+    double pk[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double l = H[7 * k];
+        if (l < 0.0 || fabs(l) < fl) modified = true;
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) t = t + V[6 * i + k] * g[i];
+        pk[k] = t / fmax(fabs(l), fl);
+    }
+    double d[6], n2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t = t + V[6 * i + k] * pk[k];
+        d[i] = -t;
+        n2 = n2 + d[i] * d[i];
+    }
+    double len = sqrt(n2);
+    if (!(len < INFINITY)) { // (an overflow of the solve: treated like a Hessian that is not finite)
+        S->flags |= SF_NDT_FLAG_NO_OVERLAP;
+        S->iterations = it;
+        S->done = 1;
+        return;
+    }
+    if (len > sa.step_size) {
+        const double sc = sa.step_size / len;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) d[i] = d[i] * sc;
+        len = sa.step_size;
+    }
+    double upd[16], Tc[16];
+    vec6_to_mat4(d, upd);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) Tc[i] = S->T[i];
+    mat4_mul(upd, Tc, Tc);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) S->T[i] = Tc[i];
+    if (trace && b == 0) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) trace[(size_t)(it + 1) * 16 + i] = Tc[i];
+    }
+    S->iterations = it + 1;
+    if (modified) S->modified += 1;
+    if (len < sa.eps) { S->converged = 1; S->done = 1; }
+}
