@@ -590,6 +590,39 @@ int sf_ndt_derivatives(sf_ndt *ndt, const double *poses, int64_t k, sf_ndt_resul
 int sf_ndt_align(sf_ndt *ndt, const double init[16], sf_ndt_result *out, double *trace);
 int sf_ndt_align_batch(sf_ndt *ndt, const double *inits, sf_ndt_result *out);
 int sf_ndt_stats_read(sf_ndt *ndt, sf_ndt_stats *out);
+/* Backtracking line search and coarse-to-fine levels for NDT (restated in tests/ndt_ls_ref_np.py).  Off by default: an
+ * alignment is then bit for bit the one above.  With sf_ndt_set_line_search(trials >= 1), per batch entry and iteration:
+ *   1. the derivatives at T as above: phi0 (the score), g, H; the usability check and SF_NDT_FLAG_NO_OVERLAP as above;
+ *   2. d = -V L~^-1 V^T g, the solve above before the scaling (same floor, same `modified`); raw = |d|, not finite: as above;
+ *   3. alpha_max = raw > step_max ? step_max / raw : 1.0; slope = ((((g0 d0 + g1 d1) + g2 d2) + g3 d3) + g4 d4) + g5 d5, unfused;
+ *   4. trial k = 0 .. trials - 1: alpha_k = ldexp(alpha_max, -k), delta_k[i] = alpha_k * d[i], T_k = M(delta_k) T;
+ *   5. phi_k, terms_k: the score and the number of terms of the entry's scan at T_k, bit for bit what sf_ndt_derivatives (and
+ *      sf_ndt_scores) return there; all trials of all entries are evaluated in one launch;
+ *   6. the smallest k with terms_k > 0, phi_k finite and phi_k <= phi0 + (armijo * alpha_k) * slope is accepted: T <- T_k,
+ *      iterations + 1, modified + 1 when an eigenvalue was negative or floored, converged when alpha_k * raw < transformation_epsilon;
+ *   7. no trial accepted: flags |= SF_NDT_FLAG_LINE_SEARCH_STALLED, the pose stays, the entry is done with converged = 0 (no
+ *      step was taken, so `modified` does not count it).
+ *   params.step_size is not used in this mode; the final pass (score, gradient, hessian at the final pose) is as above.
+ * sf_ndt_scores: score and n_terms of entry 0 of the source at poses [k][16], any k; a sum that is not finite gives (0, 0).
+ * sf_ndt_line_search_read: entry 0 of the last sf_ndt_align, one row per iteration whose trials were evaluated (the stalled one
+ *   included, so iterations or iterations + 1 rows): the direction d as `delta`, phi / n_terms of every trial (zeros beyond
+ *   `trials`), chosen = the accepted k or -1.  rows may be NULL (cap 0) to ask for *n; cap below the count with rows given is
+ *   SF_ERR_INVALID (*n set).  SF_ERR_STATE when the last sf_ndt_align ran without the search, or none has run.
+ * sf_ndt_align_levels: several sf_ndt on one target at descending resolution, each with its source set (the same scans), aligned
+ *   in turn: level l is bit for bit sf_ndt_align_batch(levels[l]) from the poses where level l - 1 ended (level 0: inits),
+ *   whatever that level's flags were; out [batch] is the last level's results verbatim, per_level [n_levels][batch] every level's.
+ * SF_ERR_INVALID ("bad arguments"), before any device work: NULL handles; trials outside [0, 16]; step_max not > 0 or not finite;
+ *   armijo outside (0, 1); n_levels < 1; levels of different contexts, batch sizes or source sizes; a level without target or
+ *   source. */
+#define SF_NDT_FLAG_LINE_SEARCH_STALLED 2
+#define SF_NDT_MAX_TRIALS 16
+typedef struct { int32_t trials, pad; double step_max, armijo; } sf_ndt_line_search;            /* trials 0: off */
+typedef struct { double alpha_max, raw_length, phi0, slope, delta[6], phi[16]; int64_t n_terms[16]; int32_t chosen, trials; } sf_ndt_ls_row;  /* chosen -1: stalled */
+void sf_ndt_default_line_search(sf_ndt_line_search *p);                                         /* 8 trials, step_max 1.0, armijo 1e-4 */
+int sf_ndt_set_line_search(sf_ndt *ndt, const sf_ndt_line_search *p);                           /* NULL or trials 0: off */
+int sf_ndt_scores(sf_ndt *ndt, const double *poses, int64_t k, double *score, int64_t *n_terms);/* entry 0 at poses [k][16], any k */
+int sf_ndt_line_search_read(sf_ndt *ndt, sf_ndt_ls_row *rows, int64_t cap, int64_t *n);         /* entry 0 of the last sf_ndt_align with the search on: one row per evaluated iteration, the stalled one included */
+int sf_ndt_align_levels(sf_ndt *const *levels, int n_levels, const double *inits, sf_ndt_result *out /* [batch] */, sf_ndt_result *per_level /* [n_levels][batch] or NULL */);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */

@@ -280,6 +280,8 @@ def _iss_params(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbor
 
 SF_NDT_DIRECT1, SF_NDT_DIRECT7 = 1, 7
 SF_NDT_FLAG_NO_OVERLAP = 1
+SF_NDT_FLAG_LINE_SEARCH_STALLED = 2
+SF_NDT_MAX_TRIALS = 16
 
 
 class NdtParams(C.Structure):
@@ -317,6 +319,27 @@ class NdtStats(C.Structure):
                     dims=tuple(int(v) for v in self.dims), build_ms=float(self.build_ms), align_ms=float(self.align_ms))
 
 
+class NdtLineSearch(C.Structure):
+    """sf_ndt_line_search (sf_ndt_default_line_search: 8 trials, step_max 1.0, armijo 1e-4; trials 0: off)."""
+    _fields_ = [("trials", C.c_int32), ("pad", C.c_int32), ("step_max", C.c_double), ("armijo", C.c_double)]
+
+    def as_dict(self):
+        return dict(trials=int(self.trials), step_max=float(self.step_max), armijo=float(self.armijo))
+
+
+class NdtLsRow(C.Structure):
+    """sf_ndt_ls_row: one iteration of the line search of entry 0 -- the range, the unscaled direction `delta`, the score phi0 and the
+    slope at the pose, phi / n_terms of the trials alpha_max / 2^k, and the accepted k (-1: stalled)."""
+    _fields_ = [("alpha_max", C.c_double), ("raw_length", C.c_double), ("phi0", C.c_double), ("slope", C.c_double), ("delta", C.c_double * 6),
+                ("phi", C.c_double * 16), ("n_terms", C.c_int64 * 16), ("chosen", C.c_int32), ("trials", C.c_int32)]
+
+    def as_dict(self):
+        k = int(self.trials)
+        return dict(alpha_max=float(self.alpha_max), raw_length=float(self.raw_length), phi0=float(self.phi0), slope=float(self.slope),
+                    delta=np.array(self.delta, dtype=np.float64), phi=np.array(self.phi, dtype=np.float64)[:k], n_terms=np.array(self.n_terms, dtype=np.int64)[:k],
+                    chosen=int(self.chosen), trials=k)
+
+
 def _rows(indices):
     return np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int32)
 
@@ -326,7 +349,7 @@ _live = weakref.WeakSet()   # every wrapper object, closed in dependency order a
 
 
 def _close_all():
-    for kind in ("Node", "Comm", "Icp", "Ndt", "BruteForceAlignment", "Features", "Map", "Cloud", "Context"):
+    for kind in ("Node", "Comm", "Icp", "NdtPyramid", "Ndt", "BruteForceAlignment", "Features", "Map", "Cloud", "Context"):
         for obj in [o for o in list(_live) if type(o).__name__ == kind]:
             try:
                 obj.close()
@@ -424,6 +447,12 @@ def load_library():
     lib.sf_ndt_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_ndt_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_ndt_stats_read.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_ndt_default_line_search.restype = None
+    lib.sf_ndt_default_line_search.argtypes = [C.c_void_p]
+    lib.sf_ndt_set_line_search.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_ndt_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.sf_ndt_line_search_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_ndt_align_levels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_test_launch_schedule.argtypes =[C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1436,10 +1465,88 @@ class Ndt:
         _check(self.lib.sf_ndt_stats_read(self.h, C.byref(st)))
         return st.as_dict()
 
+    def set_line_search(self, trials=8, step_max=1.0, armijo=1e-4):
+        """The backtracking line search of the alignments from now on: per iteration the `trials` step lengths
+        alpha_max / 2^k along the unscaled Newton direction, alpha_max = min(1, step_max / |d|), the first that meets the Armijo
+        condition taken.  trials=0 switches it off: the alignments are then bit for bit those of an object that never had it."""
+        p = NdtLineSearch(int(trials), 0, float(step_max), float(armijo))
+        _check(self.lib.sf_ndt_set_line_search(self.h, C.byref(p)))
+        return self
+
+    def scores(self, source, poses):
+        """Score and number of terms of `source` (a Cloud or [n, 3]) at poses [k, 4, 4] -> (score float64 [k], n_terms int64 [k]): bit for
+        bit the score and n_terms of derivatives() there, without the gradient and the Hessian."""
+        self._set_source(source)
+        poses = _f64(poses).reshape(-1, 16)
+        score, terms = np.zeros(len(poses), np.float64), np.zeros(len(poses), np.int64)
+        _check(self.lib.sf_ndt_scores(self.h, _p(poses) if len(poses) else None, C.c_int64(len(poses)), _p(score) if len(poses) else None,
+                                      _p(terms) if len(poses) else None))
+        return score, terms
+
+    def line_search_rows(self):
+        """The line search of the last align() with the search on, one dict per evaluated iteration (NdtLsRow.as_dict)."""
+        n = C.c_int64()
+        _check(self.lib.sf_ndt_line_search_read(self.h, None, C.c_int64(0), C.byref(n)))
+        rows = (NdtLsRow * max(n.value, 1))()
+        _check(self.lib.sf_ndt_line_search_read(self.h, rows, C.c_int64(n.value), None))
+        return [rows[i].as_dict() for i in range(n.value)]
+
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             self.lib.sf_ndt_destroy(self.h)
             self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NdtPyramid:
+    """Coarse-to-fine NDT (sf_ndt_align_levels): one Ndt per entry of `resolutions` (descending) on the same target,
+    aligned in turn, each level from the pose where the previous one ended.  line_search: True (the defaults of
+    Ndt.set_line_search), False, or a dict of its arguments; ndt_kwargs go to every Ndt."""
+
+    def __init__(self, ctx, target, resolutions, line_search=True, **ndt_kwargs):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.levels = []
+        _live.add(self)
+        for r in resolutions:
+            self.levels.append(Ndt(ctx, target, float(r), **ndt_kwargs))
+            if line_search:
+                self.levels[-1].set_line_search(**(line_search if isinstance(line_search, dict) else {}))
+        if not self.levels:
+            raise SlamFusionError("NdtPyramid: no resolutions")
+
+    def _run(self, sources, inits):
+        for lv in self.levels:
+            lv._set_source(sources)
+        batch = self.levels[0].batch
+        inits = _f64(inits).reshape(-1, 16)
+        if len(inits) != batch:
+            raise SlamFusionError("NdtPyramid: %d poses for %d scans" % (len(inits), batch))
+        n = len(self.levels)
+        handles = (C.c_void_p * n)(*[lv.h.value for lv in self.levels])
+        out, per = (NdtResult * batch)(), (NdtResult * (n * batch))()
+        _check(self.lib.sf_ndt_align_levels(handles, C.c_int(n), _p(inits), out, per))
+        res = [out[b].as_dict() for b in range(batch)]
+        for b in range(batch):
+            res[b]["per_level"] = [per[l * batch + b].as_dict() for l in range(n)]
+        return res
+
+    def align(self, source, init=None):
+        """One scan (a Cloud or [n, 3]) from `init` (None: the identity) -> the last level's dict of Ndt.align plus per_level (a list of
+        every level's dict)."""
+        return self._run(source if isinstance(source, Cloud) else _f32(source).reshape(1, -1, 3), np.eye(4) if init is None else init)[0]
+
+    def align_batch(self, sources, inits):
+        """sources [batch, n, 3] from inits [batch, 4, 4] -> a list of batch such dicts."""
+        return self._run(_f32(sources).reshape(len(sources), -1, 3), inits)
+
+    def close(self):
+        for lv in getattr(self, "levels", []):
+            lv.close()
 
     def __del__(self):
         try:

@@ -341,3 +341,222 @@ __global__ __launch_bounds__(NDT_SBLK) void k_ndt_step(NdtState *__restrict__ st
     if (modified) S->modified += 1;
     if (len < sa.eps) { S->converged = 1; S->done = 1; }
 }
+
+// ------------------------------------------------------------------ line search (sf_ndt_set_line_search)
+// Per iteration, after k_ndt_derivs as above:
+//   k_ndt_step_ls      one workgroup per batch entry: the reduction and the 6 x 6 solve of k_ndt_step up to d (the same expressions
+//                      in the same order), then alpha_max, the slope and the `trials` poses T_k = M(ldexp(alpha_max, -k) d) T
+//   k_ndt_scores<NB>   one lane per source point with k_ndt_derivs' mapping, blockIdx.y the entry, blockIdx.z the trial: the score
+//                      in slot 0 and the terms in slot 1 of the same block_reduce_store (its butterfly pairs the same lanes whatever
+//                      the slot), so that the sums are bit for bit k_ndt_derivs' acc[0] and acc[29] at that pose
+//   k_ndt_pick         one workgroup per entry: reduce_partials over each trial's rows, then on one lane the smallest k that meets
+//                      the Armijo condition, the pose, the counters, the flags and the rows of entry 0
+constexpr int NREC_NDT_SCORE = 2;
+
+struct NdtLsArg { double step_max, armijo, eps, hessian_floor; int trials; };
+
+struct NdtLsEntry {
+    double Tk[SF_NDT_MAX_TRIALS][16];
+    double alpha_max, raw, phi0, slope;
+    int modified, pad;
+};
+
+// pose p = blockIdx.y * gridDim.z + blockIdx.z reads poses[p][16] and the scan blockIdx.y (src_stride 0: every pose the same
+// scan); done: the states whose done flag lets an entry leave at once, or nullptr
+template <int NB>
+__global__ __launch_bounds__(BLK) void k_ndt_scores(NdtGrid g, NdtConst cn, const float *__restrict__ src, int n, size_t src_stride, const NdtState *__restrict__ done,
+                                                    const double *__restrict__ poses, size_t pose_stride, double *__restrict__ partials, int nblocks)
+{
+    const int b = blockIdx.y;
+    if (done && done[b].done) return;
+    const size_t p = (size_t)b * gridDim.z + blockIdx.z;
+    const double *T = poses + (size_t)b * pose_stride + (size_t)blockIdx.z * 16;
+    double acc[NREC_NDT_SCORE] = {0.0, 0.0};
+    const int i = blockIdx.x * BLK + (int)threadIdx.x;
+    if (i < n) {
+        const float *q = src + (size_t)b * src_stride + 3 * (size_t)i;
+        const double x0 = (double)q[0], x1 = (double)q[1], x2 = (double)q[2];
+        double y[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) y[d] = ((T[4 * d] * x0 + T[4 * d + 1] * x1) + T[4 * d + 2] * x2) + T[4 * d + 3];
+        const double gx = (y[0] - g.org[0]) * g.inv_h, gy = (y[1] - g.org[1]) * g.inv_h, gz = (y[2] - g.org[2]) * g.inv_h;
+        if (gx >= 0.0 && gx < (double)g.dim[0] && gy >= 0.0 && gy < (double)g.dim[1] && gz >= 0.0 && gz < (double)g.dim[2]) {
+            const int cx = (int)floor(gx), cy_ = (int)floor(gy), cz = (int)floor(gz);
+            int terms = 0;
+            for (int nb = 0; nb < NB; ++nb) { // the home cell, then +x -x +y -y +z -z
+                const int ax = (nb + 1) >> 1, sg = (nb & 1) ? 1 : -1;
+                const int ox = cx + (ax == 1 ? sg : 0), oy = cy_ + (ax == 2 ? sg : 0), oz = cz + (ax == 3 ? sg : 0);
+                if (ox < 0 || ox >= g.dim[0] || oy < 0 || oy >= g.dim[1] || oz < 0 || oz >= g.dim[2]) continue;
+                const int32_t v = g.cell_voxel[((size_t)oz * (size_t)g.dim[1] + (size_t)oy) * (size_t)g.dim[0] + (size_t)ox];
+                if (v < 0) continue;
+                const double2 *r = reinterpret_cast<const double2 *>(g.vox + (size_t)v * NDT_VOX_STRIDE);
+                const double2 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+                const double r4 = r[4].x;
+                const double q0 = y[0] - r0.x, q1 = y[1] - r0.y, q2 = y[2] - r1.x;
+                const double bxx = r1.y, bxy = r2.x, bxz = r2.y, byy = r3.x, byz = r3.y, bzz = r4;
+                const double c0 = (bxx * q0 + bxy * q1) + bxz * q2;
+                const double c1 = (bxy * q0 + byy * q1) + byz * q2;
+                const double c2 = (bxz * q0 + byz * q1) + bzz * q2;
+                const double s = (q0 * c0 + q1 * c1) + q2 * c2;
+                const double e = exp(-(cn.half_d2 * s));
+                acc[0] = acc[0] + cn.d1 * e;
+                ++terms;
+            }
+            acc[1] = (double)terms;
+        }
+    }
+    block_reduce_store<NREC_NDT_SCORE>(acc, partials + (p * (size_t)nblocks + blockIdx.x) * REC_STRIDE);
+}
+
+// sf_ndt_scores: one workgroup per pose
+__global__ __launch_bounds__(NDT_SBLK) void k_ndt_scores_out(const double *__restrict__ partials, int nblocks, double *__restrict__ out)
+{
+    __shared__ double rec[REC_STRIDE];
+    reduce_partials<NREC_NDT_SCORE, NDT_SBLK>(partials + (size_t)blockIdx.x * nblocks * REC_STRIDE, nblocks, rec);
+    if (threadIdx.x != 0) return;
+    const bool finite = fabs(rec[0]) < INFINITY; // (NaN compares false)
+    out[2 * (size_t)blockIdx.x] = finite ? rec[0] : 0.0;
+    out[2 * (size_t)blockIdx.x + 1] = finite ? rec[1] : 0.0;
+}
+
+__global__ __launch_bounds__(NDT_SBLK) void k_ndt_step_ls(NdtState *__restrict__ st, const double *__restrict__ partials, int nblocks, NdtLsArg la, int it,
+                                                          NdtLsEntry *__restrict__ ls, sf_ndt_ls_row *__restrict__ rows)
+{
+    const int b = blockIdx.x;
+    NdtState *S = st + b;
+    if (S->done) return;
+    __shared__ double rec[REC_STRIDE];
+    reduce_partials<NREC_NDT, NDT_SBLK>(partials + (size_t)b * nblocks * REC_STRIDE, nblocks, rec);
+    if (threadIdx.x != 0) return;
+    double g[6], H[36];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) g[k] = rec[1 + k];
+    {
+        int k = 7;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int c = a; c < 6; ++c) { H[6 * a + c] = rec[k]; H[6 * c + a] = rec[k]; ++k; }
+    }
+    double hsum = 0.0, gsum = 0.0;
+#pragma unroll
+    for (int k = 0; k < 36; ++k) hsum = hsum + fabs(H[k]);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) gsum = gsum + fabs(g[k]);
+    const bool usable = rec[29] > 0.0 && hsum > 0.0 && hsum < INFINITY && gsum < INFINITY && fabs(rec[0]) < INFINITY;
+    if (!usable) { // the pose stays as it is
+        S->flags |= SF_NDT_FLAG_NO_OVERLAP;
+        S->iterations = it;
+        S->done = 1;
+        return;
+    }
+    double V[36];
+    jacobi_sym<6>(H, V);
+    double amax = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) amax = fmax(amax, fabs(H[7 * k]));
+    const double fl = la.hessian_floor * amax;
+    bool modified = false;
+    double pk[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const double l = H[7 * k];
+        if (l < 0.0 || fabs(l) < fl) modified = true;
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) t = t + V[6 * i + k] * g[i];
+        pk[k] = t / fmax(fabs(l), fl);
+    }
+    double d[6], n2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t = t + V[6 * i + k] * pk[k];
+        d[i] = -t;
+        n2 = n2 + d[i] * d[i];
+    }
+    const double raw = sqrt(n2);
+    if (!(raw < INFINITY)) {
+        S->flags |= SF_NDT_FLAG_NO_OVERLAP;
+        S->iterations = it;
+        S->done = 1;
+        return;
+    }
+    const double alpha_max = raw > la.step_max ? la.step_max / raw : 1.0;
+    const double slope = ((((g[0] * d[0] + g[1] * d[1]) + g[2] * d[2]) + g[3] * d[3]) + g[4] * d[4]) + g[5] * d[5];
+    NdtLsEntry *L = ls + b;
+    double Tc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) Tc[i] = S->T[i];
+    for (int k = 0; k < la.trials; ++k) {
+        const double alpha = ldexp(alpha_max, -k);
+        double dk[6], upd[16], Tk[16];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) dk[i] = alpha * d[i];
+        vec6_to_mat4(dk, upd);
+        mat4_mul(upd, Tc, Tk);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) L->Tk[k][i] = Tk[i];
+    }
+    L->alpha_max = alpha_max;
+    L->raw = raw;
+    L->phi0 = rec[0];
+    L->slope = slope;
+    L->modified = modified ? 1 : 0;
+    if (rows && b == 0) {
+        sf_ndt_ls_row *R = rows + it;
+        R->alpha_max = alpha_max;
+        R->raw_length = raw;
+        R->phi0 = rec[0];
+        R->slope = slope;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) R->delta[i] = d[i];
+        R->trials = la.trials;
+    }
+}
+
+__global__ __launch_bounds__(NDT_SBLK) void k_ndt_pick(NdtState *__restrict__ st, const double *__restrict__ tpart, int nblocks, NdtLsArg la, int it,
+                                                       const NdtLsEntry *__restrict__ ls, double *__restrict__ trace, sf_ndt_ls_row *__restrict__ rows)
+{
+    const int b = blockIdx.x;
+    NdtState *S = st + b;
+    if (S->done) return; // (also an entry that k_ndt_step_ls has just ended)
+    __shared__ double rec[REC_STRIDE];
+    __shared__ double phi[SF_NDT_MAX_TRIALS], terms[SF_NDT_MAX_TRIALS];
+    for (int k = 0; k < la.trials; ++k) {
+        reduce_partials<NREC_NDT_SCORE, NDT_SBLK>(tpart + ((size_t)b * la.trials + k) * nblocks * REC_STRIDE, nblocks, rec);
+        if (threadIdx.x == 0) { phi[k] = rec[0]; terms[k] = rec[1]; }
+    }
+    if (threadIdx.x != 0) return;
+    const NdtLsEntry *L = ls + b;
+    int chosen = -1;
+    double alpha_chosen = 0.0;
+    for (int k = 0; k < la.trials && chosen < 0; ++k) {
+        const double alpha = ldexp(L->alpha_max, -k);
+        if (terms[k] > 0.0 && fabs(phi[k]) < INFINITY && phi[k] <= L->phi0 + (la.armijo * alpha) * L->slope) { chosen = k; alpha_chosen = alpha; }
+    }
+    if (rows && b == 0) {
+        sf_ndt_ls_row *R = rows + it;
+        for (int k = 0; k < SF_NDT_MAX_TRIALS; ++k) {
+            R->phi[k] = k < la.trials ? phi[k] : 0.0;
+            R->n_terms[k] = k < la.trials ? (int64_t)terms[k] : 0;
+        }
+        R->chosen = chosen;
+    }
+    if (chosen < 0) { // the pose stays as it is
+        S->flags |= SF_NDT_FLAG_LINE_SEARCH_STALLED;
+        S->iterations = it;
+        S->done = 1;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) S->T[i] = L->Tk[chosen][i];
+    if (trace && b == 0) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) trace[(size_t)(it + 1) * 16 + i] = L->Tk[chosen][i];
+    }
+    S->iterations = it + 1;
+    if (L->modified) S->modified += 1;
+    if (alpha_chosen * L->raw < la.eps) { S->converged = 1; S->done = 1; }
+}

@@ -1,7 +1,9 @@
 // sf_ndt_host.hpp -- the host side of the NDT calls (include/slamfusion.h, sf_ndt_*): the object, the voxel build on an index of
 // its own and the launch list of an alignment.  Included by sf_icp.hip at file scope, after everything else; the kernels are
 // sf_ndt.hpp's.  An alignment enqueues max_iterations pairs (k_ndt_derivs, k_ndt_step), one more derivative pass at the final
-// pose and the copy of the states, and waits once.
+// pose and the copy of the states, and waits once.  With the line search on (sf_ndt_set_line_search) an iteration is four launches
+// (k_ndt_derivs, k_ndt_step_ls, k_ndt_scores over every entry's trials, k_ndt_pick), still without a wait in between;
+// sf_ndt_align_levels runs one such alignment per level.
 
 struct sf_ndt {
     sf_ctx *ctx = nullptr;
@@ -10,6 +12,10 @@ struct sf_ndt {
     sf_cloud *points = nullptr; // sf_ndt_set_target_map: the map's points in original order
     sf::DevBuf flag, pos, occ, is_voxel, vpos, tmp, vox, cov, vcell, vcount, cell_voxel;
     sf::DevBuf src, state, partials, trace;
+    sf_ndt_line_search ls{0, 0, 1.0, 1e-4};            // trials 0: off
+    sf::DevBuf ls_entry, ls_partials, ls_rows, poses, scores;
+    std::vector<sf_ndt_ls_row> rows;                   // entry 0 of the last sf_ndt_align with the search on
+    bool has_rows = false;
     int64_t n_points = 0, n_cells = 0, n_occupied = 0, n_voxels = 0, n_src = 0;
     int batch = 0;
     bool has_target = false, has_source = false;
@@ -164,8 +170,21 @@ int ndt_reserve_run(sf_ndt *ndt, int entries, int nblocks)
     return SF_OK;
 }
 
+// the scores of gridDim.y * gridDim.z poses in one launch: pose (y, z) at poses + y * pose_stride + 16 z, its rows at slab y * nz + z
+void ndt_launch_scores(sf_ndt *ndt, const NdtGrid &g, const NdtConst &cn, int ny, int nz, size_t src_stride, const NdtState *done, const double *poses, size_t pose_stride,
+                       double *partials, int nblocks)
+{
+    hipStream_t s = ndt->ctx->stream;
+    const dim3 grid((unsigned)nblocks, (unsigned)ny, (unsigned)nz);
+    if (ndt->prm.neighbours == SF_NDT_DIRECT7)
+        hipLaunchKernelGGL(k_ndt_scores<7>, grid, dim3(BLK), 0, s, g, cn, ndt->src.as<float>(), (int)ndt->n_src, src_stride, done, poses, pose_stride, partials, nblocks);
+    else
+        hipLaunchKernelGGL(k_ndt_scores<1>, grid, dim3(BLK), 0, s, g, cn, ndt->src.as<float>(), (int)ndt->n_src, src_stride, done, poses, pose_stride, partials, nblocks);
+}
+
 // entries states start at `poses` [entries][16]; iterations > 0: the Newton loop first; then the derivatives at the final poses
-int ndt_run(sf_ndt *ndt, const double *poses, int entries, size_t src_stride, int iterations, bool timed, sf_ndt_result *out, double *trace)
+// with the line search on, an iteration is (k_ndt_derivs, k_ndt_step_ls, k_ndt_scores, k_ndt_pick); want_rows: the rows of entry 0
+int ndt_run(sf_ndt *ndt, const double *poses, int entries, size_t src_stride, int iterations, bool timed, sf_ndt_result *out, double *trace, bool want_rows = false)
 {
     sf_ctx *ctx = ndt->ctx;
     SF_HIP(hipSetDevice(ctx->device));
@@ -182,14 +201,35 @@ int ndt_run(sf_ndt *ndt, const double *poses, int entries, size_t src_stride, in
         SF_TRY(ndt->trace.reserve(sizeof(double) * 16 * (size_t)(iterations + 1)));
         d_trace = ndt->trace.as<double>();
     }
+    const int trials = iterations > 0 ? (int)ndt->ls.trials : 0;
+    sf_ndt_ls_row *d_rows = nullptr;
+    if (want_rows) ndt->has_rows = false;
+    if (trials > 0) {
+        SF_TRY(ndt->ls_entry.reserve(sizeof(NdtLsEntry) * (size_t)entries));
+        SF_TRY(ndt->ls_partials.reserve(sizeof(double) * REC_STRIDE * (size_t)nblocks * (size_t)trials * (size_t)entries));
+        if (want_rows) {
+            SF_TRY(ndt->ls_rows.reserve(sizeof(sf_ndt_ls_row) * (size_t)iterations));
+            d_rows = ndt->ls_rows.as<sf_ndt_ls_row>();
+        }
+    }
     SF_TRY(sf::upload_staged(ctx, ndt->state.p, h.data(), sizeof(NdtState) * (size_t)entries));
     const NdtGrid g = ndt_grid(ndt);
     const NdtConst cn = ndt_constants(ndt->prm);
     const NdtStepArg sa{ndt->prm.step_size, ndt->prm.transformation_epsilon, ndt->prm.hessian_floor};
     SF_TRY(ndt_mark(ndt, 0));
+    const NdtLsArg la{ndt->ls.step_max, ndt->ls.armijo, ndt->prm.transformation_epsilon, ndt->prm.hessian_floor, trials};
     for (int it = 0; it < iterations; ++it) {
         ndt_launch_derivs(ndt, g, cn, entries, src_stride, 0, nblocks);
-        hipLaunchKernelGGL(k_ndt_step, dim3((unsigned)entries), dim3(NDT_SBLK), 0, s, ndt->state.as<NdtState>(), ndt->partials.as<double>(), nblocks, sa, it, 0, d_trace);
+        if (trials == 0) {
+            hipLaunchKernelGGL(k_ndt_step, dim3((unsigned)entries), dim3(NDT_SBLK), 0, s, ndt->state.as<NdtState>(), ndt->partials.as<double>(), nblocks, sa, it, 0, d_trace);
+            continue;
+        }
+        hipLaunchKernelGGL(k_ndt_step_ls, dim3((unsigned)entries), dim3(NDT_SBLK), 0, s, ndt->state.as<NdtState>(), ndt->partials.as<double>(), nblocks, la, it,
+                           ndt->ls_entry.as<NdtLsEntry>(), d_rows);
+        ndt_launch_scores(ndt, g, cn, entries, trials, src_stride, ndt->state.as<NdtState>(), reinterpret_cast<const double *>(ndt->ls_entry.p), sizeof(NdtLsEntry) / sizeof(double),
+                          ndt->ls_partials.as<double>(), nblocks);
+        hipLaunchKernelGGL(k_ndt_pick, dim3((unsigned)entries), dim3(NDT_SBLK), 0, s, ndt->state.as<NdtState>(), ndt->ls_partials.as<double>(), nblocks, la, it,
+                           ndt->ls_entry.as<NdtLsEntry>(), d_trace, d_rows);
     }
     ndt_launch_derivs(ndt, g, cn, entries, src_stride, 1, nblocks);
     hipLaunchKernelGGL(k_ndt_step, dim3((unsigned)entries), dim3(NDT_SBLK), 0, s, ndt->state.as<NdtState>(), ndt->partials.as<double>(), nblocks, sa, iterations, 1, d_trace);
@@ -204,6 +244,20 @@ int ndt_run(sf_ndt *ndt, const double *poses, int entries, size_t src_stride, in
         const int rows = out[0].iterations;
         if (rows > 0) SF_HIP(hipMemcpy(trace + 16, d_trace + 16, sizeof(double) * 16 * (size_t)rows, hipMemcpyDeviceToHost));
     }
+    if (d_rows) { // one row per iteration whose trials were evaluated: the steps taken and the stalled one
+        const int rows = out[0].iterations + ((out[0].flags & SF_NDT_FLAG_LINE_SEARCH_STALLED) ? 1 : 0);
+        ndt->rows.resize((size_t)rows);
+        if (rows > 0) SF_HIP(hipMemcpy(ndt->rows.data(), d_rows, sizeof(sf_ndt_ls_row) * (size_t)rows, hipMemcpyDeviceToHost));
+        ndt->has_rows = true;
+    }
+    return SF_OK;
+}
+
+int ndt_check_line_search(const sf_ndt_line_search *p)
+{
+    SF_CHECK(p->trials >= 0 && p->trials <= SF_NDT_MAX_TRIALS, SF_ERR_INVALID, "bad arguments: ndt line search trials must be 0 .. 16 (got %d)", (int)p->trials);
+    SF_CHECK(std::isfinite(p->step_max) && p->step_max > 0.0, SF_ERR_INVALID, "bad arguments: ndt line search step_max must be positive and finite (got %g)", p->step_max);
+    SF_CHECK(p->armijo > 0.0 && p->armijo < 1.0, SF_ERR_INVALID, "bad arguments: ndt line search armijo must lie in (0, 1) (got %g)", p->armijo);
     return SF_OK;
 }
 
@@ -351,7 +405,7 @@ extern "C" int sf_ndt_align(sf_ndt *ndt, const double init[16], sf_ndt_result *o
 {
     SF_CHECK(ndt && init && out, SF_ERR_INVALID, "bad arguments");
     SF_CHECK(ndt->has_target && ndt->has_source, SF_ERR_INVALID, "bad arguments: ndt needs a target and a source first");
-    return ndt_run(ndt, init, 1, 3 * (size_t)ndt->n_src, (int)ndt->prm.max_iterations, true, out, trace);
+    return ndt_run(ndt, init, 1, 3 * (size_t)ndt->n_src, (int)ndt->prm.max_iterations, true, out, trace, true);
 }
 
 extern "C" int sf_ndt_stats_read(sf_ndt *ndt, sf_ndt_stats *out)
@@ -360,5 +414,93 @@ extern "C" int sf_ndt_stats_read(sf_ndt *ndt, sf_ndt_stats *out)
     *out = sf_ndt_stats{ndt->n_points, ndt->n_cells, ndt->n_occupied, ndt->n_voxels, {0, 0, 0}, ndt->build_ms, ndt->align_ms};
     if (ndt->has_target)
         for (int d = 0; d < 3; ++d) out->dims[d] = ndt->index->grid.dim[d];
+    return SF_OK;
+}
+
+extern "C" void sf_ndt_default_line_search(sf_ndt_line_search *p)
+{
+    if (!p) return;
+    *p = sf_ndt_line_search{8, 0, 1.0, 1e-4};
+}
+
+extern "C" int sf_ndt_set_line_search(sf_ndt *ndt, const sf_ndt_line_search *p)
+{
+    SF_CHECK(ndt, SF_ERR_INVALID, "bad arguments");
+    if (p) SF_TRY(ndt_check_line_search(p));
+    if (p && p->trials > 0) ndt->ls = sf_ndt_line_search{p->trials, 0, p->step_max, p->armijo};
+    else ndt->ls.trials = 0;
+    return SF_OK;
+}
+
+extern "C" int sf_ndt_scores(sf_ndt *ndt, const double *poses, int64_t k, double *score, int64_t *n_terms)
+{
+    SF_CHECK(ndt && k >= 0 && ((poses && score && n_terms) || k == 0), SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(ndt->has_target && ndt->has_source, SF_ERR_INVALID, "bad arguments: ndt needs a target and a source first");
+    if (k == 0) return SF_OK;
+    sf_ctx *ctx = ndt->ctx;
+    SF_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int nblocks = (int)ndt_blocks(ndt->n_src, BLK);
+    const int64_t cap = std::min<int64_t>(k, NDT_MAX_BATCH * SF_NDT_MAX_TRIALS); // poses per launch
+    SF_TRY(ndt->poses.reserve(sizeof(double) * 16 * (size_t)cap));
+    SF_TRY(ndt->scores.reserve(sizeof(double) * 2 * (size_t)cap));
+    SF_TRY(ndt->ls_partials.reserve(sizeof(double) * REC_STRIDE * (size_t)nblocks * (size_t)cap));
+    const NdtGrid g = ndt_grid(ndt);
+    const NdtConst cn = ndt_constants(ndt->prm);
+    std::vector<double> h(2 * (size_t)cap);
+    for (int64_t at = 0; at < k; at += cap) {
+        const int chunk = (int)std::min<int64_t>(cap, k - at);
+        SF_TRY(sf::upload_staged(ctx, ndt->poses.p, poses + 16 * at, sizeof(double) * 16 * (size_t)chunk));
+        SF_TRY(ndt_mark(ndt, 0));
+        ndt_launch_scores(ndt, g, cn, chunk, 1, 0, nullptr, ndt->poses.as<double>(), 16, ndt->ls_partials.as<double>(), nblocks); // every pose reads entry 0 of the source
+        hipLaunchKernelGGL(k_ndt_scores_out, dim3((unsigned)chunk), dim3(NDT_SBLK), 0, s, ndt->ls_partials.as<double>(), nblocks, ndt->scores.as<double>());
+        SF_HIP(hipGetLastError());
+        SF_TRY(ndt_mark(ndt, 1));
+        SF_HIP(hipMemcpyAsync(h.data(), ndt->scores.p, sizeof(double) * 2 * (size_t)chunk, hipMemcpyDeviceToHost, s));
+        SF_HIP(hipStreamSynchronize(s));
+        SF_TRY(ndt_event_ms(ndt, &ndt->align_ms));
+        for (int i = 0; i < chunk; ++i) {
+            score[at + i] = h[2 * (size_t)i];
+            n_terms[at + i] = (int64_t)h[2 * (size_t)i + 1];
+        }
+    }
+    return SF_OK;
+}
+
+extern "C" int sf_ndt_line_search_read(sf_ndt *ndt, sf_ndt_ls_row *rows, int64_t cap, int64_t *n)
+{
+    SF_CHECK(ndt, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(ndt->has_rows, SF_ERR_STATE, "ndt: no sf_ndt_align with the line search on has run");
+    const int64_t have = (int64_t)ndt->rows.size();
+    if (n) *n = have;
+    SF_CHECK(!rows || cap >= have, SF_ERR_INVALID, "bad arguments: cap %lld is below the %lld rows", (long long)cap, (long long)have);
+    if (rows) std::copy(ndt->rows.begin(), ndt->rows.end(), rows);
+    return SF_OK;
+}
+
+extern "C" int sf_ndt_align_levels(sf_ndt *const *levels, int n_levels, const double *inits, sf_ndt_result *out, sf_ndt_result *per_level)
+{
+    SF_CHECK(levels && inits && out, SF_ERR_INVALID, "bad arguments");
+    SF_CHECK(n_levels >= 1, SF_ERR_INVALID, "bad arguments: ndt needs at least one level (got %d)", n_levels);
+    for (int l = 0; l < n_levels; ++l) {
+        const sf_ndt *a = levels[l], *f = levels[0];
+        SF_CHECK(a, SF_ERR_INVALID, "bad arguments");
+        SF_CHECK(a->has_target && a->has_source, SF_ERR_INVALID, "bad arguments: ndt level %d needs a target and a source first", l);
+        SF_CHECK(a->ctx == f->ctx, SF_ERR_INVALID, "bad arguments: ndt level %d belongs to another context", l);
+        SF_CHECK(a->batch == f->batch && a->n_src == f->n_src, SF_ERR_INVALID, "bad arguments: ndt level %d holds %d scans of %lld points, level 0 %d of %lld", l, a->batch,
+                 (long long)a->n_src, f->batch, (long long)f->n_src);
+    }
+    const int batch = levels[0]->batch;
+    std::vector<double> poses(inits, inits + 16 * (size_t)batch);
+    std::vector<sf_ndt_result> res((size_t)batch);
+    for (int l = 0; l < n_levels; ++l) {
+        sf_ndt *ndt = levels[l];
+        SF_TRY(ndt_run(ndt, poses.data(), batch, 3 * (size_t)ndt->n_src, (int)ndt->prm.max_iterations, true, res.data(), nullptr));
+        for (int b = 0; b < batch; ++b) {
+            for (int i = 0; i < 16; ++i) poses[16 * (size_t)b + i] = res[(size_t)b].T[i];
+            if (per_level) per_level[(size_t)l * batch + b] = res[(size_t)b];
+        }
+    }
+    for (int b = 0; b < batch; ++b) out[b] = res[(size_t)b];
     return SF_OK;
 }
