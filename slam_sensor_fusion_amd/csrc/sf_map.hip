@@ -1173,13 +1173,15 @@ __device__ __forceinline__ void store_normal_cov(int cnt, const double C[6], int
     }
 }
 
-// the estimate of sorted position j: cells z-major, then y, then one contiguous x-run per row (block_rows), ascending id inside a
-// cell.  The order of these float64 sums is what makes a carried estimate (sf_map_patch) the bits of a full one: k_normals and
-// k_normals_list both come here
-__device__ __forceinline__ void normals_point(const SfGrid &g, double r2, int R, int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+// the estimate of sorted position j: cells z-major, then y, then one contiguous x-run per row (box_rows over the ball_box: the
+// layers of cells that can hold a neighbour), ascending id inside a cell.  The order of these float64 sums is what makes a carried estimate
+// (sf_map_patch) the bits of a full one: k_normals and k_normals_list both come here.  R, trim: normals_walk of the host
+__device__ __forceinline__ void normals_point(const SfGrid &g, double r2, float trim, int R, int64_t j, float4 *__restrict__ nrm4, double *__restrict__ cov6)
 {
     const float4 p = g.pts[j];
-    const int cx = sf::grid_cell((p.x - g.org[0]) * g.inv_h, g.dim[0]), cy = sf::grid_cell((p.y - g.org[1]) * g.inv_h, g.dim[1]), cz = sf::grid_cell((p.z - g.org[2]) * g.inv_h, g.dim[2]);
+    const float gx = (p.x - g.org[0]) * g.inv_h, gy = (p.y - g.org[1]) * g.inv_h, gz = (p.z - g.org[2]) * g.inv_h;
+    const int cx = sf::grid_cell(gx, g.dim[0]), cy = sf::grid_cell(gy, g.dim[1]), cz = sf::grid_cell(gz, g.dim[2]);
+    const sf::BallBox box = sf::ball_box(g, gx, gy, gz, cx, cy, cz, R, trim);
     double sum[3] = {0, 0, 0}, mean[3] = {0, 0, 0}, C[6] = {0, 0, 0, 0, 0, 0};
     int cnt = 0;
     for (int pass = 0; pass < 2; ++pass) {
@@ -1187,7 +1189,7 @@ __device__ __forceinline__ void normals_point(const SfGrid &g, double r2, int R,
             if (cnt < 3) break;
             for (int d = 0; d < 3; ++d) mean[d] = sum[d] / cnt;
         }
-        sf::block_rows(g, cx, cy, cz, R, [&](uint32_t a, uint32_t b) {
+        sf::box_rows(g, box, [&](uint32_t a, uint32_t b) {
             for (uint32_t k = a; k < b; ++k) {
                 const float4 q = g.pts[k];
                 const double ex = (double)q.x - (double)p.x, ey = (double)q.y - (double)p.y, ez = (double)q.z - (double)p.z;
@@ -1203,11 +1205,11 @@ __device__ __forceinline__ void normals_point(const SfGrid &g, double r2, int R,
     store_normal_cov(cnt, C, j, nrm4, cov6);
 }
 
-__global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, int R, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+__global__ __launch_bounds__(256) void k_normals(SfGrid g, double r2, float trim, int R, float4 *__restrict__ nrm4, double *__restrict__ cov6)
 {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= g.n) return;
-    normals_point(g, r2, R, j, nrm4, cov6);
+    normals_point(g, r2, trim, R, j, nrm4, cov6);
 }
 
 // ---- k-NN / hybrid normals: the neighbourhood is the k-NN list of the point's own coordinates (sf_knn.hpp), the
@@ -1257,10 +1259,10 @@ __global__ __launch_bounds__(256) void k_normals_knn(SfGrid g, SfWindow w, int k
 // One lane per changed position -- t < n_groups: the centroid of voxel t (added), beyond: the old point of voxel t - n_groups
 // where it had one (removed).  Every point of the patched index that has it within the radius gets its bit: the cells within
 // R of the position's cell, k_normals' own predicate (symmetric in the two points, so "it is my neighbour" and "I am within
-// its radius" agree exactly).  A removed point is looked up in the cell the OLD grid had it in (its clamp to the old upper
-// face is the one its neighbours' walks saw).  Exact rather than whole cells: the re-estimate costs two walks of 27 cells per
-// marked point, the mark one; a sphere holds a sixth of the points of the cube of cells around it.
-__global__ __launch_bounds__(256) void k_normals_mark(SfGrid g, int odx, int ody, int odz, double r2, int R, const uint32_t *__restrict__ g_fresh, const float *__restrict__ g_centroid,
+// its radius" agree exactly), walked through the same ball_box with the same reach.  A removed point is looked up in the cell the OLD
+// grid had it in (its clamp to the old upper face is the one its neighbours' walks saw).  Exact rather than whole cells: the
+// re-estimate costs two walks per marked point, the mark one; a sphere holds a sixth of the points of the cube of cells around it.
+__global__ __launch_bounds__(256) void k_normals_mark(SfGrid g, int odx, int ody, int odz, double r2, float trim, int R, const uint32_t *__restrict__ g_fresh, const float *__restrict__ g_centroid,
                                                        const float *__restrict__ g_old, int64_t n_groups, uint32_t *__restrict__ bitmap)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1271,10 +1273,10 @@ __global__ __launch_bounds__(256) void k_normals_mark(SfGrid g, int odx, int ody
     const float *src = removed ? g_old : g_centroid;
     const float px = src[3 * v], py = src[3 * v + 1], pz = src[3 * v + 2];
     const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
-    const int cx = sf::grid_cell((px - g.org[0]) * g.inv_h, removed ? odx : nx), cy = sf::grid_cell((py - g.org[1]) * g.inv_h, removed ? ody : ny),
-              cz = sf::grid_cell((pz - g.org[2]) * g.inv_h, removed ? odz : nz);
-    if (max(cx - R, 0) > min(cx + R, nx - 1)) return; // (a removed point beyond a grid that shrank; only x is tested: block_rows reads the bounds of the x-run before any test, empty y / z ranges never enter their loops)
-    sf::block_rows(g, cx, cy, cz, R, [&](uint32_t a, uint32_t b) {
+    const float gx = (px - g.org[0]) * g.inv_h, gy = (py - g.org[1]) * g.inv_h, gz = (pz - g.org[2]) * g.inv_h;
+    const int cx = sf::grid_cell(gx, removed ? odx : nx), cy = sf::grid_cell(gy, removed ? ody : ny), cz = sf::grid_cell(gz, removed ? odz : nz);
+    // (a removed point beyond a grid that shrank: box_rows visits nothing when the x-range is empty, before it reads a bound; empty y / z ranges never enter their loops)
+    sf::box_rows(g, sf::ball_box(g, gx, gy, gz, cx, cy, cz, R, trim), [&](uint32_t a, uint32_t b) {
         for (uint32_t k = a; k < b; ++k) {
             const float4 q = g.pts[k];
             const double ex = (double)px - (double)q.x, ey = (double)py - (double)q.y, ez = (double)pz - (double)q.z;
@@ -1308,14 +1310,28 @@ __global__ __launch_bounds__(256) void k_normals_compact(const uint32_t *__restr
     if ((int64_t)o < cap) list[o] = (uint32_t)p;
 }
 
-__global__ __launch_bounds__(256) void k_normals_list(SfGrid g, double r2, int R, const uint32_t *__restrict__ list, int64_t n_list, float4 *__restrict__ nrm4, double *__restrict__ cov6)
+__global__ __launch_bounds__(256) void k_normals_list(SfGrid g, double r2, float trim, int R, const uint32_t *__restrict__ list, int64_t n_list, float4 *__restrict__ nrm4, double *__restrict__ cov6)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_list) return;
-    normals_point(g, r2, R, (int64_t)list[t], nrm4, cov6);
+    normals_point(g, r2, trim, R, (int64_t)list[t], nrm4, cov6);
 }
 
-inline int normals_reach(float radius, float h) { return std::max(1, (int)std::ceil((double)radius / (double)h - 1e-9)); }
+// What k_normals, k_normals_mark and k_normals_list walk by, one function so that a carried estimate and a full one see the same
+// cells: the rule's r2 in float64, the reach of sf_walk.hpp (c) in float64, capped by the grid before the conversion, and
+// ball_box's trim for that reach, rounded up (a larger trim only keeps more cells).
+struct NormalsWalk { double r2; float trim; int R; };
+inline NormalsWalk normals_walk(const SfGrid &g, float radius)
+{
+    NormalsWalk w;
+    w.r2 = (double)radius * (double)radius;
+    const double reach = std::ceil(((double)radius * (1.0 + 1.0e-6) + (double)g.gap_eps) * (double)g.inv_h);
+    w.R = (int)std::min(std::max(reach, 1.0), (double)std::max(g.dim[0], std::max(g.dim[1], g.dim[2])));
+    const double trim = ((double)radius * (1.0 + 1.0e-6) + (double)g.gap_eps) * (double)g.inv_h - (double)(w.R - 1);
+    w.trim = (float)trim;
+    if ((double)w.trim < trim) w.trim = std::nextafter(w.trim, INFINITY);
+    return w;
+}
 
 int carry_reestimate(sf_map *m, const sf_cloud::MergeRecord &rec, const int old_dim[3], float radius, bool with_cov, int64_t *n_dirty)
 {
@@ -1325,8 +1341,7 @@ int carry_reestimate(sf_map *m, const sf_cloud::MergeRecord &rec, const int old_
     const int64_t n = g.n, ng = rec.n_groups;
     *n_dirty = 0;
     if (n <= 0) return SF_OK;
-    const double r2 = (double)radius * (double)radius;
-    const int R = normals_reach(radius, g.h);
+    const NormalsWalk w = normals_walk(g, radius);
     // [bitmap: 8 words per block of 256 positions | counts | their exclusive prefix (one entry more: the total)]
     const int64_t nb = sf::div_up(n, 256);
     const size_t off_cnt = 4 * 8 * (size_t)nb, off_pre = off_cnt + 4 * (size_t)(nb + 1), total = off_pre + 4 * (size_t)(nb + 1);
@@ -1334,7 +1349,7 @@ int carry_reestimate(sf_map *m, const sf_cloud::MergeRecord &rec, const int old_
     unsigned char *base = m->carry_tmp.as<unsigned char>();
     uint32_t *bitmap = reinterpret_cast<uint32_t *>(base), *blk_cnt = reinterpret_cast<uint32_t *>(base + off_cnt), *blk_pre = reinterpret_cast<uint32_t *>(base + off_pre);
     SF_HIP(hipMemsetAsync(base, 0, off_pre, st)); // bitmap and counts (the count behind the last block stays 0)
-    hipLaunchKernelGGL(k_normals_mark, dim3(nblk(2 * ng)), dim3(256), 0, st, g, old_dim[0], old_dim[1], old_dim[2], r2, R, rec.g_fresh, rec.g_centroid, rec.g_old, ng, bitmap);
+    hipLaunchKernelGGL(k_normals_mark, dim3(nblk(2 * ng)), dim3(256), 0, st, g, old_dim[0], old_dim[1], old_dim[2], w.r2, w.trim, w.R, rec.g_fresh, rec.g_centroid, rec.g_old, ng, bitmap);
     hipLaunchKernelGGL(k_normals_count, dim3(nblk(nb)), dim3(256), 0, st, bitmap, nb, blk_cnt);
     SF_TRY(sf::scan_u32<0>(ctx, blk_cnt, blk_pre, nb + 1));
     uint32_t *h_cnt = &ctx->h_pinned->carry_count;
@@ -1348,7 +1363,7 @@ int carry_reestimate(sf_map *m, const sf_cloud::MergeRecord &rec, const int old_
     SF_TRY(m->carry_list.reserve(sizeof(uint32_t) * (size_t)std::max<int64_t>(nd + nd / 2, 1 << 16)));
     uint32_t *list = m->carry_list.as<uint32_t>();
     hipLaunchKernelGGL(k_normals_compact, dim3((unsigned)nb), dim3(256), 0, st, bitmap, blk_pre, n, nd, list);
-    hipLaunchKernelGGL(k_normals_list, dim3(nblk(nd)), dim3(256), 0, st, g, r2, R, list, nd, m->nrm4.as<float4>(), with_cov ? m->cov6.as<double>() : nullptr);
+    hipLaunchKernelGGL(k_normals_list, dim3(nblk(nd)), dim3(256), 0, st, g, w.r2, w.trim, w.R, list, nd, m->nrm4.as<float4>(), with_cov ? m->cov6.as<double>() : nullptr);
     SF_HIP(hipGetLastError());
     return SF_OK; // enqueued behind the patch: every reader of the normals is on this stream
 }
@@ -1443,9 +1458,9 @@ extern "C" int sf_map_estimate_normals_cov(sf_map *m, float radius, int with_cov
 {
     SF_CHECK(m && m->built, SF_ERR_STATE, "map not built");
     SF_CHECK(radius > 0, SF_ERR_INVALID, "radius must be positive");
-    const int R = normals_reach(radius, m->grid.h);
+    const NormalsWalk w = normals_walk(m->grid, radius);
     return estimate_normals(m, 0, radius, with_covariance, [&](float4 *nrm4, double *cov6) {
-        hipLaunchKernelGGL(k_normals, dim3(nblk(m->grid.n)), dim3(256), 0, m->ctx->stream, m->grid, (double)radius * (double)radius, R, nrm4, cov6);
+        hipLaunchKernelGGL(k_normals, dim3(nblk(m->grid.n)), dim3(256), 0, m->ctx->stream, m->grid, w.r2, w.trim, w.R, nrm4, cov6);
     });
 }
 

@@ -1,14 +1,14 @@
 // sf_walk.hpp — the two lane-per-point walks over the block of cells around a point of the uniform-grid map index (device side,
-// gfx950): radius_walk, trimmed by the gaps against a float32 radius rule (the radius filter, clustering), and block_rows,
-// untrimmed (the normals, their carry marks, the neighbour table).  The geometry they rest on is sf_nn.hpp's.
+// gfx950): radius_walk, trimmed by the gaps against a float32 radius rule (the radius filter, clustering), box_rows over a
+// ball_box, trimmed per axis against the float64 rule of the normals and their carry marks, and block_rows, untrimmed (the
+// neighbour table).  The geometry they rest on is sf_nn.hpp's.
 #pragma once
 #include "sf_nn.hpp"
 
 namespace sf {
 
 // visit(a, b) for the cell_start run [a, b) of every (z, y) row of the block of radius R around cell (cx, cy, cz): z-major, then
-// y, one contiguous x-run per row.  (cx, cy, cz) may lie outside the grid on the upper side (k_normals_mark); the caller then
-// makes sure the x-run is not empty, because its bounds are read before any test.
+// y, one contiguous x-run per row.  The cell is one of the grid: the bounds of the x-run are read before any test.
 template <class F>
 __device__ __forceinline__ void block_rows(const SfGrid &g, int cx, int cy, int cz, int R, F visit)
 {
@@ -20,6 +20,50 @@ __device__ __forceinline__ void block_rows(const SfGrid &g, int cx, int cy, int 
         for (int y = y0; y <= y1; ++y) {
             const size_t row = ((size_t)z * ny + y) * nx;
             visit(g.cell_start[row + x0], g.cell_start[row + x1 + 1]);
+        }
+}
+
+// block_rows for the float64 rule of the normals and their carry marks, ex^2 + ey^2 + ez^2 <= r2d on the exact differences of the
+// float32 coordinates: the box of cells within R of the position's cell, less on every axis and side the outermost layer of cells
+// where it holds nothing the rule accepts.  ball_box decides that once per position (six comparisons, no loop), box_rows walks the
+// box as block_rows walks its block (the same rows in the same order, nothing computed per row), so every float64 sum over the
+// accepted points keeps its order and its bits whatever R is, as long as R reaches them all.  (gx, gy, gz) are the grid
+// coordinates G of the position, (cx, cy, cz) its cell, which may lie beyond the grid on the upper side (k_normals_mark): an axis
+// whose range comes out empty makes box_rows visit nothing, before any bound is read.
+// The argument, in the terms of (a) - (c) of radius_walk below.  (a) holds exactly here: per axis |p - q| <= r, the differences
+// being exact in float64.  (c) gives R = ceil((r (1 + 1e-6) + gap_eps) inv_h), normals_walk of the host.  The trim: f = G(p) - c
+// is exact in float32 (c = floor(G(p)), or the clamp of it).  A point q of a cell <= c - R has G(q) < c - R + 1, so
+// G(p) - G(q) > f + R - 1; one of a cell >= c + R has G(q) >= c + R (the clamped last cell too), so G(q) - G(p) >= R - f.  By (b)
+// |p - q| inv_h >= |G(p) - G(q)| - S, so with trim = (r (1 + 1e-6) + gap_eps) inv_h - (R - 1), rounded up by the host -- the
+// expression under the ceil of R less R - 1, hence in (0, 1] --, the lower layer holds no neighbour when f >= trim and the upper
+// one when fl(1 - f) >= trim: gap_eps inv_h exceeds S by 2^-23 maxdim, more than the one rounding of 1 - f.  No layer nearer than
+// R can ever be left out (its gap is below R - 1 <= r inv_h cells), so one comparison per side is all a loop could do.  At a
+// radius of exactly one cell R = 2 and trim = 1e-6 + gap_eps inv_h: the walk stays the 27 cells it was with the reach
+// ceil(radius / h), except within that margin of a face.  The margin is kept that small because a lane that keeps a layer makes
+// its whole wave wait for it: with 1e-3 in place of 1e-6 the launch was 6 % slower.  (Per-row skips and x-trims as in radius_walk,
+// and the same per-axis trim through trim_left / trim_right loops, were measured as well: profiles/normals_reach_ab.txt.)
+struct BallBox { int xa, xb, ya, yb, za, zb; };
+__device__ __forceinline__ BallBox ball_box(const SfGrid &g, float gx, float gy, float gz, int cx, int cy, int cz, int R, float trim)
+{
+    const float fx = gx - (float)cx, fy = gy - (float)cy, fz = gz - (float)cz;
+    BallBox b;
+    b.xa = max(cx - R + (fx >= trim ? 1 : 0), 0);
+    b.xb = min(cx + R - (1.0f - fx >= trim ? 1 : 0), g.dim[0] - 1);
+    b.ya = max(cy - R + (fy >= trim ? 1 : 0), 0);
+    b.yb = min(cy + R - (1.0f - fy >= trim ? 1 : 0), g.dim[1] - 1);
+    b.za = max(cz - R + (fz >= trim ? 1 : 0), 0);
+    b.zb = min(cz + R - (1.0f - fz >= trim ? 1 : 0), g.dim[2] - 1);
+    return b;
+}
+template <class F>
+__device__ __forceinline__ void box_rows(const SfGrid &g, const BallBox &b, F visit)
+{
+    if (b.xa > b.xb) return;
+    const int nx = g.dim[0], ny = g.dim[1];
+    for (int z = b.za; z <= b.zb; ++z)
+        for (int y = b.ya; y <= b.yb; ++y) {
+            const size_t row = ((size_t)z * ny + y) * nx;
+            visit(g.cell_start[row + b.xa], g.cell_start[row + b.xb + 1]);
         }
 }
 
@@ -40,7 +84,8 @@ __device__ __forceinline__ void block_rows(const SfGrid &g, int cx, int cy, int 
 //     slack SfGrid carries for exactly this.
 // (c) Reach: floor(a) - floor(b) <= ceil(D) whenever a - b <= D, and the clamp only brings cells closer, so q's cell is within
 //     R = ceil((r (1 + 1e-6) + gap_eps) inv_h) of p's on every axis (the host computes it in float64; 1e-6 covers (a) and its own
-//     roundings).  normals_reach's ceil(radius / h - 1e-9) is one short when r is a whole number of cells and p, q straddle it.
+//     roundings).  normals_walk (sf_map.hip) takes the same expression for the float64 rule of ball_box: ceil(radius / h) alone is
+//     one short when r is a whole number of cells and G(p), G(q) round to either side of two faces r apart.
 // (d) Row skip and x-trim (trim_left / trim_right), the rule of knn_search with tau = r2: a point binned in cell c != cq has G on
 //     the far side of the face between, so by (b) its true axis distance from p is at least safe_gap(cell_gap * h, gap_eps), up to
 //     the relative roundings of forming it (a few u).  A row or an end cell is left out only when the sum g2 of those squared gaps

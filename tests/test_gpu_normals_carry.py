@@ -84,6 +84,71 @@ def test_carried_normals_equal_a_full_estimate(api, ctx, synth, cell, lattice, r
         api.voxel_merge_min_points(prev)
 
 
+@pytest.mark.parametrize("cov", [False, True])
+def test_a_patch_at_one_end_of_a_straddling_pair_reaches_the_other(api, ctx, cov):
+    """q and p lie within the radius (0.25 m = one cell) of each other by the float64 rule, in cells two apart on x: the float32
+    grid coordinates round to either side of two faces (tests/normals_ref_np.py: find_straddles).  A growth step that adds p, and
+    one that moves q out of p's radius (a point merged into q's voxel: the old q is a removed position), must mark the other end:
+    the carried estimate equals the full one bit for bit and the other end's count moves by one.  Every point sits alone in its
+    0.1 m voxel, so the voxel filter hands its coordinates through unchanged."""
+    import normals_ref_np as nr
+    radius = cell = 0.25
+    r32, found = nr.find_straddles(cell, 1, 77)
+    assert r32 == np.float32(radius) and len(found) > 0
+    org, qx, px = found[0]
+    base = np.array([org, org + np.float32(3.0), org + np.float32(3.0)], np.float32)
+    q, p = base.copy(), base.copy()
+    q[0], p[0] = qx, px
+    around = lambda e, s: [e + np.array(d, np.float32) for d in ((0.12 * s, 0, 0), (0, 0.13, 0), (0, -0.13, 0), (0, 0, 0.13), (0, 0, -0.13))]
+    anchor, cap = np.full(3, org, np.float32), np.full(3, org + np.float32(70 * cell), np.float32)
+    start = np.stack([anchor, cap, q] + around(q, -1.0) + around(p, 1.0)).astype(np.float32)
+    frac = (float(q[1]) / LEAF) % 1.0
+    beside_q = (q + np.array([0, 0.02 if frac < 0.5 else -0.02, 0], np.float32)).astype(np.float32)      # inside q's voxel, 0.01 m off the pair's line after the merge
+    prev = api.voxel_merge_min_points(0)
+    try:
+        dev = api.Cloud(ctx, start)
+        dev.voxel_downsample(LEAF, "pcl")
+        assert len(dev) == len(start) and (dev.download() == q).all(1).sum() == 1
+        mp = api.Map(ctx, dev, cell)
+        mp.estimate_normals(radius, cov)
+        mp.set_normals_carry(True)
+
+        def row_of(pt):
+            at = np.flatnonzero((dev.download() == pt).all(1))
+            assert len(at) == 1, pt
+            return int(at[0])
+
+        def count_of(m, pt):
+            return int(m.download_normals()[1][row_of(pt)])
+        before = count_of(mp, q)
+        assert before == 6
+        # 1. p arrives
+        st, merged = dev.voxel_merge(api.Cloud(ctx, p[None]), LEAF)
+        assert st == 0 and merged and len(dev) == len(start) + 1
+        assert mp.patch(dev), mp.last_patch
+        assert mp.normals_carry_info()[0] == 1
+        ix = mp.index()
+        g = lambda x: int(np.floor(np.float32(np.float32(x - ix["org"][0]) * np.float32(ix["inv_h"]))))
+        assert ix["org"][0] == org and g(p[0]) - g(q[0]) == 2 and float(p[0]) - float(q[0]) <= radius      # the pair straddles in this index
+        ref = _reference(api, ctx, dev, 0, cell, radius, cov)
+        assert count_of(ref, q) == before + 1 and count_of(ref, p) == 7
+        _assert_same_normals(mp, ref, cov, "the upper end of a straddling pair added")
+        ref.close()
+        # 2. q moves 0.01 m sideways: out of p's radius; only its OLD position is within it
+        st, merged = dev.voxel_merge(api.Cloud(ctx, beside_q[None]), LEAF)
+        assert st == 0 and merged and len(dev) == len(start) + 1
+        assert (dev.download() == q).all(1).sum() == 0
+        assert mp.patch(dev), mp.last_patch
+        assert mp.normals_carry_info()[0] == 1
+        ref = _reference(api, ctx, dev, 0, cell, radius, cov)
+        assert count_of(ref, p) == 6
+        _assert_same_normals(mp, ref, cov, "the lower end of a straddling pair removed")
+        ref.close()
+        mp.close()
+    finally:
+        api.voxel_merge_min_points(prev)
+
+
 def test_only_the_changed_neighbourhood_is_estimated_again(api, ctx, synth):
     """points re-estimated: at least every point with a changed position within the radius (the kernel's own predicate), at most
     the points whose cell lies within R + 1 cells of a pending point's cell -- an old point and its new centroid share a
