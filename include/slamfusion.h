@@ -236,6 +236,33 @@ int sf_map_knn(sf_map *m, const float *queries, int64_t n, int k, float max_d2, 
  * The map remembers (k, max_radius, with_covariance) in place of the radius: with sf_map_set_normals_carry on, sf_map_patch is
  * followed by this estimate in full on every path (sf_map_normals_carry_info: {0, 0, n, n}). */
 int sf_map_estimate_normals_knn(sf_map *m, int k, float max_radius, int with_covariance);
+/* Radius search with variable-length rows (extension, no reference code): pcl radiusSearch, Open3D
+ * search_radius_vector_3d (search_hybrid_vector_3d is sf_map_knn(q, max_nn, r2)).  r2 = (float)(radius * radius); row i holds every
+ * indexed point p the window accepts with d2(q_i, p) < r2 under the float32, unfused, strict rule of sf_map_nn / sf_map_knn /
+ * sf_map_radius_outliers; idx in ORIGINAL point order, d2 the float32 value that was compared.  So min(count_i, 64) and the first 64
+ * entries of a distance-ordered row are exactly sf_map_knn(q_i, 64, r2).  A non-finite query or an empty map gives an empty row
+ * (no walk).  The rows are CSR: offsets[n + 1] (host, may be NULL), offsets[i + 1] - offsets[i] the count of row i; the entries
+ * stay on the device, owned by the map, until the next radius call, sf_map_build or sf_map_patch, and sf_map_radius_results
+ * downloads them.
+ * search: arbitrary queries (host pointer, as sf_map_knn), the window honoured.  graph: the queries are the map's own points, row i
+ *   belongs to ORIGINAL point i, the window is ignored (as the outlier and clustering calls ignore it); a point that is not indexed
+ *   has an empty row and appears in no row; a point's own entry (d2 = 0) is in its row, so the counts are sf_map_radius_outliers'.
+ * results: the rows, concatenated; either pointer may be NULL; *total is always set (0 with no lists); cap < total with a pointer
+ *   given is SF_ERR_INVALID and writes nothing; SF_ERR_STATE when there are no lists (no call so far, or a build or patch since).
+ * SF_ERR_INVALID: a radius that is not positive and finite or whose r2 is not; an order that is not one of the two; n < 0.
+ * SF_ERR_STATE: a map that is not built.  n == 0 is SF_OK with offsets[0] = 0.  SF_ERR_OVERFLOW: more than 2^32 - 2 entries in all
+ * (the offsets on the device are 32-bit, the sort takes no more) -- decided from a 64-bit sum of the counts before anything is
+ * reserved or filled; SF_ERR_NOMEM: an allocation failed.  Both leave the map without lists and otherwise usable.
+ * stats: the rows, those searched (finite queries / indexed points of a map that is not empty), the rows of count 0, the entries,
+ * the longest row.  fill: both forms give the same bytes; automatic is the one measured faster. */
+#define SF_RADIUS_ORDER_INDEX    0   /* rows ascend in position in the index (the order of the walk) */
+#define SF_RADIUS_ORDER_DISTANCE 1   /* rows ascend in (bits of d2, position in the index): the order of sf_map_knn */
+typedef struct { int64_t n_queries, n_searched, n_empty, total, max_count; } sf_radius_stats;
+int sf_map_radius_search(sf_map *m, const float *queries, int64_t n, double radius, int order, int64_t *offsets, sf_radius_stats *stats);
+int sf_map_radius_graph(sf_map *m, double radius, int order, int64_t *offsets, sf_radius_stats *stats);
+int sf_map_radius_results(sf_map *m, int32_t *idx, float *d2, int64_t cap, int64_t *total);
+int sf_map_set_radius_fill(sf_map *m, int mode);          /* 0 = automatic (default), 1 = one lane per row, 2 = one wave per row */
+int sf_map_radius_launch_ms(sf_map *m, float ms[3]);      /* count+scan, fill, sort of the last call; zeros unless sf_map_profile_launches is on */
 /* Outlier removal (extension, no reference code): pcl::StatisticalOutlierRemoval / pcl::RadiusOutlierRemoval,
  * Open3D remove_statistical_outlier / remove_radius_outlier.  The window is ignored, as the normals passes ignore it; the map's
  * index, normals and neighbour table are not modified.

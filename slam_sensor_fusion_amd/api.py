@@ -76,6 +76,23 @@ class OutlierStats(C.Structure):
                     threshold=float(self.threshold))
 
 
+SF_KNN_MAX = 64
+RADIUS_ORDERS = {"index": 0, "distance": 1}  # SF_RADIUS_ORDER_*
+RADIUS_FILLS = {"auto": 0, "lane": 1, "wave": 2}
+
+
+def _radius_order(order):
+    return RADIUS_ORDERS[order] if order in RADIUS_ORDERS else int(order)
+
+
+class RadiusStats(C.Structure):
+    """sf_radius_stats: the rows of a radius call, those searched, those left empty, the entries in all and the longest row."""
+    _fields_ = [("n_queries", C.c_int64), ("n_searched", C.c_int64), ("n_empty", C.c_int64), ("total", C.c_int64), ("max_count", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class ClusterStats(C.Structure):
     """sf_cluster_stats: what a clustering call found (n_noise, n_kept: the indexed points labelled -1 / the points with a label)."""
     _fields_ = [(name, C.c_int64) for name in ("n_points", "n_valid", "n_core", "n_border", "n_noise", "n_clusters", "largest_size", "n_kept")]
@@ -453,6 +470,11 @@ def load_library():
     lib.sf_ndt_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sf_ndt_line_search_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.sf_ndt_align_levels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_map_radius_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_map_radius_graph.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_map_radius_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_map_set_radius_fill.argtypes = [C.c_void_p, C.c_int]
+    lib.sf_map_radius_launch_ms.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_launch_schedule.argtypes =[C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1149,6 +1171,50 @@ class Map:
         cnt = np.empty(len(q), np.int32)
         _check(self.lib.sf_map_knn(self.h, _p(q), C.c_int64(len(q)), C.c_int(k), C.c_float(max_d2), _p(idx), _p(d2), _p(cnt)))
         return idx, d2, cnt
+
+    def _radius_rows(self, rows, call):
+        offsets = np.zeros(rows + 1, np.int64)
+        st, total = RadiusStats(), C.c_int64()
+        _check(call(_p(offsets), C.byref(st)))
+        idx = np.empty(int(st.total), np.int32)
+        d2 = np.empty(int(st.total), np.float32)
+        _check(self.lib.sf_map_radius_results(self.h, _p(idx), _p(d2), C.c_int64(len(idx)), C.byref(total)))
+        assert total.value == len(idx) == offsets[-1]
+        return offsets, idx, d2, st.as_dict()
+
+    def radius_search(self, queries, radius, order="index"):
+        """sf_map_radius_search (pcl radiusSearch, Open3D search_radius_vector_3d): every indexed point the window accepts with float32
+        d2 < float32(radius^2) of each query -> (offsets int64 [n + 1], idx int32 [total] in original point order, d2 float32 [total],
+        stats dict); row i is idx[offsets[i]:offsets[i + 1]].  order "index": rows ascend in position in the index; "distance": in
+        (d2, position), the order of knn, so a row's first 64 entries are knn(q, 64, float32(radius^2))."""
+        q = _f32(queries).reshape(-1, 3)
+        o = _radius_order(order)
+        return self._radius_rows(len(q), lambda off, st: self.lib.sf_map_radius_search(self.h, _p(q), C.c_int64(len(q)), C.c_double(radius), C.c_int(o), off, st))
+
+    def radius_graph(self, radius, order="index"):
+        """sf_map_radius_graph: radius_search of the map's own points without the window, row i for original point i (itself
+        included; empty for a point that is not indexed); the row lengths are radius_outliers' n_neighbors."""
+        o = _radius_order(order)
+        return self._radius_rows(len(self), lambda off, st: self.lib.sf_map_radius_graph(self.h, C.c_double(radius), C.c_int(o), off, st))
+
+    def hybrid_search(self, queries, radius, max_nn):
+        """Open3D search_hybrid_vector_3d: at most max_nn nearest indexed points within radius = knn(queries, max_nn,
+        float32(radius^2)) -> (idx [n, max_nn], d2 [n, max_nn], count [n])."""
+        if not 1 <= int(max_nn) <= SF_KNN_MAX:
+            raise ValueError("hybrid_search: max_nn must be 1 .. %d (got %r)" % (SF_KNN_MAX, max_nn))
+        return self.knn(queries, int(max_nn), np.float32(float(radius) * float(radius)))
+
+    def set_radius_fill(self, mode="auto"):
+        """sf_map_set_radius_fill: "auto" (default: the form measured faster, DESIGN.md §27), "lane" (one lane per row) or "wave" (one wave per row);
+        the rows are the same bytes either way."""
+        _check(self.lib.sf_map_set_radius_fill(self.h, C.c_int(RADIUS_FILLS[mode] if mode in RADIUS_FILLS else int(mode))))
+        return self
+
+    def radius_launch_ms(self):
+        """sf_map_radius_launch_ms: (count + scan, fill, sort) device ms of the last radius call; zeros unless profile_launches is on."""
+        ms = (C.c_float * 3)()
+        _check(self.lib.sf_map_radius_launch_ms(self.h, ms))
+        return tuple(float(v) for v in ms)
 
     def statistical_outliers(self, k, std_ratio=2.0, flavour="pcl"):
         """sf_map_statistical_outliers: -> (keep bool [n], mean_dist float64 [n], stats dict), original point order.  flavour "pcl":

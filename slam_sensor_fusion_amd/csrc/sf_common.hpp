@@ -235,6 +235,17 @@ struct sf_map {
     sf::DevBuf out_flags, out_val, out_red;
     // sf_map_cluster_* (and the sf_cloud_*_cluster[s] calls on a temporary map): the union-find, labels and sizes (sf_cluster.hpp, ClusterBufs)
     sf::DevBuf cl;
+    // sf_map_radius_search / sf_map_radius_graph (sf_radius.hpp): counts and offsets uint32[rows + 1], the four counters, and the
+    // lists -- ids and float32 d2 in index order, or the sort's ping-pong keys ((row << 32) | bits of d2) and ids in distance order.
+    // rad_idx / rad_d2 point at what holds the rows of the last call while rad_valid; build and patch drop them (map_points_moved).
+    sf::DevBuf rad_cnt, rad_off, rad_red, rad_ids, rad_ids_alt, rad_d2, rad_keys, rad_keys_alt;
+    sf::DevBuf rad_q;                // the queries of sf_map_radius_search on the device
+    const int32_t *rad_idx = nullptr;
+    bool rad_valid = false;
+    int64_t rad_total = 0;
+    int rad_fill = 0;                // sf_map_set_radius_fill: 0 automatic, 1 one lane per row, 2 one wave per row
+    hipEvent_t rad_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; // count | scan || fill | sort, when sf_map_profile_launches is on
+    float rad_ms[3] = {0.0f, 0.0f, 0.0f};
     int64_t n = 0;
     bool built = false, has_normals = false, has_cov = false;
     uint64_t generation = 0; // process-unique stamp of the index contents (build / normals): captured hipGraphs key on it

@@ -213,6 +213,10 @@ extern "C" void sf_map_destroy(sf_map *m)
     m->nbr.release();
     m->out_flags.release(); m->out_val.release(); m->out_red.release();
     m->cl.release();
+    m->rad_cnt.release(); m->rad_off.release(); m->rad_red.release(); m->rad_ids.release(); m->rad_ids_alt.release(); m->rad_d2.release();
+    m->rad_keys.release(); m->rad_keys_alt.release(); m->rad_q.release();
+    for (hipEvent_t ev : m->rad_ev)
+        if (ev) { hipError_t e2 = hipEventDestroy(ev); (void)e2; }
     sf_ctx *ctx = m->ctx;
     delete m;
     sf::ctx_release(ctx);
@@ -895,6 +899,7 @@ void map_points_moved(sf_map *m)
 {
     m->pts_stamp = next_generation();
     m->nbr_stamp = 0; // the table (its allocation is kept) describes other points
+    m->rad_valid = false; // ... and so do the radius lists
     if (m->served) m->moved_after_serving = true;
 }
 
@@ -1763,6 +1768,9 @@ extern "C" int sf_cloud_remove_radius_outliers(sf_cloud *c, double radius, int m
     SF_CHECK_ROR(radius, min_neighbors);
     return filter_cloud(c, cell, stats, [=](sf_map *m, sf_outlier_stats *st) { return radius_outliers_device(m, radius, min_neighbors, st); });
 }
+
+// ------------------------------------------------------------------ radius search with variable-length rows (extension, no reference code)
+#include "sf_radius.hpp"
 
 // ------------------------------------------------------------------ clustering (extension, no reference code)
 #include "sf_cluster.hpp"

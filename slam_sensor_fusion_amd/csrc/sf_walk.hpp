@@ -91,7 +91,11 @@ __device__ __forceinline__ void box_rows(const SfGrid &g, const BallBox &b, F vi
 //     the relative roundings of forming it (a few u).  A row or an end cell is left out only when the sum g2 of those squared gaps
 //     has g2 * 0.998 >= r2; then dy^2 + dz^2 (+ dx^2) >= g2 (1 - 8u) and fl(d2) >= that (1 - 5u) >= r2 / 0.998 * (1 - 13u) > r2:
 //     rejected by the rule itself.
-template <bool AUX, bool END, class F>
+// DETAIL: visit(k, aux[k], accepted, d2, q) instead, with the float32 d2 that was compared and the candidate q (its id in q.w), for
+// the callers that hand the neighbours out (sf_radius.hpp); for an empty slot of a trip only accepted = false means anything (q is
+// zeros and d2 the distance to them).  The default is the walk as it was,
+// token for token: the choice is made while compiling.
+template <bool AUX, bool END, bool DETAIL = false, class F>
 __device__ __forceinline__ void radius_walk(const SfGrid &g, const float4 p, float r2, int R, uint32_t end, const int32_t *__restrict__ aux, F visit)
 {
     const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
@@ -117,11 +121,47 @@ __device__ __forceinline__ void radius_walk(const SfGrid &g, const float4 p, flo
                 const float4 q0 = load_point(g, k, true), q1 = load_point(g, k + 1, k + 1 < b), q2 = load_point(g, k + 2, k + 2 < b), q3 = load_point(g, k + 3, k + 3 < b);
                 const int32_t a0 = AUX ? aux[k] : 0, a1 = AUX ? aux[k + 1 < b ? k + 1 : k] : 0, a2 = AUX ? aux[k + 2 < b ? k + 2 : k] : 0,
                               a3 = AUX ? aux[k + 3 < b ? k + 3 : k] : 0;
-                visit(k, a0, l2_simple(p.x, p.y, p.z, q0.x, q0.y, q0.z) < r2);
-                visit(k + 1, a1, k + 1 < b && l2_simple(p.x, p.y, p.z, q1.x, q1.y, q1.z) < r2);
-                visit(k + 2, a2, k + 2 < b && l2_simple(p.x, p.y, p.z, q2.x, q2.y, q2.z) < r2);
-                visit(k + 3, a3, k + 3 < b && l2_simple(p.x, p.y, p.z, q3.x, q3.y, q3.z) < r2);
+                if constexpr (DETAIL) {
+                    const float d0 = l2_simple(p.x, p.y, p.z, q0.x, q0.y, q0.z), d1 = l2_simple(p.x, p.y, p.z, q1.x, q1.y, q1.z),
+                                d2 = l2_simple(p.x, p.y, p.z, q2.x, q2.y, q2.z), d3 = l2_simple(p.x, p.y, p.z, q3.x, q3.y, q3.z);
+                    visit(k, a0, d0 < r2, d0, q0);
+                    visit(k + 1, a1, k + 1 < b && d1 < r2, d1, q1);
+                    visit(k + 2, a2, k + 2 < b && d2 < r2, d2, q2);
+                    visit(k + 3, a3, k + 3 < b && d3 < r2, d3, q3);
+                } else {
+                    visit(k, a0, l2_simple(p.x, p.y, p.z, q0.x, q0.y, q0.z) < r2);
+                    visit(k + 1, a1, k + 1 < b && l2_simple(p.x, p.y, p.z, q1.x, q1.y, q1.z) < r2);
+                    visit(k + 2, a2, k + 2 < b && l2_simple(p.x, p.y, p.z, q2.x, q2.y, q2.z) < r2);
+                    visit(k + 3, a3, k + 3 < b && l2_simple(p.x, p.y, p.z, q3.x, q3.y, q3.z) < r2);
+                }
             }
+        }
+    }
+}
+
+// The rows of radius_walk alone: visit(a, b) for the x-run [a, b) of sorted positions of every row the walk above would enter, in
+// its order, with its skips and trims -- for a caller that deals the candidates of a run over the lanes of a wave (the wave fill
+// of sf_radius.hpp).  The same expressions on the same inputs, so the same runs: what one form visits the other does.
+template <class F>
+__device__ __forceinline__ void radius_runs(const SfGrid &g, const float4 p, float r2, int R, F visit)
+{
+    const int nx = g.dim[0], ny = g.dim[1], nz = g.dim[2];
+    const float gx = (p.x - g.org[0]) * g.inv_h, gy = (p.y - g.org[1]) * g.inv_h, gz = (p.z - g.org[2]) * g.inv_h;
+    const int cx = grid_cell(gx, nx), cy = grid_cell(gy, ny), cz = grid_cell(gz, nz);
+    const int x0 = max(cx - R, 0), x1 = min(cx + R, nx - 1);
+    const int y0 = max(cy - R, 0), y1 = min(cy + R, ny - 1);
+    const int z0 = max(cz - R, 0), z1 = min(cz + R, nz - 1);
+    const float h = g.h, ge = g.gap_eps;
+    for (int z = z0; z <= z1; ++z) {
+        const float rz = safe_gap(cell_gap(gz, z, cz) * h, ge);
+        if (!(rz * rz * 0.998f < r2)) continue;
+        for (int y = y0; y <= y1; ++y) {
+            const float ry = safe_gap(cell_gap(gy, y, cy) * h, ge);
+            const float g2 = ry * ry + rz * rz;
+            if (!(g2 * 0.998f < r2)) continue;
+            const int xa = trim_left(g, gx, cx, x0, g2, r2), xb = trim_right(g, gx, cx, x1, g2, r2);
+            const size_t row = ((size_t)z * ny + y) * nx;
+            visit(g.cell_start[row + xa], g.cell_start[row + xb + 1]);
         }
     }
 }

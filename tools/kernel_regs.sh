@@ -18,7 +18,7 @@ for l in sys.stdin:
     for key in ('VGPRs', 'Occupancy \[waves/SIMD\]', 'SGPRs Spill', 'ScratchSize \[bytes/lane\]', 'LDS Size \[bytes/block\]'):
         m = re.search(key + r': (\d+)', l)
         if m and name: d[key] = m.group(1)
-    if name and 'LDS Size' in l and any(k in name for k in ('$ALSO', 'k_nn_red', 'k_nn_deferred', 'k_ref_nn', 'k_ref_fused', 'k_bf', 'k_map_nn', 'k_icp_fused', 'k_nn_cov', 'k_cov_solve', 'k_normals', 'k_patch_old', 'k_map_knn', 'k_normals_knn', 'k_knn_mean_dist', 'k_tree_sum', 'k_flag_mean_dist', 'k_sum_kept', 'k_radius_count', 'k_cluster', 'k_plane', 'k_box', 'k_flag_boxes', 'k_reg_', 'k_iss_', 'k_features_gather', 'k_ndt_')):
+    if name and 'LDS Size' in l and any(k in name for k in ('$ALSO', 'k_nn_red', 'k_nn_deferred', 'k_ref_nn', 'k_ref_fused', 'k_bf', 'k_map_nn', 'k_icp_fused', 'k_nn_cov', 'k_cov_solve', 'k_normals', 'k_patch_old', 'k_map_knn', 'k_normals_knn', 'k_knn_mean_dist', 'k_tree_sum', 'k_flag_mean_dist', 'k_sum_kept', 'k_radius_count', 'k_rad_', 'k_cluster', 'k_plane', 'k_box', 'k_flag_boxes', 'k_reg_', 'k_iss_', 'k_features_gather', 'k_ndt_')):
         short = re.sub(r'^_ZN12_GLOBAL__N_1\d+', '', name)[:$WIDTH]
         print(short, 'vgpr', d.get('VGPRs'), 'occ', d.get('Occupancy \[waves/SIMD\]'), 'sgpr-spill', d.get('SGPRs Spill'), 'scratch', d.get('ScratchSize \[bytes/lane\]'), 'lds', d.get('LDS Size \[bytes/block\]'))
 "
