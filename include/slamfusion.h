@@ -171,7 +171,7 @@ int sf_map_cell_size(sf_map *m, float *cell, int32_t dims[3]);
 #define SF_PATCH_BOUND_REPLACED (-1) /* (not returned any more: a replaced bound costs one reduction over the cloud, then the patch goes on) */
 #define SF_PATCH_ORIGIN_MOVED   (-2) /* a new centroid lies below the grid origin: every cell changes */
 #define SF_PATCH_LIMITS         (-3) /* 2^28 points / 2^32 cells / table memory */
-#define SF_PATCH_CLAMPED_POINT  (-4) /* a point the old grid had clamped to its upper face now lies in a cell of its own */
+#define SF_PATCH_CLAMPED_POINT  (-4) /* a point the old grid had clamped to its upper face now lies in a cell of its own, whether it stays or the merge replaced it */
 int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched);
 /* For a map that is going to grow (sf_map_patch): the grid starts at the multiple of `cells` cells (0 = off, the default: at the
  * smallest coordinates themselves) below the smallest coordinates, so growth by a few metres in any direction -- below the

@@ -352,8 +352,9 @@ extern "C" int sf_map_build(sf_map *m, sf_cloud *cloud, float cell)
 // stay is what it was (ascending id inside a cell, and ids keep their order), and the new index is a MERGE of two sorted
 // sequences: the old entries minus the replaced ones, and the centroids sorted by (cell, id).  One streaming pass over the
 // old entries instead of four sort passes and a random gather; the result is bit-identical to sf_map_build of the merged
-// cloud with the same cell (tests/test_gpu_map_growth.py).  Anything this cannot express -- the smallest coordinate of
-// the map changed, a point that sat clamped at the old upper face, 64-bit cell ids -- takes the build.
+// cloud with the same cell (tests/test_gpu_map_growth.py against a rebuild, tests/test_gpu_growth_direct.py against numpy).  Anything
+// this cannot express -- the smallest coordinate of the map changed, a point that sat clamped at the old upper face (one that stays
+// or one the merge replaced), 64-bit cell ids -- takes the build.
 namespace {
 
 struct PatchGeom { float org[3]; float inv_h; int dim[3]; int old_dim[3]; };
@@ -381,7 +382,13 @@ __global__ void k_patch_groups(PatchGeom geo, const uint32_t *__restrict__ g_ran
     ins_key[g] = patch_key(geo, g_centroid[3 * g], g_centroid[3 * g + 1], g_centroid[3 * g + 2], nullptr);
     ins_val[g] = (uint32_t)g;
     if (!g_fresh[g]) { // the old point of this voxel: where it lies in the index (entries ascend in (cell, id))
-        const uint32_t r = g_rank[g], key = patch_key(geo, g_old[3 * g], g_old[3 * g + 1], g_old[3 * g + 2], nullptr);
+        bool moved;
+        const uint32_t r = g_rank[g], key = patch_key(geo, g_old[3 * g], g_old[3 * g + 1], g_old[3 * g + 2], &moved);
+        // a replaced point that the old grid had clamped to its upper face: the index has it in its old cell, in front of the later
+        // entries of that cell, while its key under the new grid is larger than theirs -- the old entries do not ascend across it, and
+        // the searches over them (here, k_patch_ranges, k_patch_new) go astray whenever they probe it.  The build decides, as for a
+        // clamped point that stays (k_patch_old); the entry is still looked for, so that the bitmap is whole when it is found
+        if (moved) ext->moved = 1u;
         int64_t lo = 0, hi = n_old;
         while (lo < hi) {
             const int64_t mid = (lo + hi) >> 1;

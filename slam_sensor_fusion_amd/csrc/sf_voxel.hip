@@ -271,7 +271,10 @@ int download_i32(sf_cloud *c, const sf::DevBuf &buf, int64_t have, int32_t *dst,
 // the keys are strictly ascending (a centroid that rounding has pushed across a voxel face breaks that: rare -> full path),
 // sort only the pending points, find each of their voxels among the old keys by binary search, sum old point first and
 // then the pending ones in ascending id (the oracle's float32 order), and copy the map once, opening the gaps for the
-// new voxels.  The result is bit-identical to the full path (tests/test_gpu_map_growth.py, test_gpu_config4_stream.py).
+// new voxels.  The result is bit-identical to the plain filter of the concatenation: tests/test_gpu_growth_direct.py holds it against
+// numpy (tests/growth_ref_np.py) at the edges of these kernels -- the 64-wide coarse table, the wave boundary of k_merge_old_keys, the
+// face-crossing centroid, every fall-back by name --, tests/test_gpu_map_growth.py and test_gpu_config4_stream.py against the oracle
+// at workload sizes.
 namespace {
 
 __device__ __forceinline__ uint32_t pcl_key_u32(const PclGeom &g, float x, float y, float z)
