@@ -1,6 +1,7 @@
 // sf_cov.hpp -- pose covariance and degeneracy of a finished alignment (sf_icp_set_covariance, include/slamfusion.h).
 // Included by sf_icp.hip inside its anonymous namespace, after every other kernel, so that none of them changes: it uses
-// that file's IcpState, query_in, robust_weight, wave_reduce_16, reduce_partials and rsqrt_nr as they are.
+// that file's IcpState, query_in and robust_weight, sf_reduce.hpp's wave_reduce_16 and reduce_partials and sf_jacobi.hpp's rsqrt_nr
+// and jacobi_sym as they are.  The first three are ICP's own, which is why this stays a fragment of that unit.
 //
 // Two launches behind the last iteration of an alignment, on its stream:
 //   k_nn_cov<MODE, WINDOW>  one lane per source point: s = T x (float64) at the FINAL pose read from IcpState, the exact

@@ -31,7 +31,6 @@
 #include "sf_order.hpp"
 #include "sf_p2p.hpp"
 #include "sf_schedule.hpp"
-#include "sf_sort.hpp"
 
 #include <cfloat>
 #include <cstdlib>
@@ -43,10 +42,12 @@
 
 namespace {
 
-constexpr int BLK = 256;
+// the float64 numerical core, shared with sf_ndt.hip: the one-lane solves, then the fixed-order reductions with BLK, REC_STRIDE and RBLK
+#include "sf_linalg.hpp"
+#include "sf_reduce.hpp"
+
 constexpr int NREC_P2P = 17;
 constexpr int NREC_PLANE = 30;
-constexpr int REC_STRIDE = 32; // doubles per scan in the exchange buffer
 
 struct IcpState {
     double T[16];
@@ -71,370 +72,6 @@ struct IcpParams {
 };
 
 inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)sf::div_up(n > 0 ? n : 1, b); }
-
-// ------------------------------------------------------------------ small device linear algebra (one lane)
-// Every loop below has compile-time bounds and is fully unrolled so the little matrices
-// live in registers (runtime-indexed arrays would go to scratch memory).
-__device__ __forceinline__ void mat4_mul(const double A[16], const double B[16], double C[16])
-{
-    double R[16];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            R[4 * r + c] = A[4 * r] * B[c] + A[4 * r + 1] * B[4 + c] + A[4 * r + 2] * B[8 + c] + A[4 * r + 3] * B[12 + c];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) C[i] = R[i];
-}
-
-// rsqrt_nr (and the symmetric Jacobi of k_cov_solve, sf_cov.hpp): shared with sf_map.hip
-#include "sf_jacobi.hpp"
-
-// One Hestenes rotation of columns P, Q (the smaller angle): with al = |u_P|^2, be = |u_Q|^2, ga = u_P . u_Q,
-// cos 2t = |be - al| / w, sin 2t = 2 ga sgn(be - al) / w, w = sqrt((be - al)^2 + 4 ga^2); c = sqrt((1 + cos 2t) / 2),
-// s = sin 2t / (2 c) -- two reciprocal square roots, no divide.
-template <int P, int Q>
-__device__ __forceinline__ bool jacobi_pair(double (&u)[9], double (&v)[9])
-{
-    double al = 0, be = 0, ga = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        al += u[3 * i + P] * u[3 * i + P];
-        be += u[3 * i + Q] * u[3 * i + Q];
-        ga += u[3 * i + P] * u[3 * i + Q];
-    }
-    if (ga * ga <= (DBL_EPSILON * DBL_EPSILON) * (al * be) || fabs(ga) < 1e-150) return false;
-    const double tau = be - al;
-    const double r = rsqrt_nr(tau * tau + 4.0 * ga * ga);
-    const double c2 = 0.5 + 0.5 * fabs(tau) * r;
-    const double rc = rsqrt_nr(c2);
-    const double c = c2 * rc, s = (tau >= 0 ? ga : -ga) * r * rc;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double a = u[3 * i + P], b = u[3 * i + Q];
-        u[3 * i + P] = c * a - s * b;
-        u[3 * i + Q] = s * a + c * b;
-        a = v[3 * i + P]; b = v[3 * i + Q];
-        v[3 * i + P] = c * a - s * b;
-        v[3 * i + Q] = s * a + c * b;
-    }
-    return true;
-}
-
-template <int A, int B>
-__device__ __forceinline__ void swap_cols_if_less(double (&s)[3], double (&u)[9], double (&v)[9], double (&inv)[3])
-{
-    if (s[B] > s[A]) {
-        double t = s[A]; s[A] = s[B]; s[B] = t;
-        t = inv[A]; inv[A] = inv[B]; inv[B] = t;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            t = u[3 * i + A]; u[3 * i + A] = u[3 * i + B]; u[3 * i + B] = t;
-            t = v[3 * i + A]; v[3 * i + A] = v[3 * i + B]; v[3 * i + B] = t;
-        }
-    }
-}
-
-// one-sided Jacobi SVD of a 3x3 (row-major), S descending — stands in for
-// Eigen::JacobiSVD<Matrix3f> at icp_point_to_point.cpp:137 (float64 here).
-// Domain: |A| = 0 or 1e-60 <= |A| <= 1e60 (tests/test_gpu_linalg_direct.py::test_svd3_supported_scale_range).  jacobi_pair
-// works on SQUARED column norms: below |A| ~ 1e-67 its |ga| < 1e-150 guard ends the sweeps before the columns are orthogonal
-// to eps (from 1e-75 down nothing rotates: V = I, S = the column norms, and n2 > 1e-300 zeroes S below 1e-150); above
-// |A| ~ 1e77 the product al * be overflows, inf <= inf skips every rotation and the result is finite and WRONG.  H of a Kabsch
-// step is a sum of products of metres and never comes near either end.  Columns whose singular value is below 8 eps S0 are
-// completed, not normalised: rank 0 gives U = I, rank 1 a unit vector orthogonal to the first column and then the cross
-// product, rank 2 the cross product -- U is orthonormal with det +1 whenever the rank is below 3.
-__device__ __forceinline__ void svd3(const double (&A)[9], double (&U)[9], double (&S)[3], double (&V)[9])
-{
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { U[i] = A[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        bool rotated = jacobi_pair<0, 1>(U, V);
-        rotated = jacobi_pair<0, 2>(U, V) || rotated;
-        rotated = jacobi_pair<1, 2>(U, V) || rotated;
-        if (!rotated) break;
-    }
-    double invS[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double n2 = U[j] * U[j] + U[3 + j] * U[3 + j] + U[6 + j] * U[6 + j];
-        invS[j] = n2 > 1e-300 ? rsqrt_nr(n2) : 0.0;
-        S[j] = n2 * invS[j];
-    }
-    swap_cols_if_less<0, 1>(S, U, V, invS);
-    swap_cols_if_less<0, 2>(S, U, V, invS);
-    swap_cols_if_less<1, 2>(S, U, V, invS);
-    const double thr = S[0] * DBL_EPSILON * 8;
-    int rank = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        if (S[j] > thr && S[j] > 0) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) U[3 * i + j] *= invS[j];
-            ++rank;
-        }
-    if (rank == 0) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) U[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    }
-    if (rank == 1) {
-        const double a0 = U[0], a1 = U[3], a2 = U[6];
-        double b0, b1, b2;
-        if (fabs(a0) <= fabs(a1) && fabs(a0) <= fabs(a2)) { b0 = 0; b1 = -a2; b2 = a1; }
-        else if (fabs(a1) <= fabs(a2)) { b0 = -a2; b1 = 0; b2 = a0; }
-        else { b0 = -a1; b1 = a0; b2 = 0; }
-        const double nb = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
-        U[1] = b0 / nb; U[4] = b1 / nb; U[7] = b2 / nb;
-        rank = 2;
-    }
-    if (rank == 2) {
-        U[2] = U[3] * U[7] - U[6] * U[4];
-        U[5] = U[6] * U[1] - U[0] * U[7];
-        U[8] = U[0] * U[4] - U[3] * U[1];
-    }
-}
-
-// Kabsch step (icp_point_to_point.cpp:112-159) from the uncentred sums of the record:
-// rec[0]=n, [1..3]=sum s, [4..6]=sum t, [7..15]=sum s t^T.  H = sum s t^T - n cs ct^T.
-__device__ __forceinline__ void kabsch_from_record(const double *rec, double (&T)[16])
-{
-    const double n = rec[0];
-    double cs[3], ct[3], H[9];
-    const double inv_n = 1.0 / n;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) { cs[d] = rec[1 + d] * inv_n; ct[d] = rec[4 + d] * inv_n; }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) H[3 * r + c] = rec[7 + 3 * r + c] - n * cs[r] * ct[c];
-    double U[9], S[3], V[9], R[9];
-    svd3(H, U, S, V);
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                R[3 * r + c] = V[3 * r] * U[3 * c] + V[3 * r + 1] * U[3 * c + 1] + V[3 * r + 2] * U[3 * c + 2];
-        const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
-        if (pass == 1 || !(det < 0)) break;
-        V[2] = -V[2]; V[5] = -V[5]; V[8] = -V[8];
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) T[i] = 0;
-    T[15] = 1;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) T[4 * r + c] = R[3 * r + c];
-        T[4 * r + 3] = ct[r] - (R[3 * r] * cs[0] + R[3 * r + 1] * cs[1] + R[3 * r + 2] * cs[2]);
-    }
-}
-
-__device__ __forceinline__ int ldlt6(const double (&A)[36], const double (&b)[6], double (&x)[6])
-{
-    double L[36], D[6], y[6];
-    bool bad = false;
-#pragma unroll
-    for (int i = 0; i < 36; ++i) L[i] = 0;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = A[6 * j + j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) d -= L[6 * j + k] * L[6 * j + k] * D[k];
-        if (!(fabs(d) > 0) || !isfinite(d)) bad = true;
-        D[j] = d;
-        L[6 * j + j] = 1;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[6 * i + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[6 * i + k] * L[6 * j + k] * D[k];
-            L[6 * i + j] = v / d;
-        }
-    }
-    if (bad) return -1;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[6 * i + k] * y[k];
-        y[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] /= D[i];
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v -= L[6 * k + i] * x[k];
-        x[i] = v;
-    }
-    return 0;
-}
-
-// R = Rz(v2) Ry(v1) Rx(v0), t = v[3:6] (Open3D TransformVector6dToMatrix4d)
-__device__ __forceinline__ void vec6_to_mat4(const double (&v)[6], double (&T)[16])
-{
-    double ca, sa, cb, sb, cg, sg; // one range reduction per angle
-    sincos(v[0], &sa, &ca);
-    sincos(v[1], &sb, &cb);
-    sincos(v[2], &sg, &cg);
-    const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                         sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                         -sb, cb * sa, cb * ca};
-#pragma unroll
-    for (int i = 0; i < 16; ++i) T[i] = 0;
-    T[15] = 1;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) T[4 * r + c] = R[3 * r + c];
-        T[4 * r + 3] = v[3 + r];
-    }
-}
-
-// ------------------------------------------------------------------ reductions
-// Wave-level sum of 32 doubles per lane in ~125 VALU instructions and no LDS traffic
-// (a plain xor-shuffle reduction of 30 doubles costs 360 ds_bpermute + 180 adds per wave and
-// dominated the kernel's instruction issue — profiles/).  Transposing butterfly: at every
-// step each lane keeps HALF of its values and adds its partner's copy of that half, so the
-// number of live values halves while the number of lanes summed doubles:
-//   32 -> 16  partner l ^ 32   v_permlane32_swap   (gfx950)
-//   16 ->  8  partner l ^ 16   v_permlane16_swap   (gfx950)
-//    8 ->  4  partner l ^ 8    DPP row_ror:8
-//    4 ->  2  partner 7-(l&7)  DPP row_half_mirror
-//    2 ->  1  partner l ^ 2    DPP quad_perm [2,3,0,1]
-//    final    partner l ^ 1    DPP quad_perm [1,0,3,2]
-// Afterwards lane l holds the 64-lane total of component (l >> 1).  Fixed order => bitwise
-// reproducible.
-__device__ __forceinline__ double swap_add_32(double a, double b)
-{
-    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
-}
-
-__device__ __forceinline__ double swap_add_16(double a, double b)
-{
-    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
-}
-
-template <int DPP_CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)__double2loint(v), DPP_CTRL, 0xf, 0xf, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)__double2hiint(v), DPP_CTRL, 0xf, 0xf, false);
-    return __hiloint2double((int)hi, (int)lo);
-}
-
-template <int DPP_CTRL>
-__device__ __forceinline__ double dpp_keep_add(double a, double b, bool upper)
-{
-    const double keep = upper ? b : a, give = upper ? a : b;
-    return keep + dpp_f64<DPP_CTRL>(give);
-}
-
-__device__ __forceinline__ double wave_reduce_32(double (&v)[32])
-{
-    const int lane = threadIdx.x & 63;
-    double w16[16], w8[8], w4[4], w2[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) w16[i] = swap_add_32(v[i], v[i + 16]);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w8[i] = swap_add_16(w16[i], w16[i + 8]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w4[i] = dpp_keep_add<0x128>(w8[i], w8[i + 4], (lane & 8) != 0);   // row_ror:8
-#pragma unroll
-    for (int i = 0; i < 2; ++i) w2[i] = dpp_keep_add<0x141>(w4[i], w4[i + 2], (lane & 4) != 0);   // row_half_mirror
-    const double w1 = dpp_keep_add<0x4e>(w2[0], w2[1], (lane & 2) != 0);                          // quad_perm [2,3,0,1]
-    return w1 + dpp_f64<0xb1>(w1);                                                                // quad_perm [1,0,3,2]
-}
-
-// 16-value form of the same butterfly (half the live registers): afterwards lane l holds the
-// 64-lane total of component (l >> 2) & 15.
-__device__ __forceinline__ double wave_reduce_16(double (&v)[16])
-{
-    const int lane = threadIdx.x & 63;
-    double w8[8], w4[4], w2[2];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w8[i] = swap_add_32(v[i], v[i + 8]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w4[i] = swap_add_16(w8[i], w8[i + 4]);
-#pragma unroll
-    for (int i = 0; i < 2; ++i) w2[i] = dpp_keep_add<0x128>(w4[i], w4[i + 2], (lane & 8) != 0);   // row_ror:8
-    double z = dpp_keep_add<0x141>(w2[0], w2[1], (lane & 4) != 0);                                // row_half_mirror
-    z = z + dpp_f64<0x4e>(z);                                                                     // quad_perm [2,3,0,1]
-    return z + dpp_f64<0xb1>(z);                                                                  // quad_perm [1,0,3,2]
-}
-
-// every lane gets the 64-lane total of one value
-__device__ __forceinline__ double wave_reduce_1(double v)
-{
-    v = swap_add_32(v, v);
-    v = swap_add_16(v, v);
-    v = v + dpp_f64<0x128>(v);
-    v = v + dpp_f64<0x141>(v);
-    v = v + dpp_f64<0x4e>(v);
-    return v + dpp_f64<0xb1>(v);
-}
-
-// Slab layout: partials[(scan * nblocks + block) * 32 + component] — a workgroup's record
-// is one contiguous 256-byte row, so both the store here and the column sums below are
-// coalesced.
-template <int NREC>
-__device__ __forceinline__ void block_reduce_store(double (&acc)[NREC], double *__restrict__ dst)
-{
-    double v[32];
-#pragma unroll
-    for (int c = 0; c < 32; ++c) v[c] = c < NREC ? acc[c] : 0.0;
-    const double total = wave_reduce_32(v);
-    __shared__ double s[BLK / 64][32];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if ((lane & 1) == 0) s[w][lane >> 1] = total;
-    __syncthreads();
-    if (threadIdx.x < NREC) {
-        const int c = threadIdx.x;
-        dst[c] = ((s[0][c] + s[1][c]) + s[2][c]) + s[3][c];
-    }
-}
-
-// Fixed-order sum of one scan's slab by RBLK = 1024 threads: thread (slice s, component c)
-// adds rows s, s+32, s+64, ... then the 32 slices are added in order.  Result in rec[]
-// (shared).  Deterministic: no atomics, the order depends only on nblocks.
-constexpr int RBLK = 1024;
-// NT = threads of the calling workgroup (a multiple of 32, at most 1024): with fewer than 1024 a thread takes several
-// slices one after the other -- every (slice, component) sum is the same expression, so the result is bit-identical
-// for every NT.
-template <int NREC, int NT = RBLK>
-__device__ __forceinline__ void reduce_partials(const double *__restrict__ part, int nblocks, double *rec)
-{
-    __shared__ double sl[32][REC_STRIDE + 1];
-    const int c = threadIdx.x & 31;
-    for (int sidx = threadIdx.x >> 5; sidx < 32; sidx += NT / 32) {
-        double v0 = 0, v1 = 0, v2 = 0, v3 = 0;
-        if (c < NREC) {
-            int b = sidx;
-            for (; b + 96 < nblocks; b += 128) {
-                const double a0 = part[(size_t)b * REC_STRIDE + c], a1 = part[(size_t)(b + 32) * REC_STRIDE + c];
-                const double a2 = part[(size_t)(b + 64) * REC_STRIDE + c], a3 = part[(size_t)(b + 96) * REC_STRIDE + c];
-                v0 += a0; v1 += a1; v2 += a2; v3 += a3;
-            }
-            for (; b < nblocks; b += 32) v0 += part[(size_t)b * REC_STRIDE + c];
-        }
-        sl[sidx][c] = (v0 + v1) + (v2 + v3);
-    }
-    __syncthreads();
-    if (threadIdx.x < REC_STRIDE) {
-        double v = 0;
-#pragma unroll
-        for (int k = 0; k < 32; ++k) v += sl[k][threadIdx.x];
-        rec[threadIdx.x] = threadIdx.x < NREC ? v : 0.0;
-    }
-    __syncthreads();
-}
 
 // ------------------------------------------------------------------ helper kernels
 // source points as SoA (coalesced lane loads of the kernels) and as float4 records (ONE 16-byte access
@@ -3095,7 +2732,6 @@ __global__ __launch_bounds__(BLK) void k_icp_fused_rob(SfGrid g, SfWindow w, con
 
 #include "sf_cov.hpp"
 #include "sf_icp_testhooks.hpp"
-#include "sf_ndt.hpp"
 
 } // namespace
 
@@ -4981,6 +4617,3 @@ extern "C" int sf_test_query_order(sf_map *map, const float *points, int batch, 
         for (int a = 0; a < 3; ++a) ordered[3 * i + a] = h_soa[(size_t)a * total + i];
     return SF_OK;
 }
-
-// ==================================================================== NDT (sf_ndt_*)
-#include "sf_ndt_host.hpp"

@@ -1,8 +1,9 @@
 // sf_icp_testhooks.hpp -- test hooks of the float64 numerical core (sf_test_linalg, sf_test_wave_reduce, sf_test_block_reduce,
 // sf_test_reduce_partials; include/slamfusion.h).  Included by sf_icp.hip inside its anonymous namespace,
-// after every other kernel (sf_cov.hpp included), so that none of them changes.  The kernels below CALL that file's
-// rsqrt_nr, svd3, kabsch_from_record, ldlt6, vec6_to_mat4, robust_weight, wave_reduce_*, block_reduce_store and
-// reduce_partials and sf_cov.hpp's jacobi_sym / recip_nr as they are: no copy of a routine, no second implementation.  Not part
+// after every other kernel (sf_cov.hpp included), so that none of them changes.  The kernels below CALL sf_linalg.hpp's svd3,
+// kabsch_from_record, ldlt6 and vec6_to_mat4, sf_reduce.hpp's wave_reduce_*, block_reduce_store and reduce_partials, sf_jacobi.hpp's
+// rsqrt_nr / jacobi_sym, sf_cov.hpp's recip_nr and that file's robust_weight as they are: no copy of a routine, no second implementation.  They
+// stay in the ICP unit because robust_weight and the instantiations they pin (NREC_COV_*, SBLK) are ICP's.  Not part
 // of the drop-in boundary and no reference counterpart (the reference calls Eigen::JacobiSVD and Open3D's solvers).
 //
 // sf_test_linalg runs one case per thread in workgroups of 64: one lane working on its own little matrix is how production

@@ -1,6 +1,7 @@
 // sf_jacobi.hpp -- rsqrt_nr and the symmetric Jacobi eigen-solve, N x N in registers.  Included inside the anonymous namespace of
-// the translation units that use them: sf_icp.hip (svd3, k_cov_solve of sf_cov.hpp, the hooks of sf_icp_testhooks.hpp) and
-// sf_map.hip (the per-label boxes of sf_box.hpp).  One implementation; tests/test_gpu_linalg_direct.py pins it through sf_icp.hip.
+// the translation units that use them: through sf_linalg.hpp (svd3) sf_icp.hip (also k_cov_solve of sf_cov.hpp and the hooks of
+// sf_icp_testhooks.hpp) and sf_ndt.hip (the voxel and Newton-step solves); directly sf_map.hip (the per-label boxes of sf_box.hpp),
+// sf_register.hip and sf_keypoint.hip.  One implementation; tests/test_gpu_linalg_direct.py pins it through sf_icp.hip.
 #pragma once
 #include <cfloat>
 

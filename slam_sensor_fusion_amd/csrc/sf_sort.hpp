@@ -89,7 +89,8 @@ __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *sh
 }
 
 // one workgroup per digit: hist[d][0..ntiles) -> exclusive prefix over the tiles, totals[d] = the row's sum
-static __global__ __launch_bounds__(SORT_BLK) void k_sort_scan(uint32_t *__restrict__ hist, int ntiles, uint32_t *__restrict__ totals)
+// (static: no template, so every unit has its own; unused: a unit that takes the scans alone never instantiates the sort that launches it)
+__attribute__((unused)) static __global__ __launch_bounds__(SORT_BLK) void k_sort_scan(uint32_t *__restrict__ hist, int ntiles, uint32_t *__restrict__ totals)
 {
     __shared__ uint32_t sh[SORT_WAVES];
     uint32_t *row = hist + (size_t)blockIdx.x * (size_t)ntiles;

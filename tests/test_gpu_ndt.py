@@ -1,4 +1,4 @@
-"""NDT registration on the device (sf_ndt_*, csrc/sf_ndt.hpp) against the numpy restatement tests/ndt_ref_np.py, whose docstring derives
+"""NDT registration on the device (sf_ndt_*, csrc/sf_ndt.hip) against the numpy restatement tests/ndt_ref_np.py, whose docstring derives
 every bound used here.  The voxel build is compared with the restatement's own voxels.  The derivative and one-step comparisons hand
 the restatement the device's downloaded voxels (mean and B, float64, the very bits the kernel reads), so that their bounds count the
 roundings of the derivative kernel and of the step alone; whole alignments are compared with the restatement run on its own voxels."""

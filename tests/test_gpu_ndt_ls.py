@@ -1,5 +1,5 @@
 """The NDT line search, the score pass and the coarse-to-fine levels on the device (sf_ndt_set_line_search, sf_ndt_scores,
-sf_ndt_line_search_read, sf_ndt_align_levels; csrc/sf_ndt.hpp) against the numpy restatement tests/ndt_ls_ref_np.py, on the fixtures whose
+sf_ndt_line_search_read, sf_ndt_align_levels; csrc/sf_ndt.hip) against the numpy restatement tests/ndt_ls_ref_np.py, on the fixtures whose
 conditions tests/test_ndt_ls_rule.py holds.  As in tests/test_gpu_ndt.py the per-row comparisons hand the restatement the device's
 downloaded voxels; whole alignments are compared with the restatement run on its own voxels."""
 import ctypes

@@ -158,18 +158,36 @@ def test_the_header_of_the_schedule_is_plain_host_code():
     assert re.findall(r'#include\s+[<"]([^>"]+)', code) == ["slamfusion.h"]
 
 
-def test_the_source_hash_reads_what_the_compiler_read(api):
-    """kernel_source_hash follows the #include "..." lines from sf_icp.hip; the dependency file the compiler wrote for that
-    translation unit (csrc/Makefile, -MMD) names what it opened.  The two sets of csrc files must be the same."""
+def _compiled_from(unit):
+    """the files of csrc/ that the dependency file of a translation unit (csrc/Makefile, -MMD) names: what the compiler opened"""
     csrc = os.path.join(ROOT, "slam_sensor_fusion_amd", "csrc")
-    dep = os.path.join(ROOT, "slam_sensor_fusion_amd", "lib", "obj", "sf_icp.hip.d")
+    dep = os.path.join(ROOT, "slam_sensor_fusion_amd", "lib", "obj", unit + ".d")
     if not os.path.isfile(dep):
         pytest.skip("no dependency file: the library was not built by csrc/Makefile here")
     with open(dep) as f:
         words = f.read().replace("\\\n", " ").split()
-    named = {os.path.basename(w) for w in words if not w.endswith(":") and os.path.realpath(os.path.join(csrc, os.path.dirname(w))) == os.path.realpath(csrc)}
+    return {os.path.basename(w) for w in words if not w.endswith(":") and os.path.realpath(os.path.join(csrc, os.path.dirname(w))) == os.path.realpath(csrc)}
+
+
+def test_the_source_hash_reads_what_the_compiler_read(api):
+    """kernel_source_hash follows the #include "..." lines from sf_icp.hip; the dependency file the compiler wrote for that
+    translation unit names what it opened.  The two sets of csrc files must be the same."""
+    named = _compiled_from("sf_icp.hip")
     assert named == set(api.kernel_sources()), sorted(named ^ set(api.kernel_sources()))
     assert "sf_icp.hip" in named and len(api.kernel_source_hash()) == 16
+
+
+def test_the_source_hash_takes_the_numerical_core_and_no_ndt(api):
+    """The dominant kernel is compiled from the core headers; NDT is a translation unit of its own and no longer moves the hash."""
+    names = api.kernel_sources()
+    assert {"sf_linalg.hpp", "sf_reduce.hpp", "sf_jacobi.hpp"} <= set(names), names
+    assert not [n for n in names if n.startswith("sf_ndt")], names
+
+
+def test_ndt_is_compiled_from_the_core_and_nothing_of_icp():
+    named = _compiled_from("sf_ndt.hip")
+    assert {"sf_ndt.hip", "sf_linalg.hpp", "sf_reduce.hpp", "sf_jacobi.hpp", "sf_sort.hpp", "sf_common.hpp"} <= named, sorted(named)
+    assert not named & {"sf_icp.hip", "sf_nn.hpp", "sf_cov.hpp", "sf_schedule.hpp", "sf_icp_object.hpp"}, sorted(named)
 
 
 def test_the_wrappers_keep_their_shape(api):

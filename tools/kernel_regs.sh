@@ -6,7 +6,8 @@ SRC="${SF_REGS_SRC:-sf_icp.hip}"
 WIDTH=34; [ -n "$SF_REGS_SRC" ] && WIDTH=40   # (the default report stays as it was)
 # SF_REGS_SRC=sf_register.hip tools/kernel_regs.sh: the pose-from-matches kernels (k_reg_*)
 # SF_REGS_SRC=sf_keypoint.hip tools/kernel_regs.sh: the ISS keypoint kernels (k_iss_*) and k_features_gather
-# SF_REGS_SRC=sf_icp.hip tools/kernel_regs.sh: the default report with the query-ordering kernels (k_order_*) in their place; the NDT kernels (k_ndt_*) are in both
+# SF_REGS_SRC=sf_ndt.hip tools/kernel_regs.sh: the NDT kernels (k_ndt_*), a translation unit of their own: in no other report
+# SF_REGS_SRC=sf_icp.hip tools/kernel_regs.sh: the default report with the query-ordering kernels (k_order_*) in their place
 ALSO=k_nn_red; [ "$SF_REGS_SRC" == sf_icp.hip ] && ALSO=k_order
 /opt/rocm/bin/hipcc "$@" -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -I../../include -I. -Rpass-analysis=kernel-resource-usage -c "$SRC" -o /tmp/kernel_regs.o 2>&1 |
   python3 -c "
