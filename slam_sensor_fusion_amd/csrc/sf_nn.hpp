@@ -9,7 +9,8 @@
 //
 // Layout: the map is sorted by cell (x fastest), so a row of cells is one contiguous candidate
 // range, and ONE 16-byte look-up returns the bounds of the three cells of a row.  The query's own
-// cell is scanned first; its x neighbours and the 8 neighbouring rows only while their gap to the
+// cell is scanned first (nn_search_wave: with the slots it leaves idle filled from its x neighbours,
+// first_window); its x neighbours and the 8 neighbouring rows only while their gap to the
 // query is smaller than the best distance so far.
 // What was measured on MI355X and shaped this file (profiles/): a branch per
 // candidate load serialises the loads into one round trip each; clamped duplicate loads keep them
@@ -391,7 +392,7 @@ __device__ __forceinline__ NNHit nn_search(const SfGrid &g, const SfWindow &w, f
 // 64 lanes active in each -- in total fewer than 64 lane-steps of real work.  Here the surviving
 // (query, range) TASKS of the whole wave go into an LDS queue and are dealt out one per lane, so
 // that work takes one or two full steps.  A task scans one contiguous candidate range:
-//   t = 0, 1   the left / right x neighbour of the own cell
+//   t = 0, 1   the left / right x neighbour of the own cell, less what the first trip's window took of it (first_window)
 //   t = 2 + k  neighbouring row k (own-x cell plus the x neighbours whose gap is still below the best)
 //   t = 10     what is left of an own cell that holds more than four points
 // and lowers its owner's packed (d2, j) in LDS with ds_min_u64.  The result is the lexicographic
@@ -445,6 +446,65 @@ __device__ __forceinline__ QueryGeo query_geo(const SfGrid &g, float qx, float q
     G.gzm = safe_gap(fz * h, ge);
     G.gzp = safe_gap((1.0f - fz) * h, ge);
     return G;
+}
+
+// The first trip of nn_search_wave: a window [lo, hi) of at most NN_ROW_CAP consecutive CSR positions of the query's own
+// row, inside [rb.s0, rb.s3).  The own cell comes first; at 1.5 points per cell it seldom fills the trip's slots, and the x
+// neighbours lie contiguous with it in the CSR, described by the row bounds the lane already holds -- so the slots the own
+// cell leaves idle go to the neighbour whose face is nearer (the first positions of the right cell, the last of the left
+// one), and what that side cannot supply to the other.  A side without a neighbour in the grid (gap 3e38) gets none: what
+// lies there in memory is another row's.  round_task re-derives the same window from the same three values.
+// SF_NN_ROW_WINDOW: 0 the own cell only, 1 nearer side first (shipped), 2 right then left, 3 the whole own row, up to 8
+// positions in two trips (profiles/row_window_ab.txt)
+#ifndef SF_NN_ROW_WINDOW
+#define SF_NN_ROW_WINDOW 1
+#endif
+#ifndef SF_NN_ROW_GATE
+#define SF_NN_ROW_GATE 0 // slot_row below: measured, off (every neighbour the grid has may fill idle slots; LADDER round 12)
+#endif
+constexpr uint32_t NN_ROW_CAP = SF_NN_ROW_WINDOW == 3 ? 8u : 4u;
+struct RowWindow { uint32_t lo, hi; };
+__device__ __forceinline__ RowWindow first_window(const RowBounds &rb, float gxm2, float gxp2)
+{
+    const uint32_t own = min(rb.s2 - rb.s1, NN_ROW_CAP);
+    RowWindow W;
+#if SF_NN_ROW_WINDOW == 0
+    W.lo = rb.s1; W.hi = rb.s1 + own;
+#else
+    const uint32_t idle = NN_ROW_CAP - own;
+    const uint32_t nl = gxm2 < 1.0e38f ? rb.s1 - rb.s0 : 0u, nr = gxp2 < 1.0e38f ? rb.s3 - rb.s2 : 0u;
+    const bool right_first = SF_NN_ROW_WINDOW == 2 || gxp2 <= gxm2;
+    const uint32_t t1 = min(idle, right_first ? nr : nl);
+    const uint32_t t2 = min(idle - t1, right_first ? nl : nr);
+    W.lo = rb.s1 - (right_first ? t2 : t1);
+    W.hi = rb.s1 + own + (right_first ? t1 : t2); // (own < NN_ROW_CAP, or nothing is added: past rb.s2 only with the whole own cell inside)
+#endif
+    return W;
+}
+
+// The row the window is laid over (SF_NN_ROW_GATE; off, the row is the one loaded: the switch bought the second launch
+// nothing and the third came out 13 us longer, profiles/row_window_ab.txt).  On: a neighbour whose gap does not pass the
+// bound the search STARTS from (the acceptance threshold, or the seed's distance: small from the second launch of an
+// alignment on) can never be queued -- the best only
+// falls -- so it gets no slot either: a slot there is a lane access for nothing.  Its cell is cut off the row (s0 = s1,
+// s3 = s2); the copy goes to WaveNN::rb0, so that round_task lays the same window (task 0 / 1 of a side that was cut off does
+// not exist), while the mask of nn_search_wave still sees the cell in the bounds as loaded and gives its gap to the
+// runner-up bound.
+__device__ __forceinline__ RowBounds slot_row(RowBounds rb, float gxm2, float gxp2, float start)
+{
+#if SF_NN_ROW_GATE
+    if (!(gxm2 * 0.998f < start)) rb.s0 = rb.s1;
+    if (!(gxp2 * 0.998f < start)) rb.s3 = rb.s2;
+#endif
+    return rb;
+}
+
+// the candidates of a non-empty window: four loads issued together, slots past W.hi dropped (scan4)
+template <bool WINDOW>
+__device__ __forceinline__ void scan_first(const SfGrid &g, const SfWindow &w, const RowWindow &W, float qx, float qy, float qz, NNHit &hit)
+{
+    if constexpr (NN_ROW_CAP == 4u) scan4<WINDOW, true>(g, w, W.lo, W.hi, qx, qy, qz, hit);
+    else scan_range<WINDOW, true>(g, w, W.lo, W.hi, qx, qy, qz, hit);
 }
 
 //   k      0   1   2   3   4   5   6   7
@@ -515,9 +575,10 @@ __device__ __forceinline__ RoundTask round_task(const SfGrid &g, WaveNN *ws, uin
     if (T.live) {
         T.bound = 3.0e38f;
         if (own_row) {
-            const RowBounds rb = ws->rb0[owner];
-            T.a = t == 0 ? rb.s0 : (t == 1 ? rb.s2 : rb.s1 + 4);
-            T.b = t == 0 ? rb.s1 : (t == 1 ? rb.s3 : rb.s2);
+            const RowBounds rb = ws->rb0[owner]; // what the first trip's window left of the own row
+            const RowWindow W = first_window(rb, G.gxm2, G.gxp2);
+            T.a = t == 0 ? rb.s0 : (t == 1 ? max(W.hi, rb.s2) : W.hi);
+            T.b = t == 0 ? W.lo : (t == 1 ? rb.s3 : rb.s2);
         } else {
             const long long step = ((long long)row_dz(t - 2) * ny + row_dy(t - 2)) * nx; // the row's cell relative to the owner's (inside the grid: checked when queued)
             const RowBounds rb = load_row_bounds(g, (size_t)((long long)ws->cell0[owner] + step));
@@ -579,32 +640,39 @@ __device__ __forceinline__ NNHit nn_search_wave(const SfGrid &g, const SfWindow 
 #ifdef SF_PHASE_TRACE
     QueryGeo G{};
     RowBounds rb0{0, 0, 0, 0};
+    RowWindow W{0, 0};
     if (valid) {
         G = query_geo(g, qx, qy, qz);
         rb0 = load_row_bounds(g, ((size_t)G.cz * ny + G.cy) * nx + G.cx);
-        ws->rb0[lane] = rb0;
+        const RowBounds rbw = slot_row(rb0, G.gxm2, G.gxp2, hit.d2);
+        ws->rb0[lane] = rbw;
+        W = first_window(rbw, G.gxm2, G.gxp2);
     }
     SF_PH(pc, 1);
-    if (valid && rb0.s1 < rb0.s2) scan4<WINDOW, true>(g, w, rb0.s1, rb0.s2, qx, qy, qz, hit);
+    if (valid && W.lo < W.hi) scan_first<WINDOW>(g, w, W, qx, qy, qz, hit);
+    { unsigned c = W.hi - W.lo; for (int o = 32; o > 0; o >>= 1) c += (unsigned)__shfl_xor((int)c, o); SF_PHC(pc, 15, c); } // live slots of the first trip
     SF_PH(pc, 2);
     if (valid) {
 #else
     if (valid) {
         const QueryGeo G = query_geo(g, qx, qy, qz);
         const RowBounds rb0 = load_row_bounds(g, ((size_t)G.cz * ny + G.cy) * nx + G.cx);
-        ws->rb0[lane] = rb0;
-        if (rb0.s1 < rb0.s2) scan4<WINDOW, true>(g, w, rb0.s1, rb0.s2, qx, qy, qz, hit);
+        const RowBounds rbw = slot_row(rb0, G.gxm2, G.gxp2, hit.d2);
+        ws->rb0[lane] = rbw;
+        const RowWindow W = first_window(rbw, G.gxm2, G.gxp2);
+        if (W.lo < W.hi) scan_first<WINDOW>(g, w, W, qx, qy, qz, hit);
 #endif
-        if (rb0.s1 + 4 < rb0.s2) {
+        if (W.hi < rb0.s2) { // an own cell of more than NN_ROW_CAP points
             if (hit.d2 > 0.0f) mask |= 1u << 10;
             else hit.lb2 = 0.0f; // the rest of the cell is not examined
         }
-        // a range that is not queued because its gap is too large bounds the runner-up by that gap
-        if (rb0.s0 < rb0.s1) {
+        // the x neighbours, less what the window took of them: a range that is not queued because its gap is too large
+        // bounds the runner-up by that gap
+        if (rb0.s0 < W.lo) {
             if (G.gxm2 * 0.998f < hit.d2) mask |= 1u;
             else hit.lb2 = fminf(hit.lb2, G.gxm2);
         }
-        if (rb0.s2 < rb0.s3) {
+        if (max(W.hi, rb0.s2) < rb0.s3) {
             if (G.gxp2 * 0.998f < hit.d2) mask |= 2u;
             else hit.lb2 = fminf(hit.lb2, G.gxp2);
         }

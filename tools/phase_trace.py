@@ -65,4 +65,5 @@ tot = v[:9].sum()
 print("iters %d batch %d reuse %s: %d waves, %.0f ticks per wave" % (args.iters, args.batch, args.reuse, waves, tot / waves))
 for i, nm in enumerate(names):
     print("  %-48s %6.1f %%  %8.0f ticks/wave" % (nm, 100 * v[i] / tot, v[i] / waves))
-print("  per wave: tasks %.1f, rounds %.2f, wave-level trips in rounds %.2f, lane trips %.1f, candidates in tasks %.1f" % (v[11] / waves, v[9] / waves, v[10] / waves, v[12] / waves, v[13] / waves))
+print("  per wave: tasks %.1f, rounds %.2f, wave-level trips in rounds %.2f, lane trips %.1f, candidates in tasks %.1f, live slots of the first trip %.1f" % (
+    v[11] / waves, v[9] / waves, v[10] / waves, v[12] / waves, v[13] / waves, v[15] / waves))
