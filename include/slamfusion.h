@@ -650,6 +650,71 @@ int sf_ndt_set_line_search(sf_ndt *ndt, const sf_ndt_line_search *p);           
 int sf_ndt_scores(sf_ndt *ndt, const double *poses, int64_t k, double *score, int64_t *n_terms);/* entry 0 at poses [k][16], any k */
 int sf_ndt_line_search_read(sf_ndt *ndt, sf_ndt_ls_row *rows, int64_t cap, int64_t *n);         /* entry 0 of the last sf_ndt_align with the search on: one row per evaluated iteration, the stalled one included */
 int sf_ndt_align_levels(sf_ndt *const *levels, int n_levels, const double *inits, sf_ndt_result *out /* [batch] */, sf_ndt_result *per_level /* [n_levels][batch] or NULL */);
+/* Range images and visibility-based removal of stale map points (extension, no reference code; the organised cloud of a LiDAR
+ * driver, Removert's range-image comparison, OctoMap-style free-space carving; DESIGN §28, restated in tests/visibility_ref_np.py).
+ * Everything below is float64, unfused, evaluated left to right as written.
+ * Sensor frame.  With a pose T [16] row-major, parent <- sensor (the form sf_icp returns): d_k = (double)p_k - T[4k+3];
+ *   x = (T[0] d0 + T[4] d1) + T[8] d2, y = (T[1] d0 + T[5] d1) + T[9] d2, z = (T[2] d0 + T[6] d1) + T[10] d2 -- R^T (p - t), no
+ *   inversion.  NULL is the identity through the same expressions: the cloud already is in the sensor frame.  So one call makes an
+ *   organised range image of a scan as received, or renders a map from a pose into the scan one would expect there.
+ * Range and angles.  h2 = x x + y y; r = sqrt(h2 + z z); az = atan2(y, x); el = atan2(z, sqrt(h2)).
+ * Pixel.  PI = the double nearest pi.  u = (az + PI) / (2 PI) * W, col = floor(u), col - W when col >= W (+pi and -pi are one
+ *   column); v = (el - el_min) / (el_max - el_min) * H, row = floor(v), row 0 the lowest elevation.  The point is outside
+ *   (n_outside) when v < 0, when row >= H, or when r > 0 && min_range <= r && r <= max_range is false; a point with a coordinate
+ *   that is not finite counts as n_nonfinite; n_points = n_projected + n_outside + n_nonfinite.
+ * Content.  Each pixel holds the minimum over its points of the key ((uint64)bits((float)r) << 32) | (uint32)i, i the point's index
+ *   in the cloud: the smallest range and on a tie the smallest index, by one 64-bit integer atomicMin per point (a non-negative
+ *   float's bits order like the float; no float atomics), the same bits on every run.  An empty pixel downloads as +inf and -1;
+ *   n_filled = the pixels that are not empty.  device_ms = the device time of the fill and the two kernels of the build.
+ * SF_ERR_INVALID, nothing touched: width outside 1 .. 16384 or height outside 1 .. 4096; bounds that are not finite or el_min >=
+ *   el_max; min_range < 0 or max_range <= min_range; a pose that is not finite; n >= 2^31.  An empty cloud is SF_OK with an empty
+ *   image; a build replaces what the image held; a new image is empty.
+ * Class of a point against one image (pose: map <- sensor of the scan the image was built from).  The point goes through the
+ *   sensor-frame and pixel rule above with the image's parameters; outside, not finite or not indexed: SF_VIS_OUTSIDE.  The window
+ *   is the pixels (row + dr, (col + dc) mod W), |dr| <= half_rows, |dc| <= half_cols, rows outside [0, H) skipped.  n_hit = the
+ *   pixels of the window that are not empty, r_near / r_far the smallest / largest range among them.  n_hit < min_hits:
+ *   SF_VIS_UNKNOWN -- an empty pixel is no evidence, a missing return is never read as free space.  margin = range_margin +
+ *   range_ratio * r.  SF_VIS_SEEN_THROUGH iff r + margin < (double)r_near (every ray near it went past it); else SF_VIS_OCCLUDED
+ *   iff r - margin > (double)r_far; else SF_VIS_WITHIN.  r comes from IEEE operations and a correctly rounded sqrt, so the class
+ *   depends on atan2 only through the two floors.
+ * sf_map_visibility: cls [n] in the ORIGINAL point order.  sf_map_visibility_votes: seen_through[i] / within[i] = the number of the
+ *   n_images images that class point i SEEN_THROUGH / WITHIN, bit for bit the counts summed over n_images single-image calls; the
+ *   map is read once however many images vote.  The class counts of the statistics are sums over the images (a point the index
+ *   does not hold counts as outside once per image), n_points and n_valid are the map's (sf_map_index), n_removed is 0.  poses NULL:
+ *   every pose the identity.  The map's index, normals, covariances and neighbour table are left alone: a caller who wants a
+ *   cleaned map keeps the map's cloud, calls sf_cloud_remove_seen_through on it and then sf_map_build.
+ * sf_cloud_remove_seen_through: classifies the cloud's own points (no index is needed or built; n_valid = the finite points) and
+ *   removes point i iff seen_through[i] >= min_seen && within[i] <= max_within.  Compacts in place like a crop -- the order is
+ *   kept, sf_cloud_last_indices reports the survivors; votes and flags never leave the device; n_removed = the points taken away.
+ * SF_ERR_INVALID, nothing touched: half_cols < 0 or half_rows < 0; 2 half_cols + 1 > W for any image; min_hits outside 1 ..
+ *   (2 half_cols + 1)(2 half_rows + 1); a margin or ratio that is negative or not finite; n_images outside 1 .. 64; a NULL image
+ *   or one of another context; a pose that is not finite; min_seen < 1 or max_within < 0.  A map that is not built is SF_ERR_STATE.
+ *   An empty cloud is SF_OK with zero statistics.  With profile != 0, or with sf_map_profile_launches on for the map forms,
+ *   device_ms = the device time from the first to the last kernel; otherwise -1. */
+typedef struct sf_range_image sf_range_image;
+typedef struct { int32_t width, height; double el_min, el_max, min_range, max_range; } sf_range_image_params;
+typedef struct { int64_t n_points, n_projected, n_outside, n_nonfinite, n_filled; float device_ms; int32_t pad; } sf_range_image_stats;
+void sf_range_image_default_params(sf_range_image_params *p);   /* 2048 x 64, -25 deg .. +3 deg in radians, 0.5 m .. 120 m */
+int sf_range_image_create(sf_ctx *ctx, const sf_range_image_params *p, sf_range_image **out);
+void sf_range_image_destroy(sf_range_image *img);
+int sf_range_image_info(const sf_range_image *img, sf_range_image_params *p);
+int sf_range_image_build(sf_range_image *img, sf_cloud *c, const double *pose /* [16] row-major, parent <- sensor, or NULL */, sf_range_image_stats *stats);
+int sf_range_image_download(sf_range_image *img, float *range /* [H][W] or NULL */, int32_t *index /* [H][W] or NULL */);
+#define SF_VIS_OUTSIDE 0
+#define SF_VIS_UNKNOWN 1
+#define SF_VIS_WITHIN 2
+#define SF_VIS_OCCLUDED 3
+#define SF_VIS_SEEN_THROUGH 4
+typedef struct { int32_t half_cols, half_rows, min_hits, profile; double range_margin, range_ratio; } sf_visibility_params;
+typedef struct { int64_t n_points, n_valid, n_outside, n_unknown, n_within, n_occluded, n_seen_through, n_removed; float device_ms; int32_t pad; } sf_visibility_stats;
+void sf_visibility_default_params(sf_visibility_params *p);   /* 1, 1, 1, 0, 0.2 m, 0.01 */
+int sf_map_visibility(sf_map *m, sf_range_image *img, const double *pose, const sf_visibility_params *p,
+                      uint8_t *cls /* [n], original order, or NULL */, sf_visibility_stats *stats);
+int sf_map_visibility_votes(sf_map *m, sf_range_image *const *imgs, const double *poses /* [B][16] */, int64_t n_images /* 1 .. 64 */,
+                            const sf_visibility_params *p, uint16_t *seen_through /* [n] or NULL */, uint16_t *within /* [n] or NULL */,
+                            sf_visibility_stats *stats);
+int sf_cloud_remove_seen_through(sf_cloud *c, sf_range_image *const *imgs, const double *poses, int64_t n_images,
+                                 const sf_visibility_params *p, int min_seen, int max_within, sf_visibility_stats *stats);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */

@@ -179,6 +179,64 @@ def _box_params(mode, up, profile):
     return p
 
 
+VIS_CLASSES = dict(outside=0, unknown=1, within=2, occluded=3, seen_through=4)  # SF_VIS_*
+
+
+class RangeImageParams(C.Structure):
+    """sf_range_image_params: width x height pixels over the full turn of azimuth and [el_min, el_max) of elevation (radians), and
+    the ranges (metres) a point must lie in to be projected."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("el_min", C.c_double), ("el_max", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_double else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+class RangeImageStats(C.Structure):
+    """sf_range_image_stats: what a build saw (n_points = n_projected + n_outside + n_nonfinite; n_filled: the pixels that are not
+    empty; device_ms: the fill and the two kernels)."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_projected", "n_outside", "n_nonfinite", "n_filled")] + [("device_ms", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_ if name != "pad"}
+
+
+class VisibilityParams(C.Structure):
+    """sf_visibility_params: the window (half_cols, half_rows pixels either side), the non-empty pixels it must hold for a verdict
+    (min_hits), the profile switch, and margin = range_margin + range_ratio * r."""
+    _fields_ = [("half_cols", C.c_int32), ("half_rows", C.c_int32), ("min_hits", C.c_int32), ("profile", C.c_int32), ("range_margin", C.c_double),
+                ("range_ratio", C.c_double)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_double else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+class VisibilityStats(C.Structure):
+    """sf_visibility_stats: the class counts summed over the images, the points and the indexed (map) or finite (cloud) ones, the
+    points a cloud call took away; device_ms: -1 unless profiled."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_valid", "n_outside", "n_unknown", "n_within", "n_occluded", "n_seen_through", "n_removed")] + \
+               [("device_ms", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_ if name != "pad"}
+
+
+def _visibility_params(half_cols, half_rows, min_hits, range_margin, range_ratio, profile):
+    """The keyword form of the visibility calls -> VisibilityParams."""
+    return VisibilityParams(int(half_cols), int(half_rows), int(min_hits), int(bool(profile)), float(range_margin), float(range_ratio))
+
+
+def _images_and_poses(images, poses):
+    """-> (the array of sf_range_image handles, float64 [B, 16] or None, B)"""
+    images = list(images)
+    handles = (C.c_void_p * max(len(images), 1))(*[im.h for im in images])
+    if poses is None:
+        return handles, None, len(images)
+    poses = _f64(poses).reshape(-1, 16)
+    if len(poses) != len(images):
+        raise SlamFusionError("one pose per image (%d images, %d poses)" % (len(images), len(poses)))
+    return handles, poses, len(images)
+
+
 ORIENT_MODES = {"none": 0, "direction": 1, "viewpoint": 2}  # SF_ORIENT_*
 FPFH_DIM = 33                                               # SF_FPFH_DIM
 
@@ -366,7 +424,7 @@ _live = weakref.WeakSet()   # every wrapper object, closed in dependency order a
 
 
 def _close_all():
-    for kind in ("Node", "Comm", "Icp", "NdtPyramid", "Ndt", "BruteForceAlignment", "Features", "Map", "Cloud", "Context"):
+    for kind in ("Node", "Comm", "Icp", "NdtPyramid", "Ndt", "BruteForceAlignment", "Features", "RangeImage", "Map", "Cloud", "Context"):
         for obj in [o for o in list(_live) if type(o).__name__ == kind]:
             try:
                 obj.close()
@@ -470,6 +528,19 @@ def load_library():
     lib.sf_ndt_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.sf_ndt_line_search_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     lib.sf_ndt_align_levels.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_range_image_default_params.restype = None
+    lib.sf_range_image_default_params.argtypes = [C.c_void_p]
+    lib.sf_visibility_default_params.restype = None
+    lib.sf_visibility_default_params.argtypes = [C.c_void_p]
+    lib.sf_range_image_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_range_image_destroy.argtypes = [C.c_void_p]
+    lib.sf_range_image_destroy.restype = None
+    lib.sf_range_image_info.argtypes = [C.c_void_p, C.c_void_p]
+    lib.sf_range_image_build.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_range_image_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_map_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_map_visibility_votes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_cloud_remove_seen_through.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.sf_map_radius_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_map_radius_graph.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_map_radius_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -931,6 +1002,17 @@ class Cloud:
                                               C.byref(n_inside)))
         return n_inside.value
 
+    def remove_seen_through(self, images, poses, min_seen=1, max_within=0, half_cols=1, half_rows=1, min_hits=1, range_margin=0.2, range_ratio=0.01, profile=False):
+        """sf_cloud_remove_seen_through: takes out the points that at least min_seen of the range images (RangeImage objects, with
+        poses [B, 4, 4] map <- sensor of the scans they were built from) class SEEN_THROUGH and at most max_within class WITHIN; in
+        place, order kept, `last_indices` reports the survivors -> stats dict (n_removed: the points taken away).  A cleaned map is
+        this call on the map's cloud, then Map.build."""
+        handles, poses, b = _images_and_poses(images, poses)
+        p, st = _visibility_params(half_cols, half_rows, min_hits, range_margin, range_ratio, profile), VisibilityStats()
+        _check(self.lib.sf_cloud_remove_seen_through(self.h, handles, _p(poses) if poses is not None else None, C.c_int64(b), C.byref(p), C.c_int(int(min_seen)),
+                                                     C.c_int(int(max_within)), C.byref(st)))
+        return st.as_dict()
+
     def compute_fpfh(self, normal_radius, radius, orient="none", toward=(0, 0, 1), cell=0.0, profile=False):
         """sf_cloud_compute_fpfh: a temporary map of the cloud, Map.estimate_normals(normal_radius) on it, then Map.compute_fpfh(radius,
         orient, toward) -> (Features in the cloud's point order, stats dict); bit for bit what those three calls give.  The cloud stays
@@ -1353,6 +1435,23 @@ class Map:
         _check(self.lib.sf_map_nn_seeded_stages(self.h, _p(q), C.c_int64(len(q)), _p(s), C.c_float(min(max_d2, 3.0e38)), _p(idx), _p(d2), _p(stage), _p(lb2)))
         return idx, d2, stage, lb2
 
+    def visibility(self, image, pose, half_cols=1, half_rows=1, min_hits=1, range_margin=0.2, range_ratio=0.01, profile=False):
+        """sf_map_visibility: every point's class (VIS_CLASSES) against one RangeImage built from a scan taken at `pose` (map <-
+        sensor, [4, 4]; None: the identity) -> (cls uint8 [n] in the original point order, stats dict).  The map stays as it is."""
+        p, st, cls = _visibility_params(half_cols, half_rows, min_hits, range_margin, range_ratio, profile), VisibilityStats(), np.zeros(max(len(self), 1), np.uint8)
+        pose = None if pose is None else _f64(pose).reshape(16)
+        _check(self.lib.sf_map_visibility(self.h, image.h, _p(pose) if pose is not None else None, C.byref(p), _p(cls), C.byref(st)))
+        return cls[:len(self)], st.as_dict()
+
+    def visibility_votes(self, images, poses, half_cols=1, half_rows=1, min_hits=1, range_margin=0.2, range_ratio=0.01, profile=False):
+        """sf_map_visibility_votes: per point the number of the images (up to 64 RangeImage objects, poses [B, 4, 4]) that class it
+        SEEN_THROUGH and WITHIN, in one pass over the map -> (seen_through uint16 [n], within uint16 [n], stats dict)."""
+        handles, poses, b = _images_and_poses(images, poses)
+        p, st, n = _visibility_params(half_cols, half_rows, min_hits, range_margin, range_ratio, profile), VisibilityStats(), len(self)
+        seen, within = np.zeros(max(n, 1), np.uint16), np.zeros(max(n, 1), np.uint16)
+        _check(self.lib.sf_map_visibility_votes(self.h, handles, _p(poses) if poses is not None else None, C.c_int64(b), C.byref(p), _p(seen), _p(within), C.byref(st)))
+        return seen[:n], within[:n], st.as_dict()
+
     def profile_launches(self, on=True):
         """sf_map_profile_launches: device events around the kernel launches of nn / knn / estimate_normals*."""
         _check(self.lib.sf_map_profile_launches(self.h, C.c_int(int(bool(on)))))
@@ -1435,6 +1534,57 @@ class Features:
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             self.lib.sf_features_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RangeImage:
+    """sf_range_image: an azimuth x elevation range image on the device (include/slamfusion.h): per pixel the
+    smallest range of the points that fall into it and the index of that point.  el_min / el_max in radians (default -25 .. +3
+    degrees)."""
+
+    def __init__(self, ctx, width=2048, height=64, el_min=None, el_max=None, min_range=0.5, max_range=120.0):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        p = RangeImageParams()
+        self.lib.sf_range_image_default_params(C.byref(p))
+        p.width, p.height, p.min_range, p.max_range = int(width), int(height), float(min_range), float(max_range)
+        if el_min is not None:
+            p.el_min = float(el_min)
+        if el_max is not None:
+            p.el_max = float(el_max)
+        _check(self.lib.sf_range_image_create(ctx.h, C.byref(p), C.byref(self.h)))
+        _live.add(self)
+
+    @property
+    def params(self):
+        p = RangeImageParams()
+        _check(self.lib.sf_range_image_info(self.h, C.byref(p)))
+        return p.as_dict()
+
+    def build(self, cloud, pose=None):
+        """sf_range_image_build: the image of `cloud` seen from `pose` ([4, 4] parent <- sensor; None: the cloud is in the sensor
+        frame already), replacing what the image held -> stats dict."""
+        st = RangeImageStats()
+        pose = None if pose is None else _f64(pose).reshape(16)
+        _check(self.lib.sf_range_image_build(self.h, cloud.h, _p(pose) if pose is not None else None, C.byref(st)))
+        return st.as_dict()
+
+    def download(self):
+        """-> (range float32 [H, W], +inf where empty; index int32 [H, W], -1 where empty)"""
+        q = self.params
+        rng, idx = np.empty((q["height"], q["width"]), np.float32), np.empty((q["height"], q["width"]), np.int32)
+        _check(self.lib.sf_range_image_download(self.h, _p(rng), _p(idx)))
+        return rng, idx
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.sf_range_image_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
