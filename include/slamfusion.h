@@ -715,6 +715,58 @@ int sf_map_visibility_votes(sf_map *m, sf_range_image *const *imgs, const double
                             sf_visibility_stats *stats);
 int sf_cloud_remove_seen_through(sf_cloud *c, sf_range_image *const *imgs, const double *poses, int64_t n_images,
                                  const sf_visibility_params *p, int min_seen, int max_within, sf_visibility_stats *stats);
+/* Scan Context place recognition over a keyframe database (extension, no reference code; Kim & Kim, IROS 2018, as used by SC-LIO-SAM
+ * and SC-A-LOAM, here without the ring-key pre-filter: the search is exhaustive and exact; DESIGN §29, restated in
+ * tests/place_ref_np.py).  Everything below is float64, unfused, evaluated left to right as written, unless said otherwise.
+ * Descriptor.  num_rings Nr (1 .. 40), num_sectors Ns (1 .. 120), min_range, max_range (metres, horizontal), sensor_height.
+ *   With a pose T [16] row-major, parent <- sensor (NULL: the identity through the same expressions): d_k = (double)p_k - T[4k+3];
+ *   x = (T[0] d0 + T[4] d1) + T[8] d2, y = (T[1] d0 + T[5] d1) + T[9] d2, z = (T[2] d0 + T[6] d1) + T[10] d2.
+ *   h2 = x x + y y; rho = sqrt(h2); az = atan2(y, x).  Sector: PI = the double nearest pi, u = (az + PI) / (2 PI) * Ns,
+ *   col = floor(u), col - Ns when col >= Ns.  Ring: v = rho / max_range * Nr, ring = floor(v).  Height: hgt = (float)(z + sensor_height).
+ *   A point with a coordinate that is not finite is n_nonfinite; else it is outside (n_outside) when min_range <= rho is false or
+ *   ring >= Nr; else below (n_below) when hgt <= 0; else binned (n_binned).  Bin [ring][col] holds the maximum hgt of its binned
+ *   points, float32; an empty bin is +0.  A 32-bit integer atomicMax on the bits of hgt, at most one per point (the lanes of a wave
+ *   that share a bin send one): a positive float orders like its bits, so the bin holds the same bits on every run.  n_filled = the bins that are not +0; n_points = n_nonfinite + n_outside +
+ *   n_below + n_binned; device_ms = the device time of the fill and the two kernels of the build.
+ * Distance.  For a descriptor a: n[j] = sqrt(sum_i a[i][j]^2), i ascending, from 0; u[i][j] = a[i][j] / n[j] where n[j] > 0, else 0;
+ *   column j is valid iff n[j] > 0.  For query q, entry c and shift s in 0 .. Ns - 1, over the j ascending for which q's column j and
+ *   c's column jc = (j + s) mod Ns are both valid: cos_j = sum_i uq[i][j] * uc[i][jc] (i ascending, multiply then add),
+ *   S = S + cos_j, V = V + 1.  d(s) = 1 - S / V, or exactly 1 when V = 0.  D(q, c) = min_s d(s); shift(q, c) = the smallest s that
+ *   attains it.  If the query's sensor stands where the entry's stood and is turned by +psi about z, shift * 2 PI / Ns ~ psi: the
+ *   candidate pose of a match is T_entry . Rz(shift * (2 PI / Ns)), computed on the host in float64.
+ * Top-k.  The k (1 .. 32) entries with the smallest (D, index); slots beyond the database size get index -1, D = +inf, shift 0 and
+ *   an all-zero pose.
+ * Database.  sf_place_db_add_cloud builds the descriptor on the device and appends it without a host round trip (entry_pose NULL:
+ *   the identity); sf_place_db_add_descriptors appends stored rows (poses NULL: identities); the unit columns of an entry are
+ *   computed once, at insertion.  The capacity doubles as the database grows and what it held is carried over; sf_place_db_clear
+ *   empties it.  sf_place_db_download: cap >= n rows, *n = n (SF_ERR_INVALID when cap is too small, *n set); desc and poses may each
+ *   be NULL.  sf_place_db_distances gives D and shift of every pair; sf_place_db_query the top-k per query with the candidate poses
+ *   (poses may be NULL); sf_place_db_query_cloud does the same for one cloud whose descriptor never leaves the device.  An empty
+ *   database is valid: distances have zero columns and every top-k slot is empty.  match_ms / select_ms: the device time of the
+ *   match (the queries' unit columns included) and of the selection.
+ * SF_ERR_INVALID, nothing touched: num_rings outside 1 .. 40 or num_sectors outside 1 .. 120; ranges or a height that are not
+ *   finite, min_range < 0 or max_range <= min_range; a pose that is not finite; a cloud of another context or with 2^31 points or
+ *   more; a descriptor given by the host (an entry or a query) that holds a negative or non-finite value; Q outside 1 .. 64; k
+ *   outside 1 .. 32. */
+typedef struct { int32_t num_rings, num_sectors; double min_range, max_range, sensor_height; } sf_place_params;
+typedef struct { int64_t n_points, n_nonfinite, n_outside, n_below, n_binned, n_filled; float device_ms; int32_t pad; } sf_place_stats;
+typedef struct { int64_t n_queries, n_entries; float match_ms, select_ms; } sf_place_match_stats;
+void sf_place_default_params(sf_place_params *p);   /* 20 x 60, 0.5 m .. 80 m, sensor 2 m above the ground */
+int sf_cloud_scan_context(sf_cloud *c, const double *pose /* [16] or NULL */, const sf_place_params *p, float *desc /* [Nr][Ns] or NULL */, sf_place_stats *stats);
+typedef struct sf_place_db sf_place_db;
+int sf_place_db_create(sf_ctx *ctx, const sf_place_params *p, sf_place_db **out);
+void sf_place_db_destroy(sf_place_db *db);
+int sf_place_db_info(const sf_place_db *db, sf_place_params *p, int64_t *n_entries);
+int sf_place_db_clear(sf_place_db *db);
+int sf_place_db_add_cloud(sf_place_db *db, sf_cloud *c, const double *pose, const double *entry_pose /* [16] */, int64_t *index, sf_place_stats *stats);
+int sf_place_db_add_descriptors(sf_place_db *db, const float *desc /* [n][Nr][Ns] */, const double *poses /* [n][16] */, int64_t n);
+int sf_place_db_download(sf_place_db *db, float *desc, double *poses, int64_t cap, int64_t *n);
+int sf_place_db_distances(sf_place_db *db, const float *queries /* [Q][Nr][Ns] */, int64_t Q /* 1 .. 64 */, double *dist /* [Q][N] */, int32_t *shift /* [Q][N] */,
+                          sf_place_match_stats *stats);
+int sf_place_db_query(sf_place_db *db, const float *queries, int64_t Q, int k /* 1 .. 32 */, int32_t *idx /* [Q][k] */, double *dist /* [Q][k] */,
+                      int32_t *shift /* [Q][k] */, double *poses /* [Q][k][16] or NULL */, sf_place_match_stats *stats);
+int sf_place_db_query_cloud(sf_place_db *db, sf_cloud *c, const double *pose, int k, int32_t *idx /* [k] */, double *dist, int32_t *shift,
+                            double *poses /* [k][16] or NULL */, sf_place_match_stats *stats, sf_place_stats *build_stats /* or NULL */);
 /* measurement (tools/knn_bench.py, tools/outlier_bench.py, tools/cluster_bench.py): with the switch on, sf_map_nn, sf_map_knn,
  * sf_map_estimate_normals[_cov|_knn], sf_map_*_outliers and sf_map_cluster_* record device events around their kernel launches (not
  * the copies); sf_map_last_launch_ms reads the latest (SF_ERR_STATE if there is none). */

@@ -237,6 +237,37 @@ def _images_and_poses(images, poses):
     return handles, poses, len(images)
 
 
+class ScanContextParams(C.Structure):
+    """sf_place_params: num_rings x num_sectors bins over [0, max_range) of horizontal range and the full turn of azimuth; a point
+    nearer than min_range is left out; sensor_height is added to z so that heights count from the ground."""
+    _fields_ = [("num_rings", C.c_int32), ("num_sectors", C.c_int32), ("min_range", C.c_double), ("max_range", C.c_double), ("sensor_height", C.c_double)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_double else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+class ScanContextStats(C.Structure):
+    """sf_place_stats: what a descriptor build saw (n_points = n_nonfinite + n_outside + n_below + n_binned; n_filled: the bins that
+    are not empty; device_ms: the fill and the two kernels)."""
+    _fields_ = [(name, C.c_int64) for name in ("n_points", "n_nonfinite", "n_outside", "n_below", "n_binned", "n_filled")] + [("device_ms", C.c_float), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_ if name != "pad"}
+
+
+class PlaceMatchStats(C.Structure):
+    """sf_place_match_stats: the pairs of a call and the device time of its match and of its selection."""
+    _fields_ = [("n_queries", C.c_int64), ("n_entries", C.c_int64), ("match_ms", C.c_float), ("select_ms", C.c_float)]
+
+    def as_dict(self):
+        return {name: (float if kind is C.c_float else int)(getattr(self, name)) for name, kind in self._fields_}
+
+
+def _scan_context_params(num_rings=20, num_sectors=60, min_range=0.5, max_range=80.0, sensor_height=2.0):
+    """The keyword form of the Scan Context calls -> ScanContextParams."""
+    return ScanContextParams(int(num_rings), int(num_sectors), float(min_range), float(max_range), float(sensor_height))
+
+
 ORIENT_MODES = {"none": 0, "direction": 1, "viewpoint": 2}  # SF_ORIENT_*
 FPFH_DIM = 33                                               # SF_FPFH_DIM
 
@@ -424,7 +455,7 @@ _live = weakref.WeakSet()   # every wrapper object, closed in dependency order a
 
 
 def _close_all():
-    for kind in ("Node", "Comm", "Icp", "NdtPyramid", "Ndt", "BruteForceAlignment", "Features", "RangeImage", "Map", "Cloud", "Context"):
+    for kind in ("Node", "Comm", "Icp", "NdtPyramid", "Ndt", "BruteForceAlignment", "Features", "RangeImage", "PlaceDB", "Map", "Cloud", "Context"):
         for obj in [o for o in list(_live) if type(o).__name__ == kind]:
             try:
                 obj.close()
@@ -541,6 +572,20 @@ def load_library():
     lib.sf_map_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_map_visibility_votes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_cloud_remove_seen_through.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.sf_place_default_params.restype = None
+    lib.sf_place_default_params.argtypes = [C.c_void_p]
+    lib.sf_cloud_scan_context.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_place_db_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_place_db_destroy.argtypes = [C.c_void_p]
+    lib.sf_place_db_destroy.restype = None
+    lib.sf_place_db_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_place_db_clear.argtypes = [C.c_void_p]
+    lib.sf_place_db_add_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_place_db_add_descriptors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    lib.sf_place_db_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.sf_place_db_distances.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_place_db_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.sf_place_db_query_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_map_radius_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_map_radius_graph.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
     lib.sf_map_radius_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -1012,6 +1057,16 @@ class Cloud:
         _check(self.lib.sf_cloud_remove_seen_through(self.h, handles, _p(poses) if poses is not None else None, C.c_int64(b), C.byref(p), C.c_int(int(min_seen)),
                                                      C.c_int(int(max_within)), C.byref(st)))
         return st.as_dict()
+
+    def scan_context(self, pose=None, **params):
+        """sf_cloud_scan_context: the Scan Context descriptor of the cloud seen from `pose` ([4, 4] parent <- sensor; None: the cloud
+        is in the sensor frame already); params: num_rings, num_sectors, min_range, max_range, sensor_height ->
+        (float32 [num_rings, num_sectors] of maximum heights, +0 where empty; stats dict)."""
+        p, st = _scan_context_params(**params), ScanContextStats()
+        desc = np.zeros((max(p.num_rings, 0), max(p.num_sectors, 0)), np.float32)
+        pose = None if pose is None else _f64(pose).reshape(16)
+        _check(self.lib.sf_cloud_scan_context(self.h, _p(pose) if pose is not None else None, C.byref(p), _p(desc), C.byref(st)))
+        return desc, st.as_dict()
 
     def compute_fpfh(self, normal_radius, radius, orient="none", toward=(0, 0, 1), cell=0.0, profile=False):
         """sf_cloud_compute_fpfh: a temporary map of the cloud, Map.estimate_normals(normal_radius) on it, then Map.compute_fpfh(radius,
@@ -1594,6 +1649,108 @@ class RangeImage:
             pass
 
 
+class PlaceDB:
+    """sf_place_db: a database of Scan Context descriptors with the poses of the keyframes they were built from, on the device
+    (include/slamfusion.h).  params: num_rings, num_sectors, min_range, max_range, sensor_height.  A query is
+    matched against every entry under every column shift; the best shift is the yaw between the two."""
+
+    def __init__(self, ctx, **params):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.h = C.c_void_p()
+        p = _scan_context_params(**params)
+        _check(self.lib.sf_place_db_create(ctx.h, C.byref(p), C.byref(self.h)))
+        _live.add(self)
+
+    @property
+    def params(self):
+        p = ScanContextParams()
+        _check(self.lib.sf_place_db_info(self.h, C.byref(p), None))
+        return p.as_dict()
+
+    @property
+    def shape(self):
+        q = self.params
+        return q["num_rings"], q["num_sectors"]
+
+    def __len__(self):
+        n = C.c_int64()
+        _check(self.lib.sf_place_db_info(self.h, None, C.byref(n)))
+        return int(n.value)
+
+    def clear(self):
+        _check(self.lib.sf_place_db_clear(self.h))
+
+    def add(self, cloud, entry_pose, pose=None):
+        """sf_place_db_add_cloud: the descriptor of `cloud` (seen from `pose`, None: already in the sensor frame) appended with the
+        keyframe's pose entry_pose ([4, 4] map <- sensor) -> (the entry's index, stats dict)."""
+        st, index = ScanContextStats(), C.c_int64()
+        pose = None if pose is None else _f64(pose).reshape(16)
+        entry_pose = None if entry_pose is None else _f64(entry_pose).reshape(16)
+        _check(self.lib.sf_place_db_add_cloud(self.h, cloud.h, _p(pose) if pose is not None else None, _p(entry_pose) if entry_pose is not None else None,
+                                              C.byref(index), C.byref(st)))
+        return int(index.value), st.as_dict()
+
+    def _rows(self, desc):
+        desc = _f32(desc)
+        rows = desc.reshape((-1,) + self.shape)
+        return rows, len(rows)
+
+    def add_descriptors(self, desc, poses=None):
+        """sf_place_db_add_descriptors: stored rows (float32 [n, num_rings, num_sectors]) and their poses ([n, 4, 4]; None: identities)"""
+        rows, n = self._rows(desc)
+        if poses is not None:
+            poses = _f64(poses).reshape(-1, 16)
+            if len(poses) != n:
+                raise SlamFusionError("one pose per descriptor (%d descriptors, %d poses)" % (n, len(poses)))
+        _check(self.lib.sf_place_db_add_descriptors(self.h, _p(rows), _p(poses) if poses is not None else None, C.c_int64(n)))
+
+    def download(self):
+        """-> (descriptors float32 [n, num_rings, num_sectors], poses float64 [n, 4, 4])"""
+        n = len(self)
+        desc, poses, got = np.zeros((n,) + self.shape, np.float32), np.zeros((n, 4, 4)), C.c_int64()
+        _check(self.lib.sf_place_db_download(self.h, _p(desc), _p(poses), C.c_int64(n), C.byref(got)))
+        return desc, poses
+
+    def distances(self, queries):
+        """sf_place_db_distances: queries float32 [Q, num_rings, num_sectors] (or one descriptor) ->
+        (D float64 [Q, n], shift int32 [Q, n], stats dict)"""
+        rows, q = self._rows(queries)
+        n, st = len(self), PlaceMatchStats()
+        dist, shift = np.zeros((q, n)), np.zeros((q, n), np.int32)
+        _check(self.lib.sf_place_db_distances(self.h, _p(rows), C.c_int64(q), _p(dist), _p(shift), C.byref(st)))
+        return dist, shift, st.as_dict()
+
+    def query(self, queries, k):
+        """sf_place_db_query: per query the k entries with the smallest (D, index) -> dict(idx int32 [Q, k] (-1: no entry), dist float64
+        [Q, k] (+inf there), shift int32 [Q, k], poses float64 [Q, k, 4, 4]: T_entry . Rz(shift 2 pi / num_sectors), stats)"""
+        rows, q = self._rows(queries)
+        kk, st = max(int(k), 1), PlaceMatchStats()
+        idx, dist, shift, poses = np.zeros((q, kk), np.int32), np.zeros((q, kk)), np.zeros((q, kk), np.int32), np.zeros((q, kk, 4, 4))
+        _check(self.lib.sf_place_db_query(self.h, _p(rows), C.c_int64(q), C.c_int(int(k)), _p(idx), _p(dist), _p(shift), _p(poses), C.byref(st)))
+        return dict(idx=idx, dist=dist, shift=shift, poses=poses, stats=st.as_dict())
+
+    def query_cloud(self, cloud, k, pose=None):
+        """sf_place_db_query_cloud: the same for one cloud, whose descriptor is built and matched on the device -> the dict of `query`
+        with Q = 1 and build_stats, the statistics of the descriptor build"""
+        kk, st, bst = max(int(k), 1), PlaceMatchStats(), ScanContextStats()
+        idx, dist, shift, poses = np.zeros((1, kk), np.int32), np.zeros((1, kk)), np.zeros((1, kk), np.int32), np.zeros((1, kk, 4, 4))
+        pose = None if pose is None else _f64(pose).reshape(16)
+        _check(self.lib.sf_place_db_query_cloud(self.h, cloud.h, _p(pose) if pose is not None else None, C.c_int(int(k)), _p(idx), _p(dist), _p(shift), _p(poses),
+                                                C.byref(st), C.byref(bst)))
+        return dict(idx=idx, dist=dist, shift=shift, poses=poses, stats=st.as_dict(), build_stats=bst.as_dict())
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.sf_place_db_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Ndt:
     """sf_ndt: Normal Distributions Transform registration of scans against the per-voxel Gaussians of `target` (a Cloud or a Map)
     at cell = resolution (include/slamfusion.h).  neighbours: 1 (the home cell) or 7 (plus the face neighbours)."""
@@ -2132,6 +2289,35 @@ def global_register(src_cloud, src_features, dst_cloud, dst_features, distance_t
     res = solver.align_batch(icp_mode)
     chosen = max(range(len(res)), key=lambda k: (res[k]["fitness"], -res[k]["rmse"], k))
     out.update(T=res[chosen]["T64"], fitness=res[chosen]["fitness"], rmse=res[chosen]["rmse"], icp=res, chosen=chosen)
+    return out
+
+
+def place_register(db, cloud, k=4, pose=None, icp=None, icp_mode="o3d_p2p"):
+    """Pose of `cloud` (a scan in the sensor frame, or seen from `pose`) in the map a PlaceDB's keyframes were taken in, without a
+    prior: PlaceDB.query_cloud, then the best candidate T_entry . Rz(shift 2 pi / num_sectors).
+    icp: None, or a factory icp(batch) -> an Icp with its target set; the candidate poses are then refined as ONE batch of the batched
+    ICP and the result with the best (fitness, -rmse) is returned.
+    -> dict(T float64 [4, 4], found, index, shift, dist (of the candidate T came from), candidates: the query_cloud dict, icp: the
+    batch results or None, chosen: the index into the candidates)."""
+    cand = db.query_cloud(cloud, k, pose)
+    live = [j for j in range(cand["idx"].shape[1]) if cand["idx"][0, j] >= 0]
+    out = dict(T=np.eye(4), found=bool(live), index=-1, shift=0, dist=float("inf"), candidates=cand, icp=None, chosen=None)
+    if not live:
+        return out
+    chosen, res = 0, None
+    if icp is not None:
+        scan = cloud.download()
+        if pose is not None:                     # the batch wants the scan in the sensor frame: R^T (p - t)
+            T = _f64(pose).reshape(4, 4)
+            scan = ((scan.astype(np.float64) - T[:3, 3]) @ T[:3, :3]).astype(np.float32)
+        solver = icp(len(live))
+        solver.set_source_batch(np.broadcast_to(scan, (len(live),) + scan.shape))
+        solver.set_initial_batch(np.stack([cand["poses"][0, j] for j in live]))
+        res = solver.align_batch(icp_mode)
+        chosen = max(range(len(res)), key=lambda j: (res[j]["fitness"], -res[j]["rmse"], -j))
+    j = live[chosen]
+    out.update(T=res[chosen]["T64"] if res is not None else cand["poses"][0, j].copy(), index=int(cand["idx"][0, j]), shift=int(cand["shift"][0, j]),
+               dist=float(cand["dist"][0, j]), icp=res, chosen=chosen)
     return out
 
 
