@@ -1190,6 +1190,11 @@ int sf_bf_set_source_cloud(sf_bf *bf, sf_cloud *cloud);
 int sf_bf_set_target(sf_bf *bf, const float *xyz, int64_t n);
 int sf_bf_set_target_map(sf_bf *bf, sf_map *map);
 int sf_bf_reset_first_alignment(sf_bf *bf, int value);
+/* Refused with the handle's state untouched (previous / best transformation, first-alignment flag, last result):
+ * SF_ERR_STATE without a source or a target, for a target with no point and for a map window that accepts none;
+ * SF_ERR_INVALID for a step that is not finite and > 0, a range that is not finite and >= 0, a sequence of more
+ * than 4 096 entries, more than 2^20 candidates in all or more than 65 535 in one x slice.  A source point with a
+ * non-finite coordinate adds 0 to every score and still counts in its divisor. */
 int sf_bf_align_clouds(sf_bf *bf, int *found);
 int sf_bf_first_alignment_completed(sf_bf *bf);
 int sf_bf_get_best_transformation(sf_bf *bf, float T[16]);

@@ -50,6 +50,10 @@ __global__ void k_bf_soa(const float *__restrict__ aos, int64_t n, float *__rest
 // every (candidate, source point) squared NN distance: grid (point blocks, candidates); T * Vector4f(p, 1) in float32,
 // unfused, column combination with k ascending (brute_force_alignment.cpp:98); NN d2 unbounded (:102).  The search is
 // the wave-cooperative one of the ICP kernels (every lane of a wave takes part, the tail included).
+// A source point with a non-finite coordinate has no neighbour: it adds 0 to its candidate's sum and still counts in the
+// divisor n, so k such points scale every score by (n - k) / n.  A departure from the reference, whose kd-tree descent
+// on a NaN query is undefined; pinned by tests/test_gpu_bf_direct.py.  (hit.j < 0 happens in no other way: the
+// threshold is unbounded and sf_bf_align_clouds refuses a target or window with nothing to search.)
 template <bool WINDOW>
 __global__ __launch_bounds__(BLK, 4) void k_bf_score(SfGrid g, SfWindow w, const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z, int n,
                                                      const float *__restrict__ poses, float *__restrict__ d2_out)
@@ -90,6 +94,23 @@ __global__ __launch_bounds__(64) void k_bf_finish(const float *__restrict__ d2, 
         }
     }
     if (lane == 0) scores[c] = __fdiv_rn(acc, (float)n);
+}
+
+// What sf_bf_align_clouds accepts of a candidate grid.  One sequence: 4 096 entries (the node's longest has 18).  All
+// four together: 2^20 candidates = 64 MiB of host matrices (the node asks for 7 776).
+constexpr size_t BF_MAX_SEQUENCE = 4096;
+constexpr size_t BF_MAX_CANDIDATES = (size_t)1 << 20;
+
+// The number of entries test_sequence(range, step) would have, without building it; 0 for a step that is not a finite
+// positive number or a range that is not a finite non-negative one, BF_MAX_SEQUENCE + 1 for anything longer than
+// BF_MAX_SEQUENCE.  The loop below runs for every int i with (float)i < b, b = range / (2 * step) + 1 rounded as there:
+// ceil(b) times, b >= 1.  (b is compared before it is converted: it may be +inf, from a tiny step.)
+size_t sequence_length(float range, float step)
+{
+    if (!(std::isfinite(step) && step > 0.0f && std::isfinite(range) && range >= 0.0f)) return 0;
+    const float b = range / (2 * step) + 1;
+    if (!(b <= (float)(BF_MAX_SEQUENCE / 2))) return BF_MAX_SEQUENCE + 1;
+    return 2 * (size_t)std::ceil(b);
 }
 
 // brute_force_alignment.cpp:148-180
@@ -213,17 +234,36 @@ extern "C" int sf_bf_align_clouds(sf_bf *bf, int *found)
     SF_CHECK(bf && found, SF_ERR_INVALID, "bad arguments");
     SF_CHECK(bf->target && bf->target->built, SF_ERR_STATE, "no target set");
     SF_CHECK(bf->n > 0, SF_ERR_STATE, "no source cloud set");
+    // Every refusal stands here, before anything is allocated, launched (the window count apart) or written to *bf.
+    // The grid first, by arithmetic: a zero step would never leave test_sequence, a tiny one would ask for a vector
+    // no host has.
+    const size_t lx = sequence_length(bf->x_range, bf->x_step), ly = sequence_length(bf->y_range, bf->y_step);
+    const size_t lz = sequence_length(bf->z_range, bf->z_step), lw = sequence_length(bf->yaw_range, bf->yaw_step);
+    SF_CHECK(lx && ly && lz && lw, SF_ERR_INVALID, "every step must be finite and > 0, every range finite and >= 0");
+    SF_CHECK(lx <= BF_MAX_SEQUENCE && ly <= BF_MAX_SEQUENCE && lz <= BF_MAX_SEQUENCE && lw <= BF_MAX_SEQUENCE, SF_ERR_INVALID,
+             "a candidate sequence has more than %zu entries", BF_MAX_SEQUENCE);
+    SF_CHECK(lx * ly * lz * lw <= BF_MAX_CANDIDATES, SF_ERR_INVALID, "%zu candidate poses, more than %zu", lx * ly * lz * lw, BF_MAX_CANDIDATES); // (<= 2^48: no overflow)
+    const size_t per_x = ly * lz * lw;
+    const size_t total = lx * per_x;
+    SF_CHECK(per_x <= 65535, SF_ERR_INVALID, "candidate slice of %zu poses does not fit one launch", per_x);
+    const int n = (int)bf->n;
+    SF_CHECK((double)per_x * (double)n < 2.0e9, SF_ERR_OVERFLOW, "%zu candidates x %d points per slice is too large", per_x, n);
+    // Then the search set.  With nothing to search every candidate would score 0 (k_bf_score) and candidate 0 would
+    // take the start-up lock.
+    SF_CHECK(bf->target->grid.n > 0, SF_ERR_STATE, "the target has no point");
+    if (bf->target->window.kind) {
+        int64_t in_window = 0;
+        SF_TRY(sf_map_window_count(bf->target, &in_window));
+        SF_CHECK(in_window > 0, SF_ERR_STATE, "the target's window accepts no point");
+    }
     SF_HIP(hipSetDevice(bf->ctx->device));
     hipStream_t st = bf->ctx->stream;
     const std::vector<float> xs = test_sequence(bf->x_range, bf->x_step), ys = test_sequence(bf->y_range, bf->y_step);
     const std::vector<float> zs = test_sequence(bf->z_range, bf->z_step), ws = test_sequence(bf->yaw_range, bf->yaw_step);
-    const size_t per_x = ys.size() * zs.size() * ws.size();
-    const size_t total = xs.size() * per_x;
-    SF_CHECK(per_x > 0 && per_x <= 65535, SF_ERR_INVALID, "candidate slice of %zu poses does not fit one launch", per_x);
-    const int n = (int)bf->n;
+    SF_CHECK(xs.size() == lx && ys.size() == ly && zs.size() == lz && ws.size() == lw, SF_ERR_STATE, "candidate sequences of %zu %zu %zu %zu entries where %zu %zu %zu %zu were counted",
+             xs.size(), ys.size(), zs.size(), ws.size(), lx, ly, lz, lw);
     const int nblocks = (int)sf::div_up(n, BLK);
     SF_TRY(bf->poses.reserve(sizeof(float) * 12 * per_x));
-    SF_CHECK((double)per_x * (double)n < 2.0e9, SF_ERR_OVERFLOW, "%zu candidates x %d points per slice is too large", per_x, n);
     SF_TRY(bf->partials.reserve(sizeof(float) * per_x * (size_t)n)); // one squared distance per (candidate of the slice, point)
     SF_TRY(bf->scores.reserve(sizeof(float) * per_x));
     std::vector<float> T(16 * total), hpose(12 * per_x), hscore(per_x);

@@ -3,9 +3,9 @@
 // Replaces the N serial FLANN kd-tree descents of
 // localization/src/icp_point_to_point.cpp:64-69 (sourceTargetCorrespondences) and the
 // Open3D hybrid search behind localization_python/.../localization_node.py:233-237.
-// One lane per query.  Two forms: nn_search (each lane on its own; map queries, REF_CPP mode,
-// the brute-force scorer) and nn_search_wave (the 64 lanes of a wave share the work; the ICP hot
-// kernel k_nn_red).
+// One lane per query.  Two forms: nn_search (each lane on its own; map queries, REF_CPP mode)
+// and nn_search_wave (the 64 lanes of a wave share the work; the ICP hot kernel k_nn_red, and
+// the brute-force scorer k_bf_score as nn_search_wave<WINDOW, true>, rings included).
 //
 // Layout: the map is sorted by cell (x fastest), so a row of cells is one contiguous candidate
 // range, and ONE 16-byte look-up returns the bounds of the three cells of a row.  The query's own
