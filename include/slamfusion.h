@@ -152,7 +152,9 @@ int sf_cloud_voxel_out_ids64(sf_cloud *c, int64_t *ids, int64_t cap_values, int6
 /* ------------------------------------------------------------------ map (NN index) */
 /* a6: setTargetPointCloud — icp_point_to_point.cpp:49-55.  Instead of a FLANN kd-tree
  * over a 10 m crop rebuilt every 3 m, the WHOLE map gets one device-resident uniform-grid
- * index (cell size `cell`, 0 = automatic); the reference's crop becomes a window. */
+ * index (cell size `cell`, 0 = automatic); the reference's crop becomes a window.
+ * An axis holds at most 2^24 = 16 777 216 cells (float32 counts no further): an explicit `cell` that needs more on any axis, or a
+ * table that does not fit, is SF_ERR_OVERFLOW and the map stays unbuilt; an automatic cell grows until both hold. */
 int sf_map_create(sf_ctx *ctx, sf_map **out);
 void sf_map_destroy(sf_map *m);
 int sf_map_build(sf_map *m, sf_cloud *cloud, float cell);

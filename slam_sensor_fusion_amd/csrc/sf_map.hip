@@ -273,12 +273,12 @@ extern "C" int sf_map_build(sf_map *m, sf_cloud *cloud, float cell)
         for (int d = 0; d < 3; ++d) {
             org[d] = n_valid > 0 ? grid_origin(mm.mn[d], h, m->origin_lattice) : 0.0f;
             double c = std::floor((n_valid > 0 ? (double)mm.mx[d] - (double)org[d] : 0.0) / h) + 1;
-            if (c > 2.0e9) ok = false;
+            if (c > 16777216.0) ok = false; // grid_cell clamps with (float)(dim - 1): beyond 2^24 cells that float can be dim itself, a cell past the grid
             dim[d] = ok ? (int)c : 1;
             cells *= c;
         }
         if (ok && cells <= max_cells) break;
-        SF_CHECK(cell <= 0, SF_ERR_OVERFLOW, "cell %.4g gives too many cells for this extent (%.3g; this device holds a table of %.3g)", (double)cell, cells, max_cells);
+        SF_CHECK(cell <= 0, SF_ERR_OVERFLOW, "cell %.4g gives too many cells for this extent (%.3g; this device holds a table of %.3g, an axis 2^24 cells)", (double)cell, cells, max_cells);
         h *= 1.5;
     }
     GridGeom g;
@@ -601,7 +601,7 @@ extern "C" int sf_map_patch(sf_map *m, sf_cloud *cloud, int *patched)
     double cells = 1;
     for (int d = 0; d < 3; ++d) {
         const double c = std::floor(((double)new_mx[d] - (double)old.org[d]) / h) + 1;
-        if (c > 2.0e9) return rebuild(SF_PATCH_LIMITS);
+        if (c > 16777216.0) return rebuild(SF_PATCH_LIMITS); // (more than 2^24 cells on an axis: the build refuses)
         g.org[d] = pg.org[d] = old.org[d];
         g.dim[d] = pg.dim[d] = (int)c;
         pg.old_dim[d] = old.dim[d];
