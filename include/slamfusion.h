@@ -1471,6 +1471,31 @@ int sf_test_cloud_minmax(sf_cloud *c, int enqueue_form, float mn[3], float mx[3]
  * SF_ERR_INVALID: a NULL argument, a map without an index, batch outside [1, 64], n outside [1, 2^20], form not 0 or 1. */
 int sf_test_query_order(sf_map *map, const float *points, int batch, int64_t n, const double *poses, int form, int table, uint16_t *keys, float *ordered);
 
+/* The neighbour cache that the launch list of the latest sf_icp_align_batch_async / sf_icp_align_batch left behind, read back
+ * (csrc/sf_icp_testhooks.hpp).  Host code alone: the context's stream is synchronised and the arrays are
+ * copied out; no kernel is launched, nothing is written on the device and no member of the object changes, so the alignment's
+ * results and every later alignment are what they would have been without the call.
+ * For scan b, per cache entry in cache order (entry i of the scan is slot b * n + i of the lane's arrays):
+ *   x0 [n][3]   the source point the entry belongs to, as the kernels read it (the ordered copy when the queries were ordered)
+ *   orig [n]    its index in the scan as given: i without ordering, the id the tile sort kept, -1 under the plain cell order
+ *               (its move kernel keeps no ids).  May be NULL.
+ *   nbr [n][3], j [n]   the cached neighbour and its position in the index (negative: none within the acceptance radius)
+ *   e [n]       E = D + M_then of the reuse certificate (<= 0: no search behind the entry)
+ * and in *info the scan's pose, its motion bound (IcpState::motion) and counters as the last launch left them.
+ * cap: entries the arrays hold.  cap = 0 with every array NULL is the size query: *info alone (info->n = entries per scan).
+ * SF_ERR_STATE, touching nothing: no alignment yet, or the latest one was REF_CPP, the single launch (its cache lives in registers),
+ * sharded, stepped or ran with the neighbour reuse off.  SF_ERR_INVALID, touching nothing: b outside the batch, cap below n, a
+ * NULL array that is needed. */
+typedef struct sf_icp_cache_info {
+    double T[16];
+    double motion;
+    int64_t n;
+    int32_t batch, mode;
+    int32_t cache_live, n_research, iterations;
+    int32_t ordered; /* 0: as given, 1: cell order (no ids kept), 2: tile order (ids kept) */
+} sf_icp_cache_info;
+int sf_icp_test_download_cache(sf_icp *icp, int b, int64_t cap, float *x0, int32_t *orig, float *nbr, int32_t *j, float *e, sf_icp_cache_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,12 @@ class IcpResult(C.Structure):
                     fitness=float(self.fitness), rmse=float(self.rmse))
 
 
+class IcpCacheInfo(C.Structure):
+    """sf_icp_cache_info: what sf_icp_test_download_cache reads of a scan's state."""
+    _fields_ = [("T", C.c_double * 16), ("motion", C.c_double), ("n", C.c_int64), ("batch", C.c_int32), ("mode", C.c_int32),
+                ("cache_live", C.c_int32), ("n_research", C.c_int32), ("iterations", C.c_int32), ("ordered", C.c_int32)]
+
+
 COV_FLAGS = {"few_corr": 1, "singular": 2, "degenerate_trans": 4, "degenerate_rot": 8}  # SF_COV_*
 
 
@@ -595,6 +601,7 @@ def load_library():
     lib.sf_test_compact.argtypes = [C.c_void_p, C.c_void_p]
     lib.sf_test_cloud_minmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.sf_test_query_order.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.sf_icp_test_download_cache.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -2040,6 +2047,20 @@ class Icp:
 
     def test_inject_barrier_timeout(self):
         _check(self.lib.sf_icp_test_inject_barrier_timeout(self.h))
+
+    def test_download_cache(self, b=0):
+        """Test hook (sf_icp_test_download_cache): the neighbour cache of scan b as the launch list of the latest alignment left it,
+        read only.  -> dict: x0 [n][3] (the query's source point), orig [n] (its index in the scan as given, -1 where the ordering
+        kept none), nbr [n][3], j [n] (index position, negative: none), e [n], and T (4x4), motion, cache_live, n_research,
+        iterations, mode, batch, ordered of the scan's state."""
+        info = IcpCacheInfo()
+        _check(self.lib.sf_icp_test_download_cache(self.h, int(b), 0, None, None, None, None, None, C.addressof(info)))
+        n = int(info.n)
+        x0, nbr = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        orig, j, e = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.float32)
+        _check(self.lib.sf_icp_test_download_cache(self.h, int(b), n, _p(x0), _p(orig), _p(nbr), _p(j), _p(e), C.addressof(info)))
+        return dict(x0=x0, orig=orig, nbr=nbr, j=j, e=e, T=np.array(info.T[:], np.float64).reshape(4, 4), motion=float(info.motion), n=n, batch=info.batch, mode=info.mode,
+                    cache_live=info.cache_live, n_research=info.n_research, iterations=info.iterations, ordered=info.ordered)
 
     def set_nn_reuse(self, on=True):
         _check(self.lib.sf_icp_set_nn_reuse(self.h, C.c_int(int(on))))

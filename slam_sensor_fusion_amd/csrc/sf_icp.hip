@@ -4553,6 +4553,13 @@ extern "C" int sf_test_reduce_partials(sf_ctx *ctx, int nrec, int nt, const doub
     return test_reduce_partials_run(ctx, nrec, nt, part, nblocks, out);
 }
 
+// ------------------------------------------------------------------ test hook of the neighbour cache (sf_icp_testhooks.hpp: reads only)
+extern "C" int sf_icp_test_download_cache(sf_icp *icp, int b, int64_t cap, float *x0, int32_t *orig, float *nbr, int32_t *j, float *e, sf_icp_cache_info *info)
+{
+    SF_CHECK(icp, SF_ERR_INVALID, "sf_icp_test_download_cache: icp is NULL");
+    return test_download_cache_run<sf_icp>(icp, b, cap, x0, orig, nbr, j, e, info);
+}
+
 // ------------------------------------------------------------------ test hook of the query order (sf_order.hpp, launch_order_plain)
 // The ordering kernels on host points: k_order_hist -> k_order_scan -> form 0: k_order_scatter + k_order_gather, form 1:
 // k_order_move, with buffers of the hook's own.  The ordered planes start as 0xff bytes: a slot no kernel wrote shows.

@@ -5,6 +5,8 @@
 // rsqrt_nr / jacobi_sym, sf_cov.hpp's recip_nr and that file's robust_weight as they are: no copy of a routine, no second implementation.  They
 // stay in the ICP unit because robust_weight and the instantiations they pin (NREC_COV_*, SBLK) are ICP's.  Not part
 // of the drop-in boundary and no reference counterpart (the reference calls Eigen::JacobiSVD and Open3D's solvers).
+// At the end of the file, host code alone: test_download_cache_run, the read-only copy of the launch list's neighbour cache behind
+// sf_icp_test_download_cache.
 //
 // sf_test_linalg runs one case per thread in workgroups of 64: one lane working on its own little matrix is how production
 // runs these routines.  The reductions run in ONE workgroup of BLK (wave and block forms) or NT (reduce_partials) threads.
@@ -196,4 +198,77 @@ int test_reduce_partials_run(sf_ctx *ctx, int nrec, int nt, const double *part, 
         SF_TEST_RP(NREC_PLANE, RBLK);
 #undef SF_TEST_RP
     });
+}
+
+// ------------------------------------------------------------------ the neighbour cache of the last alignment, read back
+// sf_icp_test_download_cache (include/slamfusion.h): host code alone.  What the launch list's kernels left in
+// the lane of the latest alignment -- per entry the query it belongs to, the cached neighbour, its index position and E, and the
+// scan's pose, motion bound and counters -- copied out after a stream synchronise.  No launch, no write on the device, no member
+// of the object changed (the object comes in const).  A template because struct sf_icp (sf_icp_object.hpp) is declared behind this
+// file; it is instantiated once, by the entry point at the end of sf_icp.hip.
+template <class Icp>
+int test_download_cache_run(const Icp *icp, int b, int64_t cap, float *x0, int32_t *orig, float *nbr, int32_t *j, float *e, sf_icp_cache_info *info)
+{
+    const auto &ln = icp->cur();
+    const auto &M = ln.meta;
+    // the launch list, enqueued whole, with the neighbour reuse on: the single launch (its cache lives in registers) and REF_CPP
+    // leave the schedule of the lane undescribed (zeros)
+    SF_CHECK(M.valid && M.batch > 0 && !icp->last_fused && !icp->shard && (M.mode == SF_ICP_O3D_P2P || M.mode == SF_ICP_P2PLANE) && M.sched.mode == M.mode && M.sched.whole &&
+                 M.sched.reuse,
+             SF_ERR_STATE, "sf_icp_test_download_cache: the latest alignment of this object is no O3D_P2P / P2PLANE launch list with neighbour reuse (none yet, REF_CPP, the single launch, sharded, stepped or reuse off)");
+    const auto &ss = icp->srcs[M.src_set];
+    SF_CHECK(ss.have_source && ss.batch == M.batch && ss.n > 0 && ln.qcache.p && ln.state.p && icp->cache_n >= ss.n * ss.batch, SF_ERR_STATE,
+             "sf_icp_test_download_cache: the source or the cache of the latest alignment is gone");
+    SF_CHECK(b >= 0 && b < M.batch, SF_ERR_INVALID, "sf_icp_test_download_cache: scan %d outside [0, %d)", b, M.batch);
+    const int64_t n = ss.n;
+    const bool sized = cap == 0 && !x0 && !orig && !nbr && !j && !e; // the size query: info alone
+    SF_CHECK(sized || (cap >= n && x0 && nbr && j && e), SF_ERR_INVALID, "sf_icp_test_download_cache: buffers of %lld entries (or NULL) for a scan of %lld", (long long)cap, (long long)n);
+    SF_CHECK(!icp->ordered || ln.Xq.p, SF_ERR_STATE, "sf_icp_test_download_cache: the ordered queries are gone");
+    SF_HIP(hipSetDevice(icp->ctx->device));
+    hipStream_t st = icp->ctx->stream; // (waits for every lane's alignment: LaneScope)
+    SF_HIP(hipStreamSynchronize(st));
+    IcpState S;
+    SF_HIP(hipMemcpyAsync(static_cast<void *>(&S), static_cast<const IcpState *>(ln.state.p) + b, sizeof(IcpState), hipMemcpyDeviceToHost, st));
+    const size_t first = (size_t)b * (size_t)n, cn = (size_t)icp->cache_n;
+    const bool tiled = icp->ordered && icp->tile_on && ln.qidx.p; // the tile sort keeps the ids of its ordered queries; the move kernel of the plain order keeps none
+    std::vector<float> xs, es;
+    std::vector<float4> c1, c2;
+    std::vector<uint32_t> ids;
+    if (!sized) {
+        xs.resize(3 * (size_t)n);
+        c1.resize((size_t)n);
+        const float *X = static_cast<const float *>(icp->ordered ? ln.Xq.p : ss.X0.p);
+        for (int a = 0; a < 3; ++a)
+            SF_HIP(hipMemcpyAsync(xs.data() + (size_t)a * n, X + (size_t)a * (size_t)ss.plane + first, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
+        const float4 *qc = static_cast<const float4 *>(ln.qcache.p);
+        SF_HIP(hipMemcpyAsync(c1.data(), qc + first, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+        if (M.mode == SF_ICP_P2PLANE) { // (neighbour's normal, E)
+            c2.resize((size_t)n);
+            SF_HIP(hipMemcpyAsync(c2.data(), qc + cn + first, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+        } else { // E alone, as floats
+            es.resize((size_t)n);
+            SF_HIP(hipMemcpyAsync(es.data(), reinterpret_cast<const float *>(qc + cn) + first, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st));
+        }
+        if (tiled && orig) {
+            ids.resize((size_t)n);
+            SF_HIP(hipMemcpyAsync(ids.data(), static_cast<const uint32_t *>(ln.qidx.p) + first, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+        }
+    }
+    SF_HIP(hipStreamSynchronize(st));
+    for (int64_t i = 0; i < (sized ? 0 : n); ++i) {
+        for (int a = 0; a < 3; ++a) x0[3 * i + a] = xs[(size_t)a * n + i];
+        nbr[3 * i] = c1[i].x; nbr[3 * i + 1] = c1[i].y; nbr[3 * i + 2] = c1[i].z;
+        std::memcpy(&j[i], &c1[i].w, sizeof(int32_t));
+        e[i] = M.mode == SF_ICP_P2PLANE ? c2[i].w : es[i];
+        if (orig) orig[i] = !icp->ordered ? (int32_t)i : tiled ? (int32_t)((int64_t)ids[i] - (int64_t)first) : -1;
+    }
+    if (info) {
+        std::memcpy(info->T, S.T, sizeof(double) * 16);
+        info->motion = S.motion;
+        info->n = n;
+        info->batch = M.batch; info->mode = M.mode;
+        info->cache_live = S.cache_live; info->n_research = S.n_research; info->iterations = S.iterations;
+        info->ordered = !icp->ordered ? 0 : tiled ? 2 : 1;
+    }
+    return SF_OK;
 }

@@ -120,6 +120,24 @@ def test_stepping_equals_one_shot(api, ctx, world):
     bitwise(one, stepped)
 
 
+def fuzz_map(rng, kind, n_map, ext, clusters=400):
+    """uniform slab (0), clustered with every seventh point an exact twin of its neighbour in the array (1), lattice (2), two planes (3)"""
+    if kind == 0:
+        m = rng.uniform(-ext, ext, (n_map, 3)) * [1.0, 1.0, 0.2]
+    elif kind == 1:
+        c = rng.uniform(-ext, ext, (clusters, 3))
+        m = c[rng.integers(0, clusters, n_map)] + rng.normal(0, 0.2, (n_map, 3))
+        k7 = len(m[1::7])
+        m[::7][:k7] = m[1::7]
+    elif kind == 2:
+        m = np.round(rng.uniform(-ext, ext, (n_map, 3)) * [1.0, 1.0, 0.2] * 8) / 8
+    else:
+        m = rng.uniform(-ext, ext, (n_map, 3))
+        m[: n_map // 2, 2] = 0.0
+        m[n_map // 2:, 0] = 2.0
+    return m.astype(np.float32)
+
+
 @pytest.mark.parametrize("scan_from", ["all", "unique"])
 @pytest.mark.parametrize("kind", [0, 1, 2, 3])
 def test_clustered_duplicated_lattice_and_planar_maps(api, ctx, synth, kind, scan_from):
@@ -136,20 +154,7 @@ def test_clustered_duplicated_lattice_and_planar_maps(api, ctx, synth, kind, sca
     rng = np.random.default_rng(780 + kind)
     n_map = int(rng.integers(100_000, 400_000))
     ext = float(rng.choice([6.0, 12.0, 20.0]))
-    if kind == 0:
-        m = rng.uniform(-ext, ext, (n_map, 3)) * [1.0, 1.0, 0.2]
-    elif kind == 1:
-        c = rng.uniform(-ext, ext, (400, 3))
-        m = c[rng.integers(0, 400, n_map)] + rng.normal(0, 0.2, (n_map, 3))
-        k7 = len(m[1::7])
-        m[::7][:k7] = m[1::7]
-    elif kind == 2:
-        m = np.round(rng.uniform(-ext, ext, (n_map, 3)) * [1.0, 1.0, 0.2] * 8) / 8
-    else:
-        m = rng.uniform(-ext, ext, (n_map, 3))
-        m[: n_map // 2, 2] = 0.0
-        m[n_map // 2:, 0] = 2.0
-    m = m.astype(np.float32)
+    m = fuzz_map(rng, kind, n_map, ext)
     mp = api.Map(ctx, api.Cloud(ctx, m), float(rng.choice([0.0, 0.25, 0.5])))
     mp.estimate_normals(0.4)
     n_scan = int(rng.integers(131_073, 160_000))

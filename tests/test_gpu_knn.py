@@ -6,23 +6,9 @@ import os
 import numpy as np
 import pytest
 
+from reuse_ref_np import obb_accept, sphere_accept   # (the window's accept rule: shared with tests/test_gpu_reuse_bound.py)
+
 pytestmark = pytest.mark.gpu
-
-
-def sphere_accept(P, centre, radius):
-    c = np.asarray(centre, np.float32)
-    d = c[None, :] - P
-    return ((d[:, 0] * d[:, 0]) + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2] < np.float32(float(radius) * float(radius))
-
-
-def obb_accept(P, centre, R, extent):
-    d = P.astype(np.float64) - np.asarray(centre, np.float64)[None, :]
-    R = np.asarray(R, np.float64).reshape(3, 3)
-    ok = np.ones(len(P), bool)
-    for k in range(3):
-        proj = (d[:, 0] * R[0, k] + d[:, 1] * R[1, k]) + d[:, 2] * R[2, k]
-        ok &= np.abs(proj) <= np.asarray(extent, np.float64)[k] / 2
-    return ok
 
 
 def knn_ref(mp, q, k, max_d2=np.inf, accept=None, positions=False):
